@@ -24,14 +24,21 @@ Contract (driver):  python bench.py --gpus N --steps K --warmup W
     own closing synchronize); the max over ranks is the time; rank 0 prints ONE JSON line.
   * `--gpus N` > 1 without an outer launcher (no WORLD_SIZE): the N ranks are started here, as
     ONE `torch.distributed.run` child before any GPU call; this process exits with its status.
-  * After the timed region the line's `parity` certifies the timed path's output (the assembled
-    frame's Reinhard bytes against the reference's SHA-256, every rank's f64 rows against a
-    one-launch render); a failed check exits 3.
+  * A plain run does only that: set up, warm up, time the K frames, print the line (`parity`
+    and `cpu_baseline` null, no extra fields).  `per_rank` and `roofline` come from the timed
+    region's own HIP events and the committed PMC summaries, so they cost no run of their own.
+  * `--dump-outputs DIR`: after the timed region, the last timed frame as DIR/<name>.npy —
+    `hdr` (this rank's rows of the HDR framebuffer, float64 or float32 as --hdr; `hdr_rank<r>`
+    at N>1), `ldr` (rank 0: the assembled frame's tonemapped bytes as float32) and `rows` (the
+    image rows the arrays hold, float64).  A frame larger than the 60 MB budget is written as a
+    fixed, seeded sample of whole rows (dump_rows); the scene and camera are the same in every
+    run, so two builds can be compared array for array.
+  * `--full` adds everything else.  After the timed region the line's `parity` certifies the
+    timed path's output (the assembled frame's Reinhard bytes against the reference's SHA-256,
+    every rank's f64 rows against a one-launch render); a failed check exits 3.
 
-Extra fields (each outside the headline's timed region, with its own timing): `per_rank`
-(render / gather / assembly per frame on every rank), `roofline` (HBM-write bound of the trace
-kernel from live per-launch HIP events; traffic and VALU counters from the committed PMC
-summaries), `single_launch` (one launch per frame, the round-3 headline path), `weak_frames`
+Extra fields under `--full` (each outside the headline's timed region, with its own timing):
+`single_launch` (one launch per frame, the round-3 headline path), `weak_frames`
 (every rank its own whole frames), `c4_tiled` (BASELINE config 4: the 7680×4320 frame through
 the same path), and at N=1 `roofline_f32` (the north star's float3 framebuffer),
 `moving_camera` (a new camera position every frame), `d2h` (the drop-in RenderImage() with
@@ -93,9 +100,17 @@ def parse_args(argv=None):
                          "the HIP events on the launch stream around the whole timed region.  "
                          "Default: 0 at N=1 (in-region event records cost ~30 us of a 20-frame "
                          "region, tools/host_overhead.py), 4 at N>1")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: the parity certification of the timed path's "
+                         "output, the extra fields (other precisions, configs and launch shapes) "
+                         "and the CPU baseline; a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed frame (HDR rows, tonemapped bytes) as "
+                         "DIR/<name>.npy after the timed region")
     ap.add_argument("--no-extras", action="store_true",
-                    help="headline only (no extra fields)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                    help="with --full: no extra fields")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: no cpu_baseline")
     ap.add_argument("--cpu-frames", type=int, default=6,
                     help="reference frames timed for cpu_baseline (first one is warm-up)")
     return ap.parse_args(argv)
@@ -623,8 +638,66 @@ def frame_parity(R: Runner, sc, res, config: str, tonemap: int, tonemap_name: st
 
 
 def parity_failed(p) -> bool:
-    return any(p.get(k) is False for k in ("ldr_sha_ok", "ldr_equals_single_gpu", "hdr_rows_ok",
-                                           "hdr_single_sha_ok"))
+    """False for None: a plain run (no --full) makes no check."""
+    return p is not None and any(p.get(k) is False for k in (
+        "ldr_sha_ok", "ldr_equals_single_gpu", "hdr_rows_ok", "hdr_single_sha_ok"))
+
+
+DUMP_BUDGET_BYTES = 60 * 10**6   # of --dump-outputs, over every array of every rank
+DUMP_SEED = 0x5EED0D
+
+
+def dump_rows(H: int, row_bytes: int, budget: int = DUMP_BUDGET_BYTES, seed: int = DUMP_SEED):
+    """Image rows that --dump-outputs writes: all H when they fit the budget (row_bytes = one
+    image row over every array written), else a fixed sample of whole rows — seeded, sorted, the
+    same in every run and on every rank."""
+    n = max(1, min(H, budget // row_bytes))
+    if n >= H:
+        return np.arange(H)
+    return np.sort(np.random.default_rng(seed).choice(H, size=n, replace=False))
+
+
+def dump_outputs(R: Runner, sc, res, path: str):
+    """--dump-outputs: the last frame of the last timed call as the caller receives it, read
+    from the timed path's own buffers after the timed region (untimed) — this rank's rank-local
+    HDR rows in image-row order (`hdr`, at N>1 `hdr_rank<r>` with its image rows in
+    `hdr_rows_rank<r>`), and on rank 0 the assembled frame's tonemapped bytes as float32 (`ldr`)
+    and the image rows both hold (`rows`).  Layouts: rt_render_gather_batch (rt_capi.h)."""
+    torch = R.torch
+    W, H = sc.camera.width, sc.camera.height
+    local, ldr = res["bufs"]
+    torch.cuda.synchronize()
+    bs = res["last_set"]
+    nf, mr = res["last_n"][bs], res["max_rows"]
+    f = nf - 1
+    keep = dump_rows(H, W * (HDR_BYTES[res["hdr"]] + 12) + 16)
+    kept = np.zeros(H, dtype=bool)
+    kept[keep] = True
+    parts, ids = [], []
+    for k, slot in enumerate(res["slots"]):
+        rows = np.asarray(block_cyclic_rows(H, res["block"], res["V"], slot) if res["split"]
+                          else range(H), dtype=np.int64)
+        if not len(rows) or not res["slot_rows"][k]:
+            continue
+        sel = np.nonzero(kept[rows])[0]
+        off = (k * nf + f) * mr * W * 3
+        got = local[bs][off:off + len(rows) * W * 3].view(len(rows), W, 3)
+        parts.append(got[torch.as_tensor(sel, device="cuda")].cpu().numpy())
+        ids.append(rows[sel])
+    hdr_np = np.float64 if res["hdr"] == "f64" else np.float32
+    hdr = np.concatenate(parts) if parts else np.empty((0, W, 3), hdr_np)
+    ids = np.concatenate(ids) if ids else np.empty(0, np.int64)
+    order = np.argsort(ids, kind="stable")
+    os.makedirs(path, exist_ok=True)
+    tag = "" if R.world == 1 else f"_rank{R.rank}"
+    np.save(os.path.join(path, f"hdr{tag}.npy"), np.ascontiguousarray(hdr[order], dtype=hdr_np))
+    if R.world > 1:
+        np.save(os.path.join(path, f"hdr_rows{tag}.npy"), ids[order].astype(np.float64))
+    if R.rank == 0:
+        frame = ldr[bs][f * H * W * 3:(f + 1) * H * W * 3].view(H, W, 3)
+        frame = frame[torch.as_tensor(keep, device="cuda")].cpu().numpy()
+        np.save(os.path.join(path, "ldr.npy"), frame.astype(np.float32))
+        np.save(os.path.join(path, "rows.npy"), keep.astype(np.float64))
 
 
 def single_launch_frames(R: Runner, sc, frames, warmup, tonemap=1):
@@ -812,8 +885,8 @@ def main(argv=None):
     tonemap = capi.TONEMAPS.index(args.tonemap)
     sc = make_config(args.config, aa=1)
     W, H = sc.camera.width, sc.camera.height
-    extras = not args.no_extras
-    batch = max(1, args.batch) if args.batch else default_batch(R.world, args.steps)
+    extras = args.full and not args.no_extras
+    batch =max(1, args.batch) if args.batch else default_batch(R.world, args.steps)
 
     weight, probe = 1, None
     if R.world > 1 and args.root_weight != "1":
@@ -833,9 +906,11 @@ def main(argv=None):
                        not args.no_pipeline, args.event_every, weight=weight)
     elapsed = res["elapsed"]
     value = res["rays"] * args.steps / elapsed / 1e6
-    # untimed: the timed path's assembled frame and rank-local rows vs the reference's SHA and a
-    # one-launch whole-frame render (every rank takes part)
-    parity = frame_parity(R, sc, res, args.config, tonemap, args.tonemap)
+    if args.dump_outputs:
+        dump_outputs(R, sc, res, args.dump_outputs)
+    # --full, untimed: the timed path's assembled frame and rank-local rows vs the reference's
+    # SHA and a one-launch whole-frame render (every rank takes part)
+    parity = frame_parity(R, sc, res, args.config, tonemap, args.tonemap) if args.full else None
     summ = per_rank_summary(res)
     r0 = res["ranks"][0]
     # the trace kernel: rank 0's render per frame — from HIP events around every
@@ -888,7 +963,7 @@ def main(argv=None):
         "metric": "Mrays/sec (primary+shadow) at 1920x1080" if args.config == "c2"
                   else f"Mrays/sec (primary+shadow), config {args.config}",
         "value": round(value, 3), "unit": "Mrays/s", "n_gpus": R.world,
-        "steps": args.steps, "warmup": args.warmup,
+        "steps": args.steps, "warmup": args.warmup, "full": args.full,
         "ms_per_step": round(elapsed / args.steps * 1e3, 5),
         "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64",
         "data": "synthetic",
@@ -950,7 +1025,7 @@ def main(argv=None):
         extras = False
     if extras:
         _extras(R, args, sc, line, res, tonemap, batch)
-    if R.world == 1 and not args.no_cpu_baseline and not parity_failed(parity):
+    if args.full and R.world == 1 and not args.no_cpu_baseline and not parity_failed(parity):
         try:
             line["cpu_baseline"] = cpu_baseline(sc, res["rays_rank"], args.cpu_frames)
         except Exception as e:  # a reported baseline, never the product path

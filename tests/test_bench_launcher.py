@@ -85,6 +85,28 @@ def test_parity_failed():
     assert bench.parity_failed({"ldr_equals_single_gpu": False})
 
 
+def test_plain_run_checks_nothing_and_full_is_opt_in():
+    a = bench.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert a.full is False and a.dump_outputs is None and a.steps == 20
+    assert bench.parse_args(["--full", "--dump-outputs", "d"]).full is True
+    assert not bench.parity_failed(None)     # a plain run's `parity`
+
+
+@pytest.mark.parametrize("H,W,hdr", [(1080, 1920, "f64"), (1080, 1920, "f32"), (2160, 3840, "f64"),
+                                     (4320, 7680, "f64"), (54, 96, "f64")])
+def test_dump_rows_are_a_fixed_sample_within_the_budget(H, W, hdr):
+    # one image row over every array --dump-outputs writes: HDR + the bytes as float32 + its index
+    row_bytes = W * (bench.HDR_BYTES[hdr] + 12) + 16
+    rows = bench.dump_rows(H, row_bytes)
+    assert list(rows) == list(bench.dump_rows(H, row_bytes))      # the same in every run
+    assert list(rows) == sorted(set(int(r) for r in rows)) and 0 <= rows[0] and rows[-1] < H
+    assert 1 <= len(rows) and len(rows) * row_bytes <= 64 * 10**6
+    if H * row_bytes <= bench.DUMP_BUDGET_BYTES:
+        assert list(rows) == list(range(H))                       # a frame that fits is whole
+    else:
+        assert (len(rows) + 1) * row_bytes > bench.DUMP_BUDGET_BYTES  # else as much as fits
+
+
 @pytest.mark.parametrize("world,steps,want", [
     (1, 20, 32), (1, 256, 32), (2, 20, 5), (8, 20, 5), (8, 8, 4), (4, 1, 4), (8, 256, 32),
     (2, 100, 25)])

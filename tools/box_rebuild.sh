@@ -20,7 +20,7 @@ cat $OUT/build_info.json
 timeout -k 10 600 python -u -m pytest tests -x -q -m gpu --timeout 240 --timeout-method thread \
   > $OUT/gpu_tests.txt 2>&1
 tail -n 2 $OUT/gpu_tests.txt
-timeout -k 10 300 python bench.py --steps 20 --warmup 5 > $OUT/bench_s20.json 2> $OUT/bench_s20.err
+timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 > $OUT/bench_s20.json 2> $OUT/bench_s20.err
 python -c "
 import json; d = json.load(open('$OUT/bench_s20.json'))
 print(d['value'], d['ms_per_step'], d['build'], d['parity'])"

@@ -4,8 +4,8 @@
 set -eu
 OUT=gpurun_out/final
 mkdir -p $OUT
-timeout -k 10 600 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err
-timeout -k 10 300 python bench.py --steps 20 --warmup 5 > $OUT/bench_s20.json 2> $OUT/bench_s20.err
+timeout -k 10 600 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
+timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 > $OUT/bench_s20.json 2> $OUT/bench_s20.err
 python -c "
 import json
 for f in ('bench_default', 'bench_s20'):

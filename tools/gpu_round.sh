@@ -10,7 +10,7 @@ timeout -k 10 900 python -u -m pytest -x -q -m gpu --timeout 300 --timeout-metho
   > $OUT/gpu_tests.log 2>&1 || { tail -40 $OUT/gpu_tests.log; exit 1; }
 tail -2 $OUT/gpu_tests.log
 echo "== bench"
-timeout -k 10 300 python -u bench.py --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err || { tail $OUT/bench.err; cat $OUT/bench.json | head -c 2000; exit 1; }
+timeout -k 10 300 python -u bench.py --full --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err || { tail $OUT/bench.err; cat $OUT/bench.json | head -c 2000; exit 1; }
 python3 -c "import json;d=json.load(open('$OUT/bench.json'));print({k:d[k] for k in ('value','ms_per_step','kernel_ms_per_frame','parity')})"
 if [ $# -gt 0 ]; then
   echo "== ab $*"

@@ -12,7 +12,7 @@ mkdir -p $OUT
 step() { echo "== $1"; }
 step kernel-trace-bench
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o run -- \
-  python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-extras > $OUT/bench_prof.json 2> $OUT/prof.err || { tail $OUT/prof.err; exit 1; }
+  python3 bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --no-extras > $OUT/bench_prof.json 2> $OUT/prof.err || { tail $OUT/prof.err; exit 1; }
 step kernel-trace-c2-batch32
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt32 -o kt -- \
   python3 tools/profile_kernel.py c2 6 0 32 > $OUT/kt32.log 2>&1 || { tail $OUT/kt32.log; exit 1; }

@@ -29,7 +29,7 @@ i = max(k for k, r in enumerate(pk) if gz(r) == 20 and "packet_direct" in r["Ker
 timed = pk[i:i + 2]
 b = json.load(open(f"{OUT}/bench_prof.json"))
 out = {"command": "rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 20 --warmup 5 "
-                  "--no-cpu-baseline --no-extras",
+                  "--full --no-cpu-baseline --no-extras",
        "note": "the timed region is ONE 20-frame packet launch + its fix-up launch; the earlier "
                "32-frame launches are the clock warm-up and warm-up frames",
        "timed_launches": [{"kernel": r["Kernel_Name"][:60], "grid_z": gz(r),
