@@ -104,8 +104,8 @@ typedef struct rt_scene_desc {
 } rt_scene_desc;
 
 /* Camera (Math.h:85-122).  aa_samples = Camera::antiAliasingAmount (reference default 32).
- * near/far are carried for API completeness; the trace does not read them (as in the
- * reference). */
+ * near/far: the trace does not read them (as in the reference); the G-buffer's normalised
+ * depth does (HitInfo::normalizedDistance, Shape.h:40-42). */
 typedef struct rt_camera {
     double position[3];
     double focal;
@@ -348,6 +348,57 @@ rt_status rt_render_device(rt_context* ctx, const rt_scene* scene, const rt_came
 rt_status rt_render_batch(rt_context* ctx, const rt_scene* scene, const rt_camera* cams,
                           int nframes, const rt_render_opts* opts, void* d_hdr64,
                           void* d_hdr32, void* d_ldr);
+
+/* ---- Full-frame G-buffer ---------------------------------------------------------------------
+ * Per pixel, the HitInfo of the camera ray: what was hit, how far away, with which normal and
+ * base colour — Scene::CalculatePixelDepth(x, y, false) (Scene.h:278-281) and
+ * HitInfo::normalizedDistance(camera) (Shape.h:40-42) for every pixel of a frame in one launch.
+ *
+ * Pixel value: pixel (x, y) holds IntersectClosest(camera.getRay(x, y, false)); the ray is the
+ *   unjittered one and aa_samples is ignored.
+ * Bit-exactness: depth, normal and prim carry the same bits rt_intersect_rays returns for that
+ *   ray.  normal is the unflipped HitInfo::normal: the plane's stored normal, the triangle's, or
+ *   unit(p - C) for a sphere.  A triangle's index is its index into rt_scene_desc.triangles; a
+ *   sphere's is the scene's index (also for scenes of more than 64 spheres, which the renderer
+ *   holds in a spatial order of its own).
+ * depth_norm: (t - near_plane) / (far_plane - near_plane) evaluated in double in that order, then
+ *   rounded to float.  near_plane == far_plane follows IEEE; there is no special case.
+ * Miss: prim = {0, -1}, depth = depth_norm = +inf, normal = albedo = 0.
+ * Layouts follow rt_render_device: row-major and rows-local (idx = (y - row_begin)*W + x, one
+ *   element group per pixel as listed below); row_begin / row_end and the block-cyclic row_block
+ *   / row_cycle of opts are honoured.  Frame f of a batch sits f*rows*W pixels into each output;
+ *   every camera must have cams[0]'s width, height, focal and aa_samples (rt_render_batch's rule).
+ * RT_ERR_INVALID_ARG: outputs == 0, an unknown bit in outputs, or a requested output whose
+ *   pointer is NULL (pointers of outputs that are not requested are ignored).
+ * Of opts only the row set and the flags RT_FLAG_GENERIC_KERNEL, RT_FLAG_NO_BVH and
+ *   RT_FLAG_TIME_KERNEL are read; max_recursion, bias, seed and tonemap are not (primary
+ *   visibility does not depend on them, nor on the materials: every scene type is served). */
+#define RT_GB_DEPTH      0x01  /* double   [px]    HitInfo::distance                          */
+#define RT_GB_DEPTH_NORM 0x02  /* float    [px]    (float)HitInfo::normalizedDistance(camera) */
+#define RT_GB_NORMAL     0x04  /* double   [px][3] HitInfo::normal                            */
+#define RT_GB_PRIM       0x08  /* int32_t  [px][2] {type, index}, as rt_intersect_rays        */
+#define RT_GB_ALBEDO     0x10  /* float    [px][3] (float)HitInfo::material.color             */
+#define RT_GB_ALL        0x1f
+
+/* The output pointers.  The identifier rt_gbuffer alone names the host entry point below (C has
+ * one name space for functions and typedefs), so the record is `struct rt_gbuffer`, or
+ * rt_gbuffer_out for short. */
+struct rt_gbuffer {
+    void* depth;
+    void* depth_norm;
+    void* normal;
+    void* prim;
+    void* albedo;
+};
+typedef struct rt_gbuffer rt_gbuffer_out;
+
+/* Device pointers, asynchronous on the context's stream. */
+rt_status rt_gbuffer_device(rt_context* ctx, const rt_scene* scene, const rt_camera* cams,
+                            int nframes, const rt_render_opts* opts, int outputs,
+                            const struct rt_gbuffer* d_out);
+/* Host pointers, synchronous, one frame. */
+rt_status rt_gbuffer(rt_context* ctx, const rt_scene* scene, const rt_camera* cam,
+                     const rt_render_opts* opts, int outputs, const struct rt_gbuffer* h_out);
 
 /* ---- Serving frame queue -------------------------------------------------------------------
  * Consecutive Scene::RenderImage() frames (Scene.h:311-328) into device framebuffers with

@@ -208,6 +208,25 @@ std::vector<float> Scene::RenderImageF32() const {
     return img;
 }
 
+rtamd::GBuffer Scene::RenderGBuffer(int outputs) const {
+    rtamd::GBuffer gb;
+    gb.width = camera.width;
+    gb.height = camera.height;
+    const size_t n = camera.width * camera.height;
+    if (outputs & RT_GB_DEPTH) gb.depth.resize(n);
+    if (outputs & RT_GB_DEPTH_NORM) gb.depth_norm.resize(n);
+    if (outputs & RT_GB_NORMAL) gb.normal.resize(n, Vec3(0, 0, 0));
+    if (outputs & RT_GB_PRIM) gb.prim.resize(2 * n);
+    if (outputs & RT_GB_ALBEDO) gb.albedo.resize(3 * n);
+    rt_scene* sc = upload();
+    const rt_camera cam = cameraDesc();
+    const rt_render_opts o = optsDesc(RT_TONEMAP_NONE);
+    const rt_gbuffer_out out{gb.depth.data(), gb.depth_norm.data(), gb.normal.data(),
+                             gb.prim.data(), gb.albedo.data()};
+    rtamd::check(rt_gbuffer(dev_->ctx, sc, &cam, &o, outputs, &out), "rt_gbuffer");
+    return gb;
+}
+
 Vec3 Scene::GeneratePixelAt(int x, int y) const {
     if (x < 0 || y < 0 || static_cast<size_t>(x) >= camera.width ||
         static_cast<size_t>(y) >= camera.height)

@@ -7,6 +7,7 @@
 //   GenerateAntiAliasing(..) → rt_trace_rays             (Scene.h:306-309)
 //   IntersectClosest(ray)    → rt_intersect_rays         (Scene.h:218-257)
 //   CalculatePixelDepth(..)  → rt_intersect_rays         (Scene.h:278-281)
+//   RenderGBuffer()          → rt_gbuffer (extension: CalculatePixelDepth of every pixel)
 // IntersectAnyBefore (Scene.h:259-276, unused by the reference) is a host utility over the
 // shapes' Intersect members.  Failures throw std::runtime_error(rt_last_error()).
 //
@@ -33,6 +34,18 @@ rt_context* thread_context(int device);
 int current_device();
 // Throws std::runtime_error carrying rt_last_error() when st != RT_OK.
 void check(rt_status st, const char* what);
+
+// Scene::RenderGBuffer's result: per pixel (row-major, Scene::GetPixelIndex) the HitInfo of
+// CalculatePixelDepth(x, y, false).  Outputs that were not requested stay empty.  A miss holds
+// prim {0, -1}, depth and depth_norm +inf, normal and albedo 0 (rt_capi.h, G-buffer).
+struct GBuffer {
+    size_t width = 0, height = 0;
+    std::vector<double> depth;       // HitInfo::distance
+    std::vector<float> depth_norm;   // (float)HitInfo::normalizedDistance(camera)
+    std::vector<Vec3> normal;        // HitInfo::normal (unflipped)
+    std::vector<int32_t> prim;       // {type, index} pairs as rt_intersect_rays reports them
+    std::vector<float> albedo;       // r g b of HitInfo::material.color
+};
 }  // namespace rtamd
 
 class Scene {
@@ -86,6 +99,9 @@ public:
     std::vector<Color> RenderImageTonemapped(int op = RT_TONEMAP_ACES) const;
     // float32 HDR framebuffer (12 B/px) instead of the reference's FP64 Vec3 (24 B/px).
     std::vector<float> RenderImageF32() const;
+    // CalculatePixelDepth(x, y, false) for every pixel in one launch (rt_gbuffer): depth,
+    // normalised depth, normal, primitive and base colour maps; `outputs` is a set of RT_GB_* bits.
+    rtamd::GBuffer RenderGBuffer(int outputs = RT_GB_ALL) const;
     void SetDevice(int device) { device_ = device; dev_.reset(); devices_.clear(); }
     // RenderImage / RenderImageTonemapped / RenderImageF32 over several GPUs of the node from
     // this process: one scene copy per GPU, block-cyclic rows, assembled on the host (distinct

@@ -34,6 +34,18 @@ RT_FLAG_NO_TILE_ORDER = 0x20
 RT_FLAG_NO_SAMPLE_PARALLEL = 0x40
 RT_OUT_HDR64, RT_OUT_HDR32, RT_OUT_LDR = 0x1, 0x2, 0x4
 RT_COMM_ID_BYTES = 128
+# G-buffer outputs (rt_capi.h RT_GB_*)
+GB_DEPTH = 0x01
+GB_DEPTH_NORM = 0x02
+GB_NORMAL = 0x04
+GB_PRIM = 0x08
+GB_ALBEDO = 0x10
+GB_ALL = 0x1F
+# per output, in bit order: name (the key of DeviceScene.gbuffer's dict and the field of
+# rt_gbuffer), bit, element type, elements per pixel
+GB_OUTPUTS = [("depth", GB_DEPTH, np.float64, 1), ("depth_norm", GB_DEPTH_NORM, np.float32, 1),
+              ("normal", GB_NORMAL, np.float64, 3), ("prim", GB_PRIM, np.int32, 2),
+              ("albedo", GB_ALBEDO, np.float32, 3)]
 
 # Every symbol include/rt_capi.h declares (checked by tests/test_capi_symbols.py).
 EXPORTED = [
@@ -47,7 +59,7 @@ EXPORTED = [
     "rt_stats_read", "rt_stats_reset", "rt_trace_rays", "rt_intersect_rays", "rt_tonemap",
     "rt_debug_f64_ops", "rt_debug_vec_ops", "rt_queue_create", "rt_queue_destroy",
     "rt_queue_submit", "rt_queue_wait", "rt_queue_synchronize", "rt_render_batch",
-    "rt_render_gather_batch", "rt_render_gather_all_batch",
+    "rt_render_gather_batch", "rt_render_gather_all_batch", "rt_gbuffer", "rt_gbuffer_device",
 ]
 
 
@@ -80,6 +92,21 @@ class Stats(ctypes.Structure):
         ("trace_rays", ctypes.c_uint64), ("shadow_rays", ctypes.c_uint64),
         ("kernel_ms", ctypes.c_double), ("launches", ctypes.c_uint64),
     ]
+
+
+class GBufferPtrs(ctypes.Structure):
+    """struct rt_gbuffer: one pointer per output (those of outputs not requested are ignored)."""
+    _fields_ = [(name, ctypes.c_void_p) for name, _, _, _ in GB_OUTPUTS]
+
+
+def gbuffer_layout(outputs: int, width: int, rows: int, frames: int | None = None) -> dict:
+    """{name: (shape, dtype)} of the requested G-buffer outputs: [frames,] rows, width[, k]
+    (frames None: a single frame without the leading axis).  Pure shape logic, no device."""
+    if outputs == 0 or outputs & ~GB_ALL:
+        raise ValueError(f"G-buffer outputs {outputs:#x}: no output or an unknown bit")
+    lead = () if frames is None else (int(frames),)
+    return {name: (lead + (rows, width) + ((k,) if k > 1 else ()), np.dtype(dt))
+            for name, bit, dt, k in GB_OUTPUTS if outputs & bit}
 
 
 class GatherTiming(ctypes.Structure):
@@ -128,6 +155,8 @@ def load_library(path: str = LIB_PATH):
         "rt_render": [vp, vp, vp, vp, vp, vp, vp, vp],
         "rt_render_device": [vp, vp, vp, vp, vp, vp, vp],
         "rt_render_batch": [vp, vp, vp, i32, vp, vp, vp, vp],
+        "rt_gbuffer": [vp, vp, vp, vp, i32, vp],
+        "rt_gbuffer_device": [vp, vp, vp, i32, vp, i32, vp],
         "rt_render_multi": [vp, vp, i32, vp, vp, vp, vp, vp, vp],
         "rt_stats_read": [vp, vp],
         "rt_stats_reset": [vp],
@@ -416,6 +445,40 @@ class DeviceScene:
         cams = np.ascontiguousarray(cams)
         _check(_lib.rt_render_batch(self.ctx.handle, self._h, cams.ctypes.data, len(cams),
                                     ctypes.byref(opts), d_hdr64, d_hdr32, d_ldr))
+
+    def gbuffer(self, outputs: int = GB_ALL, cams: np.ndarray | None = None, opts=None) -> dict:
+        """The frame's G-buffer as host arrays (rt_gbuffer; with `cams`, an rt_camera array as
+        `cameras()` makes, one frame per camera through rt_gbuffer_device): {name: array} for the
+        outputs requested (GB_* bits), shaped [frames,] rows, W[, k] — depth float64, depth_norm
+        float32, normal float64 ×3, prim int32 ×2 {type, index}, albedo float32 ×3."""
+        o = opts if opts is not None else default_opts()
+        cam = self.data.camera
+        rows = rendered_rows(o, cam.height)
+        if cams is None:
+            out = {n: np.empty(s, d) for n, (s, d) in
+                   gbuffer_layout(outputs, cam.width, rows).items()}
+            ptrs = GBufferPtrs(**{n: a.ctypes.data for n, a in out.items()})
+            _check(_lib.rt_gbuffer(self.ctx.handle, self._h, self.camera.ctypes.data,
+                                   ctypes.byref(o), outputs, ctypes.byref(ptrs)))
+            return out
+        import torch
+        cams = np.ascontiguousarray(cams)
+        lay = gbuffer_layout(outputs, cam.width, rows, len(cams))
+        dev = {n: torch.empty(int(np.prod(s)) * d.itemsize, dtype=torch.uint8,
+                              device=f"cuda:{self.ctx.device}") for n, (s, d) in lay.items()}
+        self.gbuffer_device(outputs, {n: t.data_ptr() for n, t in dev.items()}, cams=cams, opts=o)
+        self.ctx.synchronize()
+        return {n: dev[n].cpu().numpy().view(d).reshape(s) for n, (s, d) in lay.items()}
+
+    def gbuffer_device(self, outputs: int, ptrs: dict, cams: np.ndarray | None = None, opts=None):
+        """Asynchronous G-buffer pass into raw device pointers (rt_gbuffer_device): `ptrs` maps
+        output names (depth, depth_norm, normal, prim, albedo) to device addresses holding
+        len(cams) frames back to back (`cams` None: this scene's camera, one frame)."""
+        o = opts if opts is not None else default_opts()
+        cams = self.camera if cams is None else np.ascontiguousarray(cams)
+        p = GBufferPtrs(**{n: int(v) for n, v in ptrs.items() if v})
+        _check(_lib.rt_gbuffer_device(self.ctx.handle, self._h, cams.ctypes.data, len(cams),
+                                      ctypes.byref(o), outputs, ctypes.byref(p)))
 
 
 def render_multi(scenes: list, *, hdr64=True, tonemap: int = TONEMAP_NONE, stats=False,

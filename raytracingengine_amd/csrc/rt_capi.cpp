@@ -756,6 +756,87 @@ rt_status enqueue_frames(rt_context* ctx, const rt_scene* sc, const rt_camera* c
     return scratch ? scratch_done(ctx) : RT_OK;
 }
 
+// ---- G-buffer (rt_gbuffer.hip) ------------------------------------------------------------
+constexpr size_t kGbBytes[5] = {8, 4, 24, 8, 12};  // per pixel, in RT_GB_* bit order
+
+rt_status check_gbuffer_args(int outputs, const rt_gbuffer_out* out) {
+    if (outputs == 0) return fail(RT_ERR_INVALID_ARG, "G-buffer: no output requested");
+    if (outputs & ~RT_GB_ALL) return fail(RT_ERR_INVALID_ARG, "G-buffer: unknown output bit");
+    if (!out) return fail(RT_ERR_INVALID_ARG, "G-buffer: the output record is NULL");
+    const void* ptr[5] = {out->depth, out->depth_norm, out->normal, out->prim, out->albedo};
+    for (int k = 0; k < 5; ++k)
+        if ((outputs & (1 << k)) && !ptr[k])
+            return fail(RT_ERR_INVALID_ARG, "G-buffer: a requested output's pointer is NULL");
+    return RT_OK;
+}
+
+// Enqueues the G-buffer pass of nframes cameras on ctx's stream into device outputs (checked by
+// the caller, which holds a DeviceGuard); at most kPkMaxBatch frames per launch.
+rt_status enqueue_gbuffer(rt_context* ctx, const rt_scene* sc, const rt_camera* cams, int nframes,
+                          const rt_render_opts* opts_in, int outputs, const rt_gbuffer_out& out) {
+    rt_status st = check_batch(cams, nframes);
+    if (st != RT_OK) return st;
+    rt_render_opts opts;
+    if (opts_in) opts = *opts_in;
+    else rt_render_opts_default(&opts);
+    // not read here: whatever the caller left in them must neither fail nor steer the pass
+    opts.max_recursion = 1;
+    opts.tonemap = RT_TONEMAP_NONE;
+    opts.flags &= RT_FLAG_GENERIC_KERNEL | RT_FLAG_NO_BVH | RT_FLAG_TIME_KERNEL;
+    TraceParams p;
+    int path;
+    bool lds;
+    size_t lds_bytes;
+    uint32_t rows;
+    st = build_params(ctx, sc, cams, &opts, p, path, lds, lds_bytes, rows);
+    if (st != RT_OK) return st;
+    const bool packet = !(opts.flags & RT_FLAG_GENERIC_KERNEL) &&
+                        gbuffer_packet_fits(p, ctx->lds_limit);
+    if (packet) p.nl = 0;  // the packet image is laid out without light records
+    p.frame_px = static_cast<uint64_t>(rows) * p.width;
+    GbOut g;
+
+    std::pair<hipEvent_t, hipEvent_t> ev{nullptr, nullptr};
+    if (opts.flags & RT_FLAG_TIME_KERNEL) {
+        if (ctx->pending.size() >= 1024) {
+            st = harvest_events(ctx, false);
+            if (st != RT_OK) return st;
+        }
+        if (!ctx->free_events.empty()) {
+            ev = ctx->free_events.back();
+            ctx->free_events.pop_back();
+        } else {
+            RT_HIP(hipEventCreate(&ev.first));
+            RT_HIP(hipEventCreate(&ev.second));
+        }
+        RT_HIP(hipEventRecord(ev.first, ctx->stream));
+    }
+    for (int f0 = 0; f0 < nframes; f0 += kPkMaxBatch) {
+        const int n = std::min(kPkMaxBatch, nframes - f0);
+        p.nframes = static_cast<uint32_t>(n);
+        for (int f = 0; f < n; ++f) {
+            for (int i = 0; i < 3; ++i) p.fr[f].cam[i] = cams[f0 + f].position[i];
+            g.planes[f][0] = cams[f0 + f].near_plane;
+            g.planes[f][1] = cams[f0 + f].far_plane;
+        }
+        const size_t off = static_cast<size_t>(f0) * p.frame_px;  // pixels
+        auto at = [&](void* base, int bit, size_t elems) -> char* {
+            return (outputs & bit) ? static_cast<char*>(base) + off * elems : nullptr;
+        };
+        g.depth = reinterpret_cast<double*>(at(out.depth, RT_GB_DEPTH, kGbBytes[0]));
+        g.depth_norm = reinterpret_cast<float*>(at(out.depth_norm, RT_GB_DEPTH_NORM, kGbBytes[1]));
+        g.normal = reinterpret_cast<double*>(at(out.normal, RT_GB_NORMAL, kGbBytes[2]));
+        g.prim = reinterpret_cast<int32_t*>(at(out.prim, RT_GB_PRIM, kGbBytes[3]));
+        g.albedo = reinterpret_cast<float*>(at(out.albedo, RT_GB_ALBEDO, kGbBytes[4]));
+        RT_HIP(launch_gbuffer(p, g, packet, 0, ctx->stream));
+    }
+    if (opts.flags & RT_FLAG_TIME_KERNEL) {
+        RT_HIP(hipEventRecord(ev.second, ctx->stream));
+        ctx->pending.push_back(ev);
+    }
+    return RT_OK;
+}
+
 }  // namespace rtamd
 
 extern "C" {
@@ -1080,6 +1161,49 @@ rt_status rt_render_batch(rt_context* ctx, const rt_scene* sc, const rt_camera* 
     DeviceGuard g(ctx->device);
     return enqueue_frames(ctx, sc, cams, nframes, opts, static_cast<double*>(d64),
                           static_cast<float*>(d32), static_cast<uint8_t*>(dldr));
+}
+
+rt_status rt_gbuffer_device(rt_context* ctx, const rt_scene* sc, const rt_camera* cams,
+                            int nframes, const rt_render_opts* opts, int outputs,
+                            const struct rt_gbuffer* d_out) {
+    rt_status st = check_gbuffer_args(outputs, d_out);
+    if (st != RT_OK) return st;
+    if (!ctx) return fail(RT_ERR_INVALID_ARG, "context is NULL");
+    DeviceGuard g(ctx->device);
+    return enqueue_gbuffer(ctx, sc, cams, nframes, opts, outputs, *d_out);
+}
+
+rt_status rt_gbuffer(rt_context* ctx, const rt_scene* sc, const rt_camera* cam,
+                     const rt_render_opts* opts, int outputs, const struct rt_gbuffer* h_out) {
+    rt_status st = check_gbuffer_args(outputs, h_out);
+    if (st != RT_OK) return st;
+    if (!ctx) return fail(RT_ERR_INVALID_ARG, "context is NULL");
+    st = validate_camera(cam);
+    if (st != RT_OK) return st;
+    DeviceGuard g(ctx->device);
+    rt_render_opts o;
+    if (opts) o = *opts;
+    else rt_render_opts_default(&o);
+    const size_t npx = static_cast<size_t>(rendered_rows(o, cam->height)) * cam->width;
+    // one staging allocation, every requested output at a 256-byte boundary
+    void* const host[5] = {h_out->depth, h_out->depth_norm, h_out->normal, h_out->prim,
+                           h_out->albedo};
+    size_t off[5], total = 0;
+    for (int k = 0; k < 5; ++k) {
+        off[k] = total;
+        if (outputs & (1 << k)) total += (npx * kGbBytes[k] + 255) / 256 * 256;
+    }
+    RT_HIP(ctx->out64.ensure(total));
+    char* base = static_cast<char*>(ctx->out64.ptr);
+    rt_gbuffer_out d{base + off[0], base + off[1], base + off[2], base + off[3], base + off[4]};
+    st = enqueue_gbuffer(ctx, sc, cam, 1, &o, outputs, d);
+    if (st != RT_OK) return st;
+    for (int k = 0; k < 5; ++k)
+        if (outputs & (1 << k))
+            RT_HIP(hipMemcpyAsync(host[k], base + off[k], npx * kGbBytes[k], hipMemcpyDeviceToHost,
+                                  ctx->stream));
+    RT_HIP(hipStreamSynchronize(ctx->stream));
+    return RT_OK;
 }
 
 rt_status rt_render(rt_context* ctx, const rt_scene* sc, const rt_camera* cam,

@@ -176,6 +176,23 @@ hipError_t launch_packet_order(const uint32_t* cost, uint32_t gx, uint32_t gy, u
                                uint32_t* keys, uint32_t* order, uint32_t* verdict,
                                hipStream_t stream);
 int packet_max_spheres();
+// G-buffer pass (rt_gbuffer.hip): per pixel, IntersectClosest of the unjittered camera ray.
+// Device outputs, any may be null; rows-local like TraceParams.out64, frame f (p.fr[f].cam,
+// p.nframes >= 1) at f * p.frame_px pixels of each.
+struct GbOut {
+    double* depth;      // [px]    HitInfo::distance, +inf on a miss
+    float* depth_norm;  // [px]    (float)((t - near) / (far - near)) of the frame's camera
+    double* normal;     // [px][3] geometric normal, as rt_intersect_rays
+    int32_t* prim;      // [px][2] {type, index}
+    float* albedo;      // [px][3] (float)material.color
+    double planes[kPkMaxBatch][2];  // frame f's camera {near_plane, far_plane}
+};
+// Whether the packet kernel serves p (its LDS image without light records fits lds_limit).
+bool gbuffer_packet_fits(const TraceParams& p, size_t lds_limit);
+// packet: gbuffer_packet_kernel (p.nl must be 0: the image is laid out without lights), else
+// gbuffer_generic_kernel.  tile_w: 8 (8×8 px per wave) or 16 (16×4), 0: the default.
+hipError_t launch_gbuffer(const TraceParams& p, const GbOut& g, bool packet, int tile_w,
+                          hipStream_t stream);
 hipError_t launch_trace_rays(const TraceParams& p, int path, bool count, const double* rays,
                              size_t n, double* out, hipStream_t stream);
 hipError_t launch_intersect_rays(const TraceParams& p, const double* rays, size_t n, double* out,

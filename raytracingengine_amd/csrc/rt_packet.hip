@@ -1439,7 +1439,9 @@ __global__ __launch_bounds__(64 * kWgWavesX * WGY, pk_waves(MAXC, FEAT, COUNT, M
     }
 }
 
-#ifdef RT_PACKET_PROBE
+#ifdef RT_PACKET_GBUFFER_TU
+// rt_gbuffer.hip: the packet machinery above (image, culls, closest hit) only
+#elif defined(RT_PACKET_PROBE)
 // tools/isa/probe.sh: one instantiation only (register / ISA studies of a single variant)
 template __global__ void packet_direct_kernel<RT_PACKET_PROBE>(TraceParams);
 #else
