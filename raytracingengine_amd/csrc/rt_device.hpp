@@ -98,17 +98,27 @@ __device__ __forceinline__ d3 unit_exact(d3 a) {
 }
 // The same bits through the cores when the operands allow it (zero components, e.g. axis-
 // aligned normals, take the exact path unless the length is exactly 1).
+// The literal divisions must stay behind a branch: an IR fdiv looks cheap before it is lowered,
+// so the compiler if-converts an unguarded fallback into the core's block and every lane pays
+// for the core AND three full divisions (~42 VALU per call; it did so for the camera ray of the
+// packet kernels and box_chain_kernel).  The empty volatile asm cannot be speculated, which
+// keeps the fallback a block of its own (tools/isa/census.py --folded,
+// tests/test_isa_unit_branch.py).  It takes the length as an in/out register operand: with an
+// operand-less asm (with or without a "memory" clobber) the C5 area variant's register
+// allocation moved the per-sample colour accumulators into scratch and C5 lost 39 %
+// (profiles/unit_branch_ab_c5_operandless_asm.txt).
 __device__ __forceinline__ d3 unit(d3 a) {
     const double x = dot(a, a);
     d3 out;
     if (x >= kUnitLo && x <= kUnitHi) {
-        const double l = sqrt_core(x);
+        double l = sqrt_core(x);
         if (l == 1.0) {
             out = a;
         } else if (fabs(a.x) >= kNumLo && fabs(a.y) >= kNumLo && fabs(a.z) >= kNumLo) {
             const double r = rcp_refined(l);
             out = mk(div_core(a.x, l, r), div_core(a.y, l, r), div_core(a.z, l, r));
         } else {
+            __asm__ volatile("" : "+v"(l));  // not speculated: see above
             out = sdiv(a, l);
         }
     } else {

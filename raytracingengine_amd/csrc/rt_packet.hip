@@ -273,7 +273,13 @@ __device__ __forceinline__ Masks<MAXC> cull_cone(const PacketScene& S, d3 axis, 
 // ray but not by the segment is kept).  The squared distance
 // from C to the segment carries < 1.5e-6·(|C−c|² + |L−c|²) of FP32 error (any of the three
 // branches, including a branch chosen wrongly next to a boundary where they meet
-// continuously), against a slack of 2e-5·(|C−c|² + |L−c|²).
+// continuously), against a slack of 2e-5·(|C−c|² + |L−c|²).  The middle branch multiplies by
+// v_rcp_f32(|L−c|²) (1 ulp: relative error ≤ 2^-23) instead of dividing (a full IEEE FP32
+// division is 12 VALU in the per-lane branch): that adds ≤ 1.2e-7·(v·s)²/|s|² ≤ 1.2e-7·|C−c|²
+// to the subtracted term, so the bound is < 1.7e-6·(|C−c|² + |L−c|²), still 12× inside the
+// slack.  v_rcp_f32 flushes denormals: a denormal |s|² gives inf and an inf or NaN distance,
+// which keeps the sphere; |s|² > 2^120, whose reciprocal would underflow to 0 and lose the
+// subtracted term, culls nothing (`huge`).
 template <int MAXC, int FEAT>
 __device__ __forceinline__ Masks<MAXC> cull_capsule(const PacketScene& S, d3 c, float R, d3 L,
                                                     double RL, double bias) {
@@ -282,7 +288,8 @@ __device__ __forceinline__ Masks<MAXC> cull_capsule(const PacketScene& S, d3 c, 
     const float sx = static_cast<float>(L.x - c.x), sy = static_cast<float>(L.y - c.y),
                 sz = static_cast<float>(L.z - c.z);
     const float sl2 = dot3f(sx, sy, sz, sx, sy, sz);
-    const float inv_sl2 = 1.0f / sl2;  // wave-uniform; only read when sl2 > 0
+    const float inv_sl2 = __builtin_amdgcn_rcpf(sl2);  // wave-uniform; only read when sl2 > 0
+    const bool huge = !(sl2 <= 0x1p120f);              // (or NaN) no usable reciprocal: keep all
     const float Rc = fmaxf(R, f32_up(RL)) + f32_up(fabs(bias)) * 1.001f;  // |n| ≤ 1 + 2ε
     auto test = [&](int k) {
         const double2* s2 = reinterpret_cast<const double2*>(S.sph + kPkSph * k);
@@ -299,11 +306,12 @@ __device__ __forceinline__ Masks<MAXC> cull_capsule(const PacketScene& S, d3 c, 
             const float wx = vx - sx, wy = vy - sy, wz = vz - sz;
             d2 = dot3f(wx, wy, wz, wx, wy, wz);
         } else {
-            d2 = vv - (vs * vs) * inv_sl2;  // one more rounding than a division: ≪ slack
+            d2 = vv - (vs * vs) * inv_sl2;  // a rounding and the reciprocal's ulp: ≪ slack
         }
         const float lim = (r + Rc) * (1.0f + static_cast<float>(kCullRel));
         const float far = static_cast<float>(kFarRatio) * r - Rc;
-        return !(d2 > lim * lim + kF32Slack * (vv + sl2)) || !(far > 0.0f) || !(vv <= far * far);
+        return !(d2 > lim * lim + kF32Slack * (vv + sl2)) || !(far > 0.0f) ||
+               !(vv <= far * far) || huge;
     };
     uint64_t live = ~0ull;  // chunks whose bounding sphere the capsule may meet
     if constexpr (MAXC > 1)

@@ -2,13 +2,31 @@
 """Static ISA census of one kernel in a `hipcc --cuda-device-only -S` listing (dev tool).
 
     python tools/isa/census.py /tmp/pk.s 'packet_direct_kernelILi1ELi0ELb0ELb0ELi1E' [--blocks]
+    python tools/isa/census.py /tmp/pk.s packet_direct_kernel --folded
 
 Counts the instructions of the kernel by class (FP64 / FP32 / int VALU, v_cndmask, v_mov,
 v_cmp, SALU, LDS, global, branches), and with --blocks prints every basic block with its size
-and class counts, so that the blocks of the hot path can be attributed to source phases."""
+and class counts, so that the blocks of the hot path can be attributed to source phases.
+
+--folded checks EVERY kernel of the listing whose name contains the pattern for basic blocks
+that hold both a shared-reciprocal division core and full IEEE divisions by the same divisor
+(unit() / light_dir() of rt_device.hpp with the fallback branch if-converted into the core:
+every lane then pays for both).  Such a block has ≥ 4 v_rcp_f64 and ≥ 3 v_div_fixup_f64, but so
+have blocks of four or more honest divisions (light_dir's fallback, the tonemap), so the
+signature is the operand: the core takes v_rcp_f64 of the divisor itself, a full division takes
+it of the v_div_scale_f64 result and names the divisor only in its v_div_fixup_f64.  A block
+where a v_rcp_f64 source is also, unmodified, the denominator of ≥ 3 v_div_fixup_f64 is
+reported.  Prints one line per such block and exits 1 when there is any.
+--shared N lowers the number of divisions that must share the core's divisor (default 3:
+unit() and light_dir()); --shared 1 also reports a single-division core (plane_t_core,
+sphere_roots_core, reinhard_byte) computed in one block with its full-division fallback.
+
+A basic block starts at a label (.LBBn_m) or at a fall-through block comment (; %bb.n)."""
 import re
 import sys
 from collections import Counter, OrderedDict
+
+FOLD_MIN_FIXUP = 3  # full divisions sharing the core's divisor: unit() has three
 
 
 def classify(op):
@@ -42,32 +60,114 @@ def classify(op):
     return "other"
 
 
+_BLOCK = re.compile(r"^(?:(\.LBB\d+_\d+):|; (%bb\.\d+):)")
+
+
+def kernels(lines, name):
+    """{mangled kernel name: OrderedDict(block -> [instruction lines])} of every kernel whose
+    name contains `name`."""
+    out = OrderedDict()
+    i = 0
+    while i < len(lines):
+        l = lines[i]
+        if l.startswith("_Z") and name in l and (l.rstrip().endswith(":") or ": ;" in l):
+            kname = l.split(":")[0]
+            end = next(j for j in range(i + 1, len(lines)) if lines[j].startswith(".Lfunc_end"))
+            blocks = OrderedDict()
+            cur = "entry"
+            blocks[cur] = []
+            for b in lines[i + 1:end]:
+                s = b.strip()
+                m = _BLOCK.match(s)
+                if m:
+                    cur = m.group(1) or m.group(2)
+                    blocks[cur] = []
+                    continue
+                if not s or s.startswith(";") or s.startswith("."):
+                    continue
+                blocks[cur].append(s.split(";")[0].strip())
+            out[kname] = blocks
+            i = end
+        i += 1
+    return out
+
+
+_REG = re.compile(r"([vs])\[(\d+):(\d+)\]|([vs])(\d+)")
+
+
+def _regs(operand):
+    """(file, first, last) of a register operand such as -v[6:7], |v[0:1]| or v3; else None."""
+    m = _REG.search(operand)
+    if not m:
+        return None
+    if m.group(1):
+        return m.group(1), int(m.group(2)), int(m.group(3))
+    return m.group(4), int(m.group(5)), int(m.group(5))
+
+
+def _operands(line):
+    parts = line.split(None, 1)
+    return [o.strip() for o in parts[1].split(",")] if len(parts) > 1 else []
+
+
+def folded_blocks(blocks, min_shared=None):
+    """[(block, size, #v_rcp_f64, #v_div_fixup_f64, #shared)] of the blocks where a v_rcp_f64
+    takes the very divisor of `shared` ≥ min_shared (default FOLD_MIN_FIXUP) v_div_fixup_f64
+    (no write in between)."""
+    if min_shared is None:
+        min_shared = FOLD_MIN_FIXUP
+    hits = []
+    for b, ins in blocks.items():
+        rcps = [i for i, l in enumerate(ins) if l.startswith("v_rcp_f64")]
+        fixs = [i for i, l in enumerate(ins) if l.startswith("v_div_fixup_f64")]
+        best = 0
+        for i in rcps:
+            src = _regs(_operands(ins[i])[1])
+            if src is None:
+                continue
+            shared = 0
+            for j in fixs:
+                if j < i or _regs(_operands(ins[j])[2]) != src:
+                    continue
+                written = False
+                for k in range(i + 1, j):
+                    ops = _operands(ins[k])
+                    d = _regs(ops[0]) if ops and ins[k].startswith("v_") else None
+                    if d and d[0] == src[0] and d[1] <= src[2] and src[1] <= d[2]:
+                        written = True
+                        break
+                shared += not written
+            best = max(best, shared)
+        if best >= min_shared:
+            hits.append((b, len(ins), len(rcps), len(fixs), best))
+    return hits
+
+
 def main():
     path, name = sys.argv[1], sys.argv[2]
-    lines = open(path).read().splitlines()
-    start = next(i for i, l in enumerate(lines) if l.startswith("_Z") and name in l and l.rstrip().endswith(":") or (l.startswith("_Z") and name in l and ": ;" in l))
-    end = next(i for i in range(start + 1, len(lines)) if lines[i].startswith(".Lfunc_end"))
-    blocks = OrderedDict()
-    cur = "entry"
-    blocks[cur] = []
-    for l in lines[start + 1:end]:
-        s = l.strip()
-        if not s or s.startswith(";") or s.startswith("."):
-            m = re.match(r"^(\.LBB\d+_\d+):", s)
-            if m:
-                cur = m.group(1)
-                blocks[cur] = []
-            continue
-        op = s.split()[0]
-        blocks[cur].append(op)
-    total = Counter(classify(o) for b in blocks.values() for o in b)
+    found = kernels(open(path).read().splitlines(), name)
+    if not found:
+        sys.exit(f"no kernel matching {name!r} in {path}")
+    if "--folded" in sys.argv:
+        bad = 0
+        shared = int(sys.argv[sys.argv.index("--shared") + 1]) if "--shared" in sys.argv else None
+        for kname, blocks in found.items():
+            hits = folded_blocks(blocks, shared)
+            bad += len(hits)
+            print(f"{kname}: {len(hits)} folded core+division blocks in {len(blocks)} blocks")
+            for b, n, rcp, fix, shared in hits:
+                print(f"  {b:14s} {n:5d} instructions  v_rcp_f64={rcp} v_div_fixup_f64={fix} "
+                      f"(core divisor shared by {shared})")
+        sys.exit(1 if bad else 0)
+    kname, blocks = next(iter(found.items()))
+    total = Counter(classify(o.split()[0]) for b in blocks.values() for o in b)
     n = sum(total.values())
     print(f"{name}: {n} instructions in {len(blocks)} blocks")
     for k, v in total.most_common():
         print(f"  {k:16s} {v:6d}")
     if "--blocks" in sys.argv:
         for b, ops in blocks.items():
-            c = Counter(classify(o) for o in ops)
+            c = Counter(classify(o.split()[0]) for o in ops)
             print(f"{b:14s} {len(ops):5d}  " + " ".join(f"{k}={v}" for k, v in c.most_common(6)))
 
 
