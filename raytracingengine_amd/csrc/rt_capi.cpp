@@ -178,6 +178,11 @@ rt_status build_params(rt_context* ctx, const rt_scene* sc, const rt_camera* cam
     p.focal = cam->focal;
     p.width = cam->width;
     p.height = cam->height;
+    const CameraConsts cc = camera_consts(cam->width, cam->height, cam->position[2], cam->focal);
+    p.half_w = cc.half_w;
+    p.half_h = cc.half_h;
+    p.cam_dz = cc.dz;
+    p.cam_dz2 = cc.dz2;
     p.aa = cam->aa_samples;
     p.max_rec = opts.max_recursion;
     p.bias = opts.bias;
@@ -462,6 +467,10 @@ rt_status packet_batch_images(rt_context* ctx, const rt_scene* sc, const rt_came
     for (int f = 0; f < nframes; ++f) {
         PkFrame& F = p.fr[f];
         for (int i = 0; i < 3; ++i) F.cam[i] = cams[f].position[i];
+        // (width, height and focal are the batch's: rt_render_batch checked them)
+        const CameraConsts cc = camera_consts(p.width, p.height, F.cam[2], p.focal);
+        p.fr_dz[f][0] = cc.dz;
+        p.fr_dz[f][1] = cc.dz2;
         F.img = nullptr;
         F.pub = nullptr;
         F.epoch = 0;

@@ -107,8 +107,9 @@ __device__ __forceinline__ d3 unit_exact(d3 a) {
 // operand-less asm (with or without a "memory" clobber) the C5 area variant's register
 // allocation moved the per-sample colour accumulators into scratch and C5 lost 39 %
 // (profiles/unit_branch_ab_c5_operandless_asm.txt).
-__device__ __forceinline__ d3 unit(d3 a) {
-    const double x = dot(a, a);
+// unit_sq: x is dot(a, a), formed by the caller (a camera ray adds the frame's dz·dz, read from
+// the kernel arguments, to its own two products: the same three products and two sums).
+__device__ __forceinline__ d3 unit_sq(d3 a, double x) {
     d3 out;
     if (x >= kUnitLo && x <= kUnitHi) {
         double l = sqrt_core(x);
@@ -127,6 +128,7 @@ __device__ __forceinline__ d3 unit(d3 a) {
     }
     return out;
 }
+__device__ __forceinline__ d3 unit(d3 a) { return unit_sq(a, dot(a, a)); }
 // directLightning's light vector (Scene.h:87-90, 110): dist = v.length(), L = v / dist and
 // 1 / (dist·dist), through the cores when the operands allow it.  L is only meaningful for
 // dist > 0 (the reference skips the light otherwise).

@@ -123,7 +123,29 @@ struct TraceParams {
     uint32_t _pad2;
     uint64_t frame_px;
     PkFrame fr[kPkMaxBatch];
+    // camera-ray terms that are constant over a frame, formed once on the host (camera_consts)
+    // and read with scalar loads by the packet kernel: width / 2, height / 2,
+    // dz = (cam.z + focal) − cam.z and dz · dz; fr_dz[f] = {dz, dz · dz} of a batch's frame f
+    // (after fr[], whose records keep their size: the kernels that do not read these fields
+    // see the layout they were tuned with)
+    double half_w, half_h, cam_dz, cam_dz2;
+    double fr_dz[kPkMaxBatch][2];
 };
+
+// Camera::getRay's frame constants (Math.h:99-121): the single IEEE double operations of the
+// device expression, in its order, so a kernel that reads them computes the bits it computed
+// itself — sx = x − W/2, sy = H/2 − y, d = (sx − cam.x, sy − cam.y, dz), |d|² = (…) + dz·dz.
+struct CameraConsts {
+    double half_w, half_h, dz, dz2;
+};
+inline CameraConsts camera_consts(uint32_t width, uint32_t height, double cam_z, double focal) {
+    CameraConsts c;
+    c.half_w = static_cast<double>(width) / 2.0;
+    c.half_h = static_cast<double>(height) / 2.0;
+    c.dz = (cam_z + focal) - cam_z;  // not focal: the sum is rounded first
+    c.dz2 = c.dz * c.dz;
+    return c;
+}
 
 // Host: the spatial sphere chunks of the packet kernel's culls (rt_bvh.cpp): perm[sorted] =
 // original index, bounds = one bounding sphere (cx cy cz R) per 64 sorted spheres.

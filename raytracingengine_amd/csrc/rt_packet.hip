@@ -563,13 +563,11 @@ __device__ __forceinline__ void triangles(const PacketScene& S, d3 o, d3 d, bool
     }
 }
 
-// IntersectClosest for a camera ray (origin = the camera) over the candidate spheres.
-template <int MAXC, int FEAT>
-__device__ __forceinline__ bool closest_camera(const PacketScene& S, const Masks<MAXC>& M,
-                                               int nchunks, d3 o, d3 d, PkHit& h) {
-    bool found = false;
-    double best = 0.0;
-    int prim = -1;
+// The candidate spheres of a camera ray (origin = the camera): closest_camera's sphere part.
+template <int MAXC>
+__device__ __forceinline__ void camera_spheres(const PacketScene& S, const Masks<MAXC>& M,
+                                               int nchunks, d3 o, d3 d, bool& found, double& best,
+                                               int& prim) {
     const double a = dot(d, d);
     const double two_a = 2.0 * a, four_a = 4.0 * a;
     const bool regular = two_a > 0.0;
@@ -605,6 +603,22 @@ __device__ __forceinline__ bool closest_camera(const PacketScene& S, const Masks
             }
         }
     }
+}
+
+// IntersectClosest for a camera ray (origin = the camera) over the candidate spheres.
+template <int MAXC, int FEAT>
+__device__ __forceinline__ bool closest_camera(const PacketScene& S, const Masks<MAXC>& M,
+                                               int nchunks, d3 o, d3 d, PkHit& h) {
+    bool found = false;
+    double best = 0.0;
+    int prim = -1;
+    // Up to 64 spheres (one mask word): a wave whose cone holds no sphere (uniform, an SGPR
+    // compare) goes straight to the planes, which do not read the quadratic's `a`.  The compiler
+    // branches around the reciprocal by itself but leaves a = d·d, 2a, 4a and the range compares
+    // (9 VALU) in front of its test.  With more chunks a similar branch cost C3/C4 2 %; the
+    // area-light variants are left alone (kLean in packet_direct_kernel).
+    if (MAXC > 1 || (FEAT & kFeatArea) != 0 || M.m[0] != 0)
+        camera_spheres<MAXC>(S, M, nchunks, o, d, found, best, prim);
     for (int i = 0; i < S.np; ++i) {
         const double* p = S.pl + kPlStride * i;
         const double denom = dot(mk(p[3], p[4], p[5]), d);
@@ -714,53 +728,62 @@ __device__ __forceinline__ double pk_transmittance(const PacketScene& S, const M
 // Δ of a threshold (1e-6, bias, maxDist), any near hit, or any value out of the fast ranges makes
 // the lane undecided, and undecided lanes run the exact march.  Returns 0 clear, 1 blocked,
 // 2 undecided.  The discriminant (and with it hit/miss) is the reference's FP64 expression.
-template <int MAXC, int FEAT>
-__device__ __forceinline__ int pk_occlusion(const PacketScene& S, const Masks<MAXC>& M,
+template <int MAXC, int FEAT, bool SPH>
+__device__ __forceinline__ int pk_occlusion_t(const PacketScene& S, const Masks<MAXC>& M,
                                             int nchunks, d3 o, d3 d, double max_dist,
                                             double bias) {
     if constexpr ((FEAT & kFeatTris) != 0) return 2;
-    const double a = dot(d, d);
-    const double two_a = 2.0 * a, four_a = 4.0 * a;
-    if (!(two_a >= 0x1p-100 && two_a <= 0x1p100)) return 2;
-    const double inv2a = rcp_refined(two_a);  // within 1 ulp of 1/2a: far inside the Δ margin
     bool blocked = false, undecided = false;
+    // Up to 64 spheres (one mask word): a packet with no sphere candidate (uniform, an SGPR
+    // compare; most of C2's, at 0.44 candidates per shadow ray) goes straight to the planes.
+    // `a` and the range test on 2a serve the sphere classification only — its roots divide by
+    // 2a; the plane classification below never reads them — so the early "undecided" for 2a
+    // outside [2^-100, 2^100] is kept whenever the mask is not empty and skipped with the rest
+    // (8 VALU per light) when it is.  SPH = false is that case as a copy of its own (pk_occlusion
+    // below): one body with the branch inside spilled 8 B more per lane in C2's fix-up variant.
+    if constexpr (SPH) {
+        const double a = dot(d, d);
+        const double two_a = 2.0 * a, four_a = 4.0 * a;
+        if (!(two_a >= 0x1p-100 && two_a <= 0x1p100)) return 2;
+        const double inv2a = rcp_refined(two_a);  // within 1 ulp of 1/2a: far inside the Δ margin
 #pragma unroll
-    for (int c = 0; c < MAXC; ++c) {
-        if (c >= nchunks) break;
-        uint64_t m = M.m[c];
-        while (m) {
-            const int i = c * 64 + __builtin_ctzll(m);
-            m &= m - 1;
-            const double* s = S.sph + kPkSph * i;
-            const d3 oc = o - mk(s[0], s[1], s[2]);
-            const double b = 2.0 * dot(oc, d);
-            const double cc = dot(oc, oc) - s[3];
-            const double disc = b * b - four_a * cc;
-            if (disc < 0.0) continue;  // miss, exactly as the reference decides it
-            if (!(disc == 0.0 || (disc > 1e-30 && disc < 1e30))) {
-                undecided = true;
-                continue;
-            }
-            // |sq − fl(√disc)| ≤ 5e-7·√disc (FP32 conversion + sqrt_f32), so both roots are within
-            // Δ = 2e-6·(|b| + sq)/2a of the reference's fl(fl(−b ∓ sq)/2a) (2× margin)
-            const double sq = static_cast<double>(sqrt_f32(static_cast<float>(disc)));
-            const double delta = 2e-6 * (fabs(b) + sq) * inv2a;
-            double t = (-b - sq) * inv2a;
-            if (!(t >= 1e-6 + delta)) {
-                if (!(t < 1e-6 - delta)) {
+        for (int c = 0; c < MAXC; ++c) {
+            if (c >= nchunks) break;
+            uint64_t m = M.m[c];
+            while (m) {
+                const int i = c * 64 + __builtin_ctzll(m);
+                m &= m - 1;
+                const double* s = S.sph + kPkSph * i;
+                const d3 oc = o - mk(s[0], s[1], s[2]);
+                const double b = 2.0 * dot(oc, d);
+                const double cc = dot(oc, oc) - s[3];
+                const double disc = b * b - four_a * cc;
+                if (disc < 0.0) continue;  // miss, exactly as the reference decides it
+                if (!(disc == 0.0 || (disc > 1e-30 && disc < 1e30))) {
                     undecided = true;
                     continue;
                 }
-                t = (-b + sq) * inv2a;
-                if (t < 1e-6 - delta) continue;  // both roots behind: no hit
+                // |sq − fl(√disc)| ≤ 5e-7·√disc (FP32 conversion + sqrt_f32), so both roots are
+                // within Δ = 2e-6·(|b| + sq)/2a of the reference's fl(fl(−b ∓ sq)/2a) (2× margin)
+                const double sq = static_cast<double>(sqrt_f32(static_cast<float>(disc)));
+                const double delta = 2e-6 * (fabs(b) + sq) * inv2a;
+                double t = (-b - sq) * inv2a;
                 if (!(t >= 1e-6 + delta)) {
-                    undecided = true;
-                    continue;
+                    if (!(t < 1e-6 - delta)) {
+                        undecided = true;
+                        continue;
+                    }
+                    t = (-b + sq) * inv2a;
+                    if (t < 1e-6 - delta) continue;  // both roots behind: no hit
+                    if (!(t >= 1e-6 + delta)) {
+                        undecided = true;
+                        continue;
+                    }
                 }
+                if (t >= max_dist + delta) continue;              // beyond the light
+                if (t > bias + delta && t < max_dist - delta) blocked = true;
+                else undecided = true;                            // near hit or on a boundary
             }
-            if (t >= max_dist + delta) continue;              // beyond the light
-            if (t > bias + delta && t < max_dist - delta) blocked = true;
-            else undecided = true;                            // near hit or on a boundary
         }
     }
     for (int i = 0; i < S.np; ++i) {
@@ -780,6 +803,16 @@ __device__ __forceinline__ int pk_occlusion(const PacketScene& S, const Masks<MA
         else undecided = true;
     }
     return undecided ? 2 : (blocked ? 1 : 0);
+}
+
+template <int MAXC, int FEAT>
+__device__ __forceinline__ int pk_occlusion(const PacketScene& S, const Masks<MAXC>& M,
+                                            int nchunks, d3 o, d3 d, double max_dist,
+                                            double bias) {
+    if constexpr (MAXC == 1 && (FEAT & kFeatArea) == 0)
+        if (M.m[0] == 0)
+            return pk_occlusion_t<MAXC, FEAT, false>(S, M, nchunks, o, d, max_dist, bias);
+    return pk_occlusion_t<MAXC, FEAT, true>(S, M, nchunks, o, d, max_dist, bias);
 }
 
 // Shadow-packet candidates: the origins `so` of the lanes in `casting_lanes` lie in a ball around
@@ -1089,9 +1122,18 @@ __global__ __launch_bounds__(64 * kWgWavesX * WGY, pk_waves(MAXC, FEAT, COUNT, M
     unsigned long long* pk_pub = P.pk_pub;
     uint32_t pk_epoch = P.pk_epoch;
     uint64_t frame_off = 0;
+    // The variants of up to 64 spheres without an area light (C2's) read the camera ray's frame
+    // constants from the host; closest_camera and pk_occlusion skip empty sphere masks for the
+    // same variants.  The others stay as they are: C5's runs at the edge of its register budget
+    // (the plane-only copy of pk_occlusion alone put 8 B more per lane into scratch), and the
+    // variants of more than 64 spheres lost time with such branches before.
+    constexpr bool kLean = MAXC == 1 && (FEAT & kFeatArea) == 0;
+    double cam_dz = P.cam_dz, cam_dz2 = P.cam_dz2;
     if (P.nframes) {
         const PkFrame& F = P.fr[blockIdx.z];
         camp = F.cam;
+        cam_dz = P.fr_dz[blockIdx.z][0];
+        cam_dz2 = P.fr_dz[blockIdx.z][1];
         pk_img = F.img;
         pk_pub = F.pub;
         pk_epoch = F.epoch;
@@ -1199,17 +1241,31 @@ __global__ __launch_bounds__(64 * kWgWavesX * WGY, pk_waves(MAXC, FEAT, COUNT, M
     int samples = 0;
     const int nsamples = MULTI ? P.aa : 1;
     for (int s = 0; s < nsamples; ++s) {
-        // Camera::getRay (Math.h:99-121)
-        double sx = static_cast<double>(xc) - static_cast<double>(P.width) / 2.0;
-        double sy = static_cast<double>(P.height) / 2.0 - static_cast<double>(y);
-        double jx = 0.0, jy = 0.0;
-        if (s > 0 && P.aa > 1) {
-            jx = u01(P.seed, pix, static_cast<uint32_t>(s), 0u);
-            jy = u01(P.seed, pix, static_cast<uint32_t>(s), 1u);
+        // Camera::getRay (Math.h:99-121).  W/2, H/2, dz = (cam.z + focal) − cam.z and dz·dz are
+        // the same for every pixel of the frame: the host forms them (camera_consts, the same
+        // IEEE operations) and they arrive as scalar loads.  FP64 has no scalar ALU here: formed
+        // in the kernel, every lane of every wave converts, halves, adds and squares them.
+        // The other variants keep camera_dir's expression (the same bits): kLean.
+        d3 d;
+        if constexpr (kLean) {
+            double sx = static_cast<double>(xc) - P.half_w;
+            double sy = P.half_h - static_cast<double>(y);
+            // Single sample: the reference adds jx = jy = 0.0.  sx and sy are differences of
+            // finite values, and x − x is +0, never −0, so v + 0.0 == v bit for bit: no adds.
+            if constexpr (MULTI) {
+                double jx = 0.0, jy = 0.0;
+                if (s > 0 && P.aa > 1) {
+                    jx = u01(P.seed, pix, static_cast<uint32_t>(s), 0u);
+                    jy = u01(P.seed, pix, static_cast<uint32_t>(s), 1u);
+                }
+                sx += jx;
+                sy += jy;
+            }
+            const d3 dv = mk(sx - cam.x, sy - cam.y, cam_dz);
+            d = unit_sq(dv, dv.x * dv.x + dv.y * dv.y + cam_dz2);
+        } else {
+            d = camera_dir(P, cam, xc, y, pix, s);
         }
-        sx += jx;
-        sy += jy;
-        const d3 d = unit(mk(sx, sy, cam.z + P.focal) - cam);
 
         d3 col;
         if (P.max_rec <= 0) {

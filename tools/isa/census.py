@@ -3,6 +3,7 @@
 
     python tools/isa/census.py /tmp/pk.s 'packet_direct_kernelILi1ELi0ELb0ELb0ELi1E' [--blocks]
     python tools/isa/census.py /tmp/pk.s packet_direct_kernel --folded
+    python tools/isa/census.py /tmp/pk.s packet_direct_kernel --uniform
 
 Counts the instructions of the kernel by class (FP64 / FP32 / int VALU, v_cndmask, v_mov,
 v_cmp, SALU, LDS, global, branches), and with --blocks prints every basic block with its size
@@ -20,6 +21,12 @@ reported.  Prints one line per such block and exits 1 when there is any.
 --shared N lowers the number of divisions that must share the core's divisor (default 3:
 unit() and light_dir()); --shared 1 also reports a single-division core (plane_t_core,
 sphere_roots_core, reinhard_byte) computed in one block with its full-division fallback.
+
+--uniform lists, for EVERY kernel whose name contains the pattern, the VALU arithmetic and
+conversion instructions all of whose sources are wave-uniform (SGPRs, literals, inline
+constants; propagated through v_mov from such a source and through the listed instructions
+themselves inside a basic block): per-lane work for one value per wave, which belongs on the
+host, once per frame, or behind a wave-uniform branch (tests/test_isa_uniform.py).
 
 A basic block starts at a label (.LBBn_m) or at a fall-through block comment (; %bb.n)."""
 import re
@@ -143,11 +150,80 @@ def folded_blocks(blocks, min_shared=None):
     return hits
 
 
+_MODIFIER_LIST = re.compile(r"\s+\w+:\[[^\]]*\]")
+_CONST = re.compile(r"^(?:0x[0-9a-f]+|[0-9]+(?:\.[0-9]+)?(?:e[-+]?[0-9]+)?|m0|ttmp\d+|ttmp\[\d+:\d+\]|"
+                    r"src_\w+)$")
+_UNIFORM_CLASSES = ("v_f64_arith", "v_f64_special", "v_f32", "v_int/bit")
+# a lane mask (carry, select, scale flag) or the lane number is an input the operands do not show
+_LANE_INPUT = ("addc", "subb", "cndmask", "div_fmas", "mbcnt", "dpp", "sdwa", "permlane", "swap")
+_TWO_DESTS = ("_co_", "div_scale", "mad_u64_u32", "mad_i64_i32")
+
+
+def _strip(operand):
+    """An operand without its sign / abs modifiers and trailing instruction modifiers."""
+    o = operand.split()[0] if operand.split() else ""
+    o = re.sub(r"^(?:neg|abs)\((.*)\)$", r"\1", o)
+    return o.lstrip("-").strip("|")
+
+
+def uniform_valu(blocks):
+    """[(block, instruction)] of the VALU arithmetic and conversion instructions all of whose
+    sources are wave-uniform: SGPRs, literals, inline constants, and VGPRs that hold such a
+    value — written, earlier in the same basic block and not since, by a v_mov from a uniform
+    source or by an instruction reported here.  Every lane of the wave computes the same value:
+    a candidate for the host (once per frame) or for a wave-uniform branch.  Instructions that
+    read a lane mask or the lane number besides their operands are never reported."""
+    hits = []
+    for b, ins in blocks.items():
+        uni = set()  # VGPR numbers holding a wave-uniform value at this point of the block
+        for l in ins:
+            op = l.split()[0]
+            ops = _operands(_MODIFIER_LIST.sub("", l))
+            if not op.startswith("v_"):
+                # loads write their first operand; stores only read it: forgetting is safe
+                d = _regs(ops[0]) if ops else None
+                if d and d[0] == "v":
+                    uni.difference_update(range(d[1], d[2] + 1))
+                continue
+            ndst = 2 if any(k in op for k in _TWO_DESTS) else 1
+            srcs = [_strip(o) for o in ops[ndst:]]
+
+            def is_uniform(o):
+                if _CONST.match(o.lower()):
+                    return True
+                r = _regs(o)
+                if r is None or o.lower().startswith(("vcc", "exec")):
+                    return False
+                return r[0] == "s" or all(k in uni for k in range(r[1], r[2] + 1))
+
+            cls = classify(op)
+            uniform = bool(srcs) and not any(k in op for k in _LANE_INPUT) and \
+                all(is_uniform(o) for o in srcs)
+            dst = _regs(ops[0]) if ops else None
+            if dst and dst[0] == "v":
+                regs = range(dst[1], dst[2] + 1)
+                if uniform and (op.startswith("v_mov_b") or cls in _UNIFORM_CLASSES):
+                    uni.update(regs)
+                else:
+                    uni.difference_update(regs)
+            if uniform and cls in _UNIFORM_CLASSES:
+                hits.append((b, l))
+    return hits
+
+
 def main():
     path, name = sys.argv[1], sys.argv[2]
     found = kernels(open(path).read().splitlines(), name)
     if not found:
         sys.exit(f"no kernel matching {name!r} in {path}")
+    if "--uniform" in sys.argv:
+        for kname, blocks in found.items():
+            hits = uniform_valu(blocks)
+            print(f"{kname}: {len(hits)} VALU arithmetic / conversion instructions with "
+                  f"wave-uniform sources only")
+            for b, l in hits:
+                print(f"  {b:14s} {l}")
+        return
     if "--folded" in sys.argv:
         bad = 0
         shared = int(sys.argv[sys.argv.index("--shared") + 1]) if "--shared" in sys.argv else None
