@@ -64,6 +64,10 @@ def lib():
                                      ctypes.c_uint64, ctypes.c_uint32, vp]
         L.oracle_closest.argtypes = [vp, vp, vp, ctypes.POINTER(ctypes.c_int32)]
         L.oracle_closest.restype = ctypes.c_int
+        L.oracle_trace_rays.argtypes = [vp, vp, vp, ctypes.c_size_t, vp, vp, vp]
+        L.oracle_trace_rays.restype = ctypes.c_int
+        L.oracle_closest_rays.argtypes = [vp, vp, ctypes.c_size_t, vp]
+        L.oracle_closest_rays.restype = None
         L.oracle_transmittance.argtypes = [vp, vp, ctypes.c_double, ctypes.c_double]
         L.oracle_transmittance.restype = ctypes.c_double
         _lib = L
@@ -140,6 +144,33 @@ def closest(sc: SceneData, ray):
     typ = lib().oracle_closest(ctypes.addressof(os_.c), r.ctypes.data, out.ctypes.data,
                                ctypes.byref(idx))
     return typ, idx.value, out
+
+
+def trace_rays(sc: SceneData, rays, max_recursion=10, bias=1e-3, seed=0x5EED, use_area_light=True):
+    """Scene::TraceRay(ray, 0, bias) per ray, the area-light draws keyed by the ray's index.
+    rays [n,6] -> (rgb [n,3] float64, trace, shadow)."""
+    os_ = OracleScene(sc)
+    r = np.ascontiguousarray(rays, np.float64).reshape(-1, 6)
+    out = np.empty((r.shape[0], 3), np.float64)
+    opts = _Opts(max_recursion, 1, bias, seed, 0, 0,
+                 os_.area.ctypes.data if (os_.area is not None and use_area_light) else None)
+    nt, ns = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    rc = lib().oracle_trace_rays(ctypes.addressof(os_.c), ctypes.addressof(opts), r.ctypes.data,
+                                 r.shape[0], out.ctypes.data, ctypes.addressof(nt),
+                                 ctypes.addressof(ns))
+    if rc != 0:
+        raise RuntimeError(f"oracle_trace_rays failed ({rc})")
+    return out, nt.value, ns.value
+
+
+def closest_rays(sc: SceneData, rays) -> np.ndarray:
+    """Scene::IntersectClosest per ray in rt_intersect_rays' layout: rays [n,6] -> [n,9]
+    {type, index, t, normal, hit point}; a miss is {0, -1, 0...}."""
+    os_ = OracleScene(sc)
+    r = np.ascontiguousarray(rays, np.float64).reshape(-1, 6)
+    out = np.empty((r.shape[0], 9), np.float64)
+    lib().oracle_closest_rays(ctypes.addressof(os_.c), r.ctypes.data, r.shape[0], out.ctypes.data)
+    return out
 
 
 # ------------------------------------------------------------------ compiled reference

@@ -12,22 +12,39 @@
 //   curves  <in.f64> <n> <out.f64>            the 7 operator curves before toColor → 7*n*3
 //   kat     sphere|plane|triangle|getray <in.f64> <n> <out.f64>
 //   closest <scene.txt> <rays.f64> <n> <out.f64>   IntersectClosest → n*9 doubles
+//   trace   <scene.txt> <rays.f64> <n> <bias> <out.f64>  Scene::TraceRay(ray, 0, bias) → n*3
 //   ppm     <in.u8> <w> <h> <out.ppm>         writePPM()
-#include "Math.h"
-#include "Shape.h"
-#include "Light.h"
-#include "Scene.h"
-#include "Image.h"
-
+// The standard headers come first so that only the reference's own classes are seen with
+// `private` spelled `public` below: mode `trace` calls Scene::TraceRay, a private member of the
+// reference's Scene (Scene.h:131).  The reference's sources are read where they lie, unedited.
+#include <algorithm>
 #include <chrono>
+#include <cmath>
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
+#include <functional>
 #include <iostream>
+#include <optional>
+#include <random>
+#include <ranges>
 #include <sstream>
+#include <stdexcept>
 #include <string>
 #include <vector>
+#ifdef _OPENMP
+#include <omp.h>
+#endif
+
+#define private public
+#include "Math.h"
+#include "Shape.h"
+#include "Light.h"
+#include "Scene.h"
+#undef private
+#include "Image.h"
 
 // Free functions defined in /root/reference/RaytracingEngine/RaytracingEngine.cpp (linked
 // from that translation unit, compiled with its main() renamed away).
@@ -318,6 +335,28 @@ int mode_closest(int argc, char** argv) {
     return 0;
 }
 
+// Scene::TraceRay(Rayon, 0, bias) per ray (GenerateAntiAliasing's body, Scene.h:306-309, on a
+// caller-given ray instead of camera.getRay's).
+int mode_trace(int argc, char** argv) {
+    if (argc < 7) return 1;
+    Loaded L = load_scene(argv[2]);
+    Scene scene = build_scene(L);
+    size_t n = std::strtoull(argv[4], nullptr, 10);
+    const double bias = std::strtod(argv[5], nullptr);
+    auto rays = read_f64(argv[3], 6 * n);
+    std::vector<double> out;
+    for (size_t i = 0; i < n; ++i) {
+        const double* r = &rays[6 * i];
+        Rayon ray(Vec3(r[0], r[1], r[2]), Vec3(r[3], r[4], r[5]));
+        const Vec3 c = scene.TraceRay(ray, 0, bias).value();
+        out.push_back(c.x);
+        out.push_back(c.y);
+        out.push_back(c.z);
+    }
+    write_bytes(argv[6], out.data(), out.size() * sizeof(double));
+    return 0;
+}
+
 int mode_ppm(int argc, char** argv) {
     if (argc < 6) return 1;
     size_t w = std::strtoull(argv[3], nullptr, 10), h = std::strtoull(argv[4], nullptr, 10);
@@ -352,7 +391,7 @@ int mode_obj(int argc, char** argv) {
 
 int main(int argc, char** argv) {
     if (argc < 2) {
-        std::fprintf(stderr, "usage: ref_harness render|tonemap|curves|kat|closest|ppm ...\n");
+        std::fprintf(stderr, "usage: ref_harness render|tonemap|curves|kat|closest|trace|ppm ...\n");
         return 1;
     }
     std::string m = argv[1];
@@ -362,6 +401,7 @@ int main(int argc, char** argv) {
     else if (m == "curves") rc = mode_curves(argc, argv);
     else if (m == "kat") rc = mode_kat(argc, argv);
     else if (m == "closest") rc = mode_closest(argc, argv);
+    else if (m == "trace") rc = mode_trace(argc, argv);
     else if (m == "ppm") rc = mode_ppm(argc, argv);
     else if (m == "obj") rc = mode_obj(argc, argv);
     if (rc == 1) std::fprintf(stderr, "bad arguments for mode %s\n", m.c_str());

@@ -400,6 +400,27 @@ int oracle_render(const o_scene* sc, const o_camera* cam, const o_opts* opt, dou
     return 0;
 }
 
+/* Scene::TraceRay(ray, 0, bias) per ray (GenerateAntiAliasing's body, Scene.h:306-309).  The
+ * build-defined area-light draws are keyed by the ray's index (pixel = i, sample = 0). */
+int oracle_trace_rays(const o_scene* sc, const o_opts* opt, const double* rays, size_t n,
+                      double* out, uint64_t* trace_rays, uint64_t* shadow_rays) {
+    Ctx c;
+    memset(&c, 0, sizeof c);
+    c.sc = sc;
+    c.opt = opt;
+    for (size_t i = 0; i < n; ++i) {
+        c.pixel = (uint64_t)i;
+        c.sample = 0u;
+        V v = trace(&c, ld3(rays + 6 * i), ld3(rays + 6 * i + 3), 0);
+        out[3 * i + 0] = v.x;
+        out[3 * i + 1] = v.y;
+        out[3 * i + 2] = v.z;
+    }
+    if (trace_rays) *trace_rays += c.ntrace;
+    if (shadow_rays) *shadow_rays += c.nshadow;
+    return 0;
+}
+
 /* ---------------------------------------------------------------- tonemap (RaytracingEngine.cpp) */
 /* ClampVec3 :70-76 */
 static V clamp3(V v, double lo, double hi) {
@@ -493,6 +514,17 @@ int oracle_closest(const o_scene* sc, const double* ray, double* out, int32_t* i
     out[4] = h.p.x; out[5] = h.p.y; out[6] = h.p.z;
     *index = h.index;
     return h.type;
+}
+void oracle_closest_rays(const o_scene* sc, const double* rays, size_t n, double* out9) {
+    for (size_t i = 0; i < n; ++i) {
+        double* w = out9 + 9 * i;
+        int32_t index;
+        int type = oracle_closest(sc, rays + 6 * i, w + 2, &index);
+        w[0] = (double)type;
+        w[1] = (double)index;
+        if (!type)
+            for (int k = 2; k < 9; ++k) w[k] = 0.0;
+    }
 }
 double oracle_transmittance(const o_scene* sc, const double* ray, double max_dist, double bias) {
     return transmittance(sc, ld3(ray), ld3(ray + 3), max_dist, bias);

@@ -66,6 +66,12 @@ double oracle_u01(uint64_t seed, uint64_t pixel, uint32_t stream, uint32_t index
 int oracle_render(const o_scene* sc, const o_camera* cam, const o_opts* opt, double* out,
                   uint64_t* trace_rays, uint64_t* shadow_rays);
 
+/* Scene::TraceRay(ray, 0, bias) for n rays {ox,oy,oz,dx,dy,dz} (any origin, any direction
+ * length) → n*3 doubles.  Ray i draws the build-defined area-light samples with pixel = i,
+ * sample = 0.  opt->row_begin/row_end/nthreads are not read.  Counts as oracle_render. */
+int oracle_trace_rays(const o_scene* sc, const o_opts* opt, const double* rays, size_t n,
+                      double* out, uint64_t* trace_rays, uint64_t* shadow_rays);
+
 /* Tonemap operator `op` (0..6, tonemapAll order) + toColor() for n pixels → n*3 bytes. */
 int oracle_tonemap(const double* hdr, size_t n, int op, uint8_t* out);
 
@@ -80,6 +86,9 @@ void oracle_get_ray(const o_camera* cam, uint32_t x, uint32_t y, int aa, uint64_
 /* Scene::IntersectClosest (Scene.h:218-257): returns prim type (0 none, 1 sphere, 2 plane,
  * 3 triangle) and fills out = {t, nx, ny, nz, px, py, pz} and *index. */
 int oracle_closest(const o_scene* sc, const double* ray, double* out, int32_t* index);
+/* oracle_closest per ray: out9 = {type, index, t, nx, ny, nz, px, py, pz} per ray, a miss is
+ * {0, -1, 0, 0, 0, 0, 0, 0, 0}. */
+void oracle_closest_rays(const o_scene* sc, const double* rays, size_t n, double* out9);
 /* Scene::computeTransmittance (Scene.h:35-77). */
 double oracle_transmittance(const o_scene* sc, const double* ray, double max_dist,
                             double bias);

@@ -9,6 +9,7 @@ and the reference's outputs for them.  The reference has no tests or fixtures of
     python tests/golden/make_golden.py          # rewrites tests/golden/*.npz / *.json
     python tests/golden/make_golden.py --full [name ...]  # full-size frames (FULL2_SCENES)
     python tests/golden/make_golden.py --oracle-full      # C5 (no reference semantics): oracle
+    python tests/golden/make_golden.py --rays             # ray_queries.npz only (tests/raysets.py)
 """
 from __future__ import annotations
 
@@ -302,8 +303,38 @@ def obj_golden():
     print({k: v.shape for k, v in out.items()})
 
 
+def ray_queries_golden():
+    """``--rays``: Scene::TraceRay(ray, 0, bias) and IntersectClosest of the compiled reference
+    on the finite ray families of tests/raysets.py, per scene of raysets.GOLDEN_SCENES.  Writes
+    tests/golden/ray_queries.npz and nothing else."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import raysets
+    if not po.ref_available():
+        po.build()
+    assert po.ref_available(), "oracle/_ref/ref_harness missing (needs the reference sources)"
+    out = {"bias": np.float64(raysets.BIAS), "scenes": np.array(raysets.GOLDEN_SCENES)}
+    with tempfile.TemporaryDirectory() as td:
+        for name in raysets.GOLDEN_SCENES:
+            sc = raysets.scene(name)
+            rays, _ = raysets.rayset(sc)
+            scene_path, rays_path = os.path.join(td, "scene.txt"), os.path.join(td, "rays.f64")
+            sc.write(scene_path)
+            rays.tofile(rays_path)
+            run("trace", scene_path, rays_path, len(rays), repr(raysets.BIAS), os.path.join(td, "tr.out"))
+            run("closest", scene_path, rays_path, len(rays), os.path.join(td, "cl.out"))
+            out[f"{name}_sha256"] = np.array(scene_hash(sc))
+            out[f"{name}_rays"] = rays
+            out[f"{name}_trace"] = np.fromfile(os.path.join(td, "tr.out"), np.float64).reshape(-1, 3)
+            out[f"{name}_closest"] = np.fromfile(os.path.join(td, "cl.out"), np.float64).reshape(-1, 9)
+    path = os.path.join(HERE, "ray_queries.npz")
+    np.savez_compressed(path, **out)
+    print("ray_queries.npz", os.path.getsize(path), "bytes")
+
+
 if __name__ == "__main__":
-    if "--refapp" in sys.argv:
+    if "--rays" in sys.argv:
+        ray_queries_golden()
+    elif "--refapp" in sys.argv:
         refapp_golden()
     elif "--obj" in sys.argv:
         obj_golden()

@@ -1,6 +1,8 @@
 """The full-frame G-buffer pass on the GPU (rt_gbuffer / rt_gbuffer_device, rt_gbuffer.hip).
 
-Reference: rt_intersect_rays (pinned to the compiled reference by the known-answer tests of
+Reference: rt_intersect_rays (pinned to the oracle and to the compiled reference on arbitrary
+rays — sphere, triangle and BVH edge cases, origins inside and on surfaces, any direction
+length — by test_gpu_ray_queries.py, and on camera-like rays by the known-answer tests of
 test_gpu_parity.py) fed with the oracle's Camera::getRay of every pixel; every 7th pixel is also
 checked against the oracle's own IntersectClosest.  Every comparison is on the bits
 (np.array_equal); depth_norm and albedo against numpy's float32 rounding of the reference doubles.
