@@ -461,7 +461,7 @@ rt_status rt_debug_assemble_rows(rt_context* ctx, const void* gathered, size_t r
                                  void* image);
 
 /* Test hook: the packet kernel's costliest-first tile order of `scene` seen from cam->position
- * (rt_capi.cpp tile_order): *tiles / *waves receive the launch shape (0 when the camera has no
+ * (rt_packet_host.cpp tile_order): *tiles / *waves receive the launch shape (0 when the camera has no
  * order state), `order` (capacity `tiles`) the dispatch order once built, `cost` (capacity
  * tiles*waves) the recorded wave durations (100 MHz ticks); either may be NULL. */
 rt_status rt_debug_tile_order(rt_context* ctx, const rt_scene* scene, const rt_camera* cam,

@@ -195,7 +195,7 @@ void build_triangle_bvh(const double* tri, int nt, std::vector<double>& nodes,
 
 namespace rtamd {
 
-// Spatial chunks of spheres for the packet kernel's culls (rt_packet.hip): a permutation that
+// Spatial chunks of spheres for the packet kernel's culls (rt_packet_device.hpp): a permutation that
 // puts spheres close together into the same 64-sphere chunk (recursive splits of the centre
 // bounds along their longest axis, left parts a multiple of 64), and a bounding sphere per chunk
 // that contains every sphere of the chunk.  A cull whose bound excludes a chunk's bounding

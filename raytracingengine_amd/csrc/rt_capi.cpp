@@ -7,8 +7,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <atomic>
-#include <array>
 #include <cmath>
 #include <cstdlib>
 #include <cstdio>
@@ -207,334 +205,6 @@ rt_status build_params(rt_context* ctx, const rt_scene* sc, const rt_camera* cam
                                   static_cast<size_t>(kLtStride) * sc->nl);
     lds = lds_bytes <= ctx->lds_limit;
     return RT_OK;
-}
-
-// The packet kernel's LDS image for this scene and camera (p.pk_image): looked up by camera
-// position and formed by one setup launch the SECOND time a camera is rendered, then copied by
-// every workgroup instead of being recomputed per workgroup.  A camera seen once (a moving
-// camera) takes the in-kernel prologue and costs no setup launch; the last kMaxPkSeen such
-// positions are remembered.  Past kMaxPkImages cached cameras the kernel forms it in LDS.
-constexpr size_t kMaxPkImages = 16;
-constexpr size_t kMaxPkSeen = 16;
-// Launch shapes (grid, row set) with their own costliest-first tile order per cached camera.
-constexpr size_t kMaxTileOrders = 8;
-// A camera without a cached image gets a publish slot instead: the launch's first workgroup
-// forms the image and hands it to the later ones through {epoch, word} granules (rt_packet.hip).
-// Slots rotate so that launches in flight on other streams keep theirs; a slot overwritten by a
-// later launch only fails its tags (the workgroup then forms the image itself).  Images above
-// kPkPubMaxWords 32-bit words (4 KiB, about 32 spheres) are formed per workgroup: reading twice
-// their size in granules costs as much as forming them (moving camera, MI355X: C2's 1.9 KiB
-// image 54.1 -> 50.8 us; C3's 14.3 KiB 555 -> 555 us; C5's 6.5 KiB 522 -> 530 us).
-constexpr size_t kPkPubSlots = 32;
-constexpr size_t kPkPubMaxWords = 1024;
-// Epochs are unique across the process (not per scene): a slot whose memory held another
-// scene's granules (a freed and re-allocated buffer) can never match a later launch's tags.
-std::atomic<uint32_t> g_pk_epoch{0};
-rt_status packet_publish_slot(rt_context* ctx, const rt_scene* sc, TraceParams& p) {
-    const size_t words = packet_lds_bytes(p.ns, p.np, p.nl) / 4;
-    static const bool off = [] {  // RTAMD_PK_PUB=0: every workgroup forms it (A/B runs)
-        const char* e = std::getenv("RTAMD_PK_PUB");
-        return e && std::atoi(e) == 0;
-    }();
-    if (off || words > kPkPubMaxWords) return RT_OK;
-    const size_t slot = kPkPubMaxWords * sizeof(unsigned long long);
-    if (!sc->pk_pub.ptr) {
-        // zeroed (epoch 0 is never used) and complete before any stream's launch reads it
-        RT_HIP(sc->pk_pub.ensure(kPkPubSlots * slot));
-        RT_HIP(hipMemsetAsync(sc->pk_pub.ptr, 0, kPkPubSlots * slot, ctx->stream));
-        RT_HIP(hipStreamSynchronize(ctx->stream));
-    }
-    uint32_t ep = ++g_pk_epoch;
-    if (ep == 0) ep = ++g_pk_epoch;
-    p.pk_epoch = ep;
-    // the first resident round: 256 CUs x 10 workgroups of 128 threads (20 waves per CU)
-    static const long first_env = [] {
-        const char* e = std::getenv("RTAMD_PK_PUB_FIRST");
-        return e ? std::atol(e) : -1L;
-    }();
-    int cus = 0;
-    RT_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
-    p.pk_pub_first = first_env >= 0 ? static_cast<uint32_t>(first_env)
-                                    : static_cast<uint32_t>(cus > 0 ? cus : 256) * 10u;
-    p.pk_pub = reinterpret_cast<unsigned long long*>(static_cast<char*>(sc->pk_pub.ptr) +
-                                                     (ep % kPkPubSlots) * slot);
-    return RT_OK;
-}
-// Costliest tiles first (rt_packet.hip packet_order_kernel): the launch that creates a camera's
-// packet image also records every wave's duration; the next launch of the same shape sorts the
-// tiles by them (one small kernel, once) and every later one dispatches the costliest tiles
-// first, so the cheapest fill the partly idle end of the launch.  The order only permutes which
-// workgroup renders which tile: every pixel is computed by the same instructions, so images do
-// not change (RT_FLAG_NO_TILE_ORDER: the default order, for A/B runs and the tests).  `*rec`
-// receives the entry whose recording launch enqueue_render marks complete.
-// existing_only: use an order already built for this shape, never record or build one (frame
-// batches with several cameras: their launch neither pays the recording nor waits on a build).
-rt_status tile_order(rt_context* ctx, rt_scene::PkImage& im, TraceParams& p, int flags,
-                     rt_scene::PkImage::TileOrder** rec, bool existing_only = false) {
-    *rec = nullptr;
-    if (flags & RT_FLAG_NO_TILE_ORDER) return RT_OK;
-    uint32_t gx, gy, waves;
-    packet_grid(p, gx, gy, waves);
-    const uint32_t key[8] = {gx, gy, waves, p.width, p.height, p.rows, p.row0,
-                             (p.row_block << 16) ^ p.row_stride};
-    const uint32_t tiles = gx * gy;
-    size_t idx = 0;
-    while (idx < im.ords.size() && std::memcmp(im.ords[idx].key, key, sizeof key) != 0) ++idx;
-    if (existing_only && (idx == im.ords.size() || im.ords[idx].state != 2)) return RT_OK;
-    if (idx == im.ords.size()) {  // a new launch shape: record this launch
-        if (im.ords.size() >= kMaxTileOrders) return RT_OK;  // the default order
-        if (im.ords.capacity() < kMaxTileOrders) im.ords.reserve(kMaxTileOrders);
-        im.ords.emplace_back();
-        auto& o = im.ords.back();
-        im.last_ord = static_cast<int>(idx);
-        hipError_t e = o.cost.ensure(sizeof(uint32_t) * tiles * waves);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&o.recorded, hipEventDisableTiming);
-        if (e != hipSuccess) {
-            o.cost.release();
-            im.ords.pop_back();
-            im.last_ord = -1;
-            return hip_fail(e, "tile order");
-        }
-        std::memcpy(o.key, key, sizeof key);
-        o.state = 1;
-        p.tile_cost = static_cast<uint32_t*>(o.cost.ptr);
-        *rec = &o;
-        return RT_OK;
-    }
-    auto& o = im.ords[idx];
-    im.last_ord = static_cast<int>(idx);
-    if (o.state == 1) {  // build the order (after the recording launch, on whatever stream)
-        RT_HIP(o.keys.ensure(sizeof(uint32_t) * tiles));
-        RT_HIP(o.order.ensure(sizeof(uint32_t) * tiles));
-        if (!o.built) RT_HIP(hipEventCreateWithFlags(&o.built, hipEventDisableTiming));
-        if (!o.verdict) RT_HIP(hipHostMalloc(reinterpret_cast<void**>(&o.verdict), sizeof(uint32_t)));
-        __atomic_store_n(o.verdict, 0u, __ATOMIC_RELAXED);
-        RT_HIP(hipStreamWaitEvent(ctx->stream, o.recorded, 0));
-        RT_HIP(launch_packet_order(static_cast<const uint32_t*>(o.cost.ptr), gx, gy, waves,
-                                   static_cast<uint32_t*>(o.keys.ptr),
-                                   static_cast<uint32_t*>(o.order.ptr), o.verdict, ctx->stream));
-        RT_HIP(hipEventRecord(o.built, ctx->stream));
-        o.state = 2;
-    } else {
-        // a narrow cost distribution keeps the default order: no table at all (the verdict is
-        // only ever read as "narrow" once the order kernel has written it)
-        if (__atomic_load_n(o.verdict, __ATOMIC_RELAXED) == 1u) return RT_OK;
-        RT_HIP(hipStreamWaitEvent(ctx->stream, o.built, 0));  // built on another stream
-    }
-    p.tile_order = static_cast<const uint32_t*>(o.order.ptr);
-    return RT_OK;
-}
-
-// A launch whose camera has no image entry yet (a moving camera): an order built earlier for the
-// same launch shape under another camera of the scene, if any — an order only permutes which
-// workgroup renders which tile, and nearby cameras share their costly tiles.
-rt_status scene_tile_order(rt_context* ctx, const rt_scene* sc, TraceParams& p, int flags,
-                           rt_scene::PkImage::TileOrder** rec) {
-    for (auto& im : sc->pk_images) {
-        const rt_status st = tile_order(ctx, im, p, flags, rec, true);
-        if (st != RT_OK || p.tile_order) return st;
-    }
-    return RT_OK;
-}
-
-// The cached image of this camera position, or null; a render on another stream than the one
-// that formed it waits for the entry's event until it has completed.
-rt_status packet_image_cached(rt_context* ctx, const rt_scene* sc, const double* cam,
-                              rt_scene::PkImage** out) {
-    *out = nullptr;
-    for (auto& im : sc->pk_images) {
-        if (std::memcmp(im.cam, cam, sizeof im.cam) != 0) continue;
-        if (!im.done && im.stream != ctx->stream) {
-            const hipError_t q = hipEventQuery(im.ready);
-            if (q == hipSuccess) im.done = true;
-            else if (q == hipErrorNotReady) RT_HIP(hipStreamWaitEvent(ctx->stream, im.ready, 0));
-            else return hip_fail(q, "hipEventQuery");
-        }
-        *out = &im;
-        return RT_OK;
-    }
-    return RT_OK;
-}
-
-// A camera without a cached image: true when it was seen before (the last kMaxPkSeen first
-// sightings) and the cache has room, i.e. it should get a cache entry now (removed from the seen
-// list); otherwise it is remembered as seen once.
-bool packet_second_sighting(const rt_scene* sc, const double* cam) {
-    auto& seen = sc->pk_seen;
-    auto it = std::find_if(seen.begin(), seen.end(), [&](const std::array<double, 3>& c) {
-        return std::memcmp(c.data(), cam, 3 * sizeof(double)) == 0;
-    });
-    if (it == seen.end()) {
-        if (seen.size() >= kMaxPkSeen) seen.erase(seen.begin());
-        seen.push_back({cam[0], cam[1], cam[2]});
-        return false;
-    }
-    if (sc->pk_images.size() >= kMaxPkImages) return false;
-    seen.erase(it);
-    return true;
-}
-
-// A new cache entry for this camera (its buffer allocated, its event created; the caller
-// enqueues the launch that forms the image and records `ready` after it on ctx->stream).
-rt_status packet_image_entry(rt_context* ctx, const rt_scene* sc, const double* cam,
-                             const TraceParams& p, rt_scene::PkImage** out) {
-    *out = nullptr;
-    // never reallocated: a frame batch holds entries of earlier frames while adding one
-    if (sc->pk_images.capacity() < kMaxPkImages) sc->pk_images.reserve(kMaxPkImages);
-    sc->pk_images.emplace_back();
-    rt_scene::PkImage& im = sc->pk_images.back();
-    std::memcpy(im.cam, cam, sizeof im.cam);
-    im.stream = ctx->stream;
-    hipError_t e = im.buf.ensure(packet_lds_bytes(p.ns, p.np, p.nl));
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&im.ready, hipEventDisableTiming);
-    if (e != hipSuccess) {
-        im.buf.release();
-        if (im.ready) (void)hipEventDestroy(im.ready);
-        sc->pk_images.pop_back();
-        return hip_fail(e, "packet image entry");
-    }
-    *out = &im;
-    return RT_OK;
-}
-
-// One-frame launches: the cached image; on a camera's second sighting a one-workgroup setup
-// launch forms its cache entry; on a first sighting a publish slot.
-rt_status packet_image(rt_context* ctx, const rt_scene* sc, TraceParams& p, int flags,
-                       rt_scene::PkImage::TileOrder** rec) {
-    *rec = nullptr;
-    rt_scene::PkImage* found = nullptr;
-    rt_status st = packet_image_cached(ctx, sc, p.cam_pos, &found);
-    if (st != RT_OK) return st;
-    if (found) {
-        p.pk_image = static_cast<const double*>(found->buf.ptr);
-        return tile_order(ctx, *found, p, flags, rec);
-    }
-    if (!packet_second_sighting(sc, p.cam_pos)) {
-        const rt_status st2 = packet_publish_slot(ctx, sc, p);
-        return st2 != RT_OK ? st2 : scene_tile_order(ctx, sc, p, flags, rec);
-    }
-    rt_scene::PkImage* im = nullptr;
-    st = packet_image_entry(ctx, sc, p.cam_pos, p, &im);
-    if (st != RT_OK) return st;
-    hipError_t e = launch_packet_image(p, static_cast<double*>(im->buf.ptr), ctx->stream);
-    if (e == hipSuccess) e = hipEventRecord(im->ready, ctx->stream);
-    if (e != hipSuccess) {
-        im->buf.release();
-        (void)hipEventDestroy(im->ready);
-        sc->pk_images.pop_back();
-        return hip_fail(e, "packet image setup");
-    }
-    p.pk_image = static_cast<const double*>(im->buf.ptr);
-    return tile_order(ctx, *im, p, flags, rec);
-}
-
-// A frame batch's image sources (p.fr[f].img for every frame, before the batch launch): a
-// cached image, or one formed by ONE small launch for every frame that has none — into a new
-// cache entry when the camera was seen before (so a revisited position costs no launch of its
-// own), else into the batch's ring slot (an entry of kPkBatchRing, reused once the launches that
-// read it have completed).  Frames with the camera of an earlier frame of the batch share its
-// image.  The tile order: frame 0's, recorded / built only when every frame has frame 0's
-// camera (a static camera), otherwise only an order built earlier for the shape.
-rt_status packet_batch_images(rt_context* ctx, const rt_scene* sc, const rt_camera* cams,
-                              int nframes, TraceParams& p, int flags,
-                              rt_scene::PkImage::TileOrder** rec, int* batch_ring) {
-    *rec = nullptr;
-    *batch_ring = -1;
-    enum Kind { kCached, kPromote, kRing, kDup };
-    Kind kind[kPkMaxBatch];
-    int dup_of[kPkMaxBatch];
-    rt_scene::PkImage* ent[kPkMaxBatch] = {};
-    bool same_cam = true;
-    bool any_ring = false;
-    const size_t cache_before = sc->pk_images.size();
-    // Every error exit after the first promotion drops the entries this call created (newest
-    // last): an entry that never received its image, with a `ready` event never recorded, would
-    // be taken as a formed image by every later render from that camera position.
-    struct Rollback {
-        const rt_scene* sc;
-        size_t keep;
-        bool armed = true;
-        ~Rollback() {
-            if (!armed) return;
-            while (sc->pk_images.size() > keep) {
-                auto& im = sc->pk_images.back();
-                im.buf.release();
-                if (im.ready) (void)hipEventDestroy(im.ready);
-                sc->pk_images.pop_back();
-            }
-        }
-    } rollback{sc, cache_before};
-    for (int f = 0; f < nframes; ++f) {
-        PkFrame& F = p.fr[f];
-        for (int i = 0; i < 3; ++i) F.cam[i] = cams[f].position[i];
-        // (width, height and focal are the batch's: rt_render_batch checked them)
-        const CameraConsts cc = camera_consts(p.width, p.height, F.cam[2], p.focal);
-        p.fr_dz[f][0] = cc.dz;
-        p.fr_dz[f][1] = cc.dz2;
-        F.img = nullptr;
-        F.pub = nullptr;
-        F.epoch = 0;
-        F._pad = 0;
-        if (std::memcmp(F.cam, p.fr[0].cam, sizeof F.cam) != 0) same_cam = false;
-        int g = 0;
-        while (g < f && std::memcmp(p.fr[g].cam, F.cam, sizeof F.cam) != 0) ++g;
-        if (g < f) {
-            kind[f] = kDup;
-            dup_of[f] = g;
-            continue;
-        }
-        rt_status st = packet_image_cached(ctx, sc, F.cam, &ent[f]);
-        if (st != RT_OK) return st;
-        if (ent[f]) {
-            kind[f] = kCached;
-            F.img = static_cast<const double*>(ent[f]->buf.ptr);
-            continue;
-        }
-        if (packet_second_sighting(sc, F.cam)) {
-            st = packet_image_entry(ctx, sc, F.cam, p, &ent[f]);
-            if (st != RT_OK) return st;
-            kind[f] = kPromote;
-            F.img = static_cast<const double*>(ent[f]->buf.ptr);
-            continue;
-        }
-        kind[f] = kRing;
-        any_ring = true;
-    }
-    const size_t img_doubles = ((packet_lds_bytes(p.ns, p.np, p.nl) + 255) & ~size_t(255)) /
-                               sizeof(double);
-    double* ring = nullptr;
-    if (any_ring) {
-        const size_t entry = img_doubles * sizeof(double) * kPkMaxBatch;
-        RT_HIP(sc->pk_batch.ensure(entry * rt_scene::kPkBatchRing));
-        const int r = sc->pk_batch_next;
-        sc->pk_batch_next = (r + 1) % rt_scene::kPkBatchRing;
-        if (!sc->pk_batch_done[r])
-            RT_HIP(hipEventCreateWithFlags(&sc->pk_batch_done[r], hipEventDisableTiming));
-        if (sc->pk_batch_used[r])  // the batch that last read this entry, on any stream
-            RT_HIP(hipStreamWaitEvent(ctx->stream, sc->pk_batch_done[r], 0));
-        ring = reinterpret_cast<double*>(static_cast<char*>(sc->pk_batch.ptr) +
-                                         static_cast<size_t>(r) * entry);
-        *batch_ring = r;
-    }
-    PkImageJobs jobs;
-    std::memset(&jobs, 0, sizeof jobs);
-    for (int f = 0; f < nframes; ++f) {
-        PkFrame& F = p.fr[f];
-        if (kind[f] == kRing) F.img = ring + static_cast<size_t>(f) * img_doubles;
-        if (kind[f] == kDup) F.img = p.fr[dup_of[f]].img;
-        if (kind[f] == kRing || kind[f] == kPromote) {
-            jobs.dst[jobs.n] = const_cast<double*>(F.img);
-            jobs.frame[jobs.n] = f;
-            ++jobs.n;
-        }
-    }
-    hipError_t e = launch_packet_image_batch(p, jobs, ctx->stream);
-    for (int f = 0; f < nframes && e == hipSuccess; ++f)
-        if (kind[f] == kPromote) e = hipEventRecord(ent[f]->ready, ctx->stream);
-    if (e != hipSuccess) return hip_fail(e, "packet batch images");  // the rollback drops them
-    rollback.armed = false;  // every promoted entry now has its image and its recorded event
-    if (kind[0] == kCached) return tile_order(ctx, *ent[0], p, flags, rec, !same_cam);
-    return scene_tile_order(ctx, sc, p, flags, rec);
 }
 
 // Whether a render of this TraceRay shape takes the breadth-first path, whose arena (ctx->wf,

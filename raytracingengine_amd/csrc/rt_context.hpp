@@ -114,7 +114,7 @@ struct rt_scene {
         hipEvent_t ready = nullptr;
         hipStream_t stream = nullptr;
         bool done = false;
-        // Costliest-first tile order of the packet kernel for this camera (rt_capi.cpp
+        // Costliest-first tile order of the packet kernel for this camera (rt_packet_host.cpp
         // tile_order): the wave durations one launch records, then the order built from them,
         // for launches of the same shape (grid, rows) — state 1 recorded, 2 ordered.  One entry
         // per launch shape (up to kMaxTileOrders), each written once and never rewritten, so a
@@ -133,7 +133,7 @@ struct rt_scene {
     };
     mutable std::vector<PkImage> pk_images;
     mutable std::vector<std::array<double, 3>> pk_seen;  // cameras rendered once, no image yet
-    // Cameras without an image: a ring of kPkPubSlots publish slots (rt_packet.hip, in-launch
+    // Cameras without an image: a ring of kPkPubSlots publish slots (rt_packet_host.cpp, in-launch
     // image hand-off), each launch tagged with its own epoch; zeroed once at allocation.
     mutable rtamd::DeviceBuffer pk_pub;
     // Frame batches with cameras that have no cached image (a moving camera): one small launch
@@ -166,6 +166,16 @@ rt_status enqueue_frames(rt_context* ctx, const rt_scene* sc, const rt_camera* c
                          const rt_render_opts* opts, double* d64, float* d32, uint8_t* dldr,
                          uint32_t frame_rows = 0);
 rt_status check_batch(const rt_camera* cams, int nframes);
+// rt_packet_host.cpp, for enqueue_frames before a packet launch.  One frame: p.pk_image from the
+// scene's cache of camera images, a setup launch on a camera's second sighting, or a publish
+// slot (p.pk_pub); a batch: p.fr[f] for every frame and *batch_ring = the ring entry its formed
+// images took, or -1.  Both set p.tile_order / p.tile_cost and *rec, the tile-order entry whose
+// recording launch the caller marks complete.
+rt_status packet_image(rt_context* ctx, const rt_scene* sc, TraceParams& p, int flags,
+                       rt_scene::PkImage::TileOrder** rec);
+rt_status packet_batch_images(rt_context* ctx, const rt_scene* sc, const rt_camera* cams,
+                              int nframes, TraceParams& p, int flags,
+                              rt_scene::PkImage::TileOrder** rec, int* batch_ring);
 // Whether a render takes the breadth-first TraceRay path, whose arena is one per context (as are
 // the ray counters): renders that use them are ordered across streams (scratch_wait/_done).
 bool uses_wavefront_arena(int path, int flags);

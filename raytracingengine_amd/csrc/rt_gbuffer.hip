@@ -3,9 +3,9 @@
 // false)), written out as depth (HitInfo::distance), normalised depth (HitInfo::normalizedDistance,
 // Shape.h:40-42), geometric normal, primitive {type, index} and base colour.
 //
-// Primary visibility does not depend on materials, so the packet machinery of rt_packet.hip
-// (the camera-constant LDS image, cull_cone, closest_camera) serves every scene type here —
-// chains and trees too — without its light records, shadow code or tonemap:
+// Primary visibility does not depend on materials, so the packet machinery of
+// rt_packet_device.hpp (the camera-constant LDS image, cull_cone, closest_camera) serves every
+// scene type here — chains and trees too — without its light records, shadow code or tonemap:
 //
 //  * gbuffer_packet_kernel<MAXC, TRIS, TW>: one wave = one TW × 64/TW pixel tile, for scenes
 //    inside the packet limits (≤ packet_max_spheres() spheres, image within the LDS limit).
@@ -15,9 +15,8 @@
 //
 // Both produce the bits rt_intersect_rays returns for the same ray: the same roots, plane
 // quotients and triangle tests in the reference's order (the packet kernel only skips candidates
-// that provably cannot win, rt_packet.hip), the same hit point cam + d·t and unit(p − C).
-#define RT_PACKET_GBUFFER_TU 1
-#include "rt_packet.hip"
+// that provably cannot win, rt_packet_device.hpp), the same hit point cam + d·t and unit(p − C).
+#include "rt_packet_device.hpp"
 
 #pragma clang fp contract(off)
 
@@ -64,6 +63,7 @@ __global__ __launch_bounds__(256, gb_waves(MAXC, TRIS)) void gbuffer_packet_kern
     constexpr int FEAT = TRIS ? kFeatTris : 0;
     const int tid = threadIdx.x, nthreads = blockDim.x;
     const int ns = P.ns, np = P.np, nl = P.nl, nb = pk_chunk_bounds(ns), nsb = ns + nb;
+    // (the image layout: pk_build_image, rt_packet_device.hpp, is the format's definition)
     double* s_sph = smem;
     double* s_pl = s_sph + kPkSph * nsb;
     double* s_pln = s_pl + kPlStride * np + kLtStride * nl;
@@ -175,7 +175,7 @@ bool gbuffer_packet_fits(const TraceParams& p, size_t lds_limit) {
 template <int MAXC, bool TRIS, int TW>
 static void launch_gb_packet(const TraceParams& p, const GbOut& g, hipStream_t stream) {
     size_t lds = pk_image_bytes(p.ns, p.np, p.nl);
-    const unsigned wgy = 10 * lds <= kLdsPerCu ? 1u : 2u;  // launch_packet_variant's choice
+    const unsigned wgy = pk_wgy(lds);
     const dim3 block(64 * kWgWavesX * wgy);
     if constexpr (TRIS) lds += sizeof(int) * kPkStack * (block.x / 64);
     constexpr unsigned TH = 64 / TW;

@@ -3,7 +3,7 @@
 // many HIP streams of the context's device, so that one frame's launch tail (its last, partly
 // idle wave rounds) overlaps the next frame's start.  Frames are independent: the queue adds no
 // dependency between them (a camera's cached packet image, shared by frames on different
-// streams, is waited for through its own event — rt_capi.cpp packet_image) — except frames
+// streams, is waited for through its own event — rt_packet_host.cpp packet_image) — except frames
 // that use scratch the context holds once: the breadth-first TraceRay arena of refraction-tree
 // scenes (ctx->wf / wf_ctl) and the ray counters.  enqueue_frames orders such a render after
 // the previous one on any stream of the context (scratch_wait / scratch_done, rt_capi.cpp), so

@@ -1,5 +1,5 @@
 // rt_trace_common.hpp — device building blocks of the trace kernels, shared by the generic
-// kernels (rt_trace.hip) and the packet-culled fast kernel (rt_packet.hip).
+// kernels (rt_trace.hip) and the packet-culled fast kernel (rt_packet_kernel.hpp).
 //
 // Reference functions restated (paths relative to /root/reference/RaytracingEngine):
 //   IntersectClosest Scene.h:218-257 (Sphere::Intersect Shape.h:72-98, Plane::Intersect
@@ -473,7 +473,7 @@ __device__ __forceinline__ uint64_t wf_shadow_mask(const SceneView& S, bool cast
 // explicit error bound Δ of the roots; planes by comparing num with x·denom (1e-9 relative
 // margin) instead of dividing.  Any root within Δ of a threshold (1e-6, bias, maxDist), any near
 // hit, triangles, or values outside the fast ranges return -1 and the exact march runs.
-// Same classification as the packet kernel's pk_occlusion (rt_packet.hip), over every sphere.
+// Same classification as the packet kernel's pk_occlusion (rt_packet_kernel.hpp), over every sphere.
 __device__ __forceinline__ int occlusion_opaque(const SceneView& S, d3 o, d3 d, double max_dist,
                                                 double bias) {
     if (S.nt > 0) return -1;

@@ -3,7 +3,7 @@ reference's frames (tests/golden/make_golden.py --full: SHA-256 of the reference
 RenderImage() and of the bytes of its tonemapAll()/tonemap(), RaytracingEngine.cpp:113-214).
 
 The bench renders C2 from one static camera, so its timed launches read the per-(scene, camera)
-packet image that the SECOND render creates (rt_capi.cpp packet_image); the first render forms
+packet image that the SECOND render creates (rt_packet_host.cpp packet_image); the first render forms
 the image inside the kernel.  Every test here renders each frame three times from one camera —
 fresh, cache-creating, cached — and pins every render.
 
@@ -231,7 +231,7 @@ def _moved(sc, k):
 def test_full_frame_moving_camera_publish_slots(ctx, oracle, name):
     """A camera that moves every frame (the bench's `moving_camera` field): no cached packet
     image, so each launch's first workgroup forms the image and publishes it to a tagged slot
-    that the later workgroups copy (rt_packet.hip, rt_capi.cpp packet_publish_slot).  At 1080p
+    that the later workgroups copy (rt_packet_host.cpp packet_publish_slot).  At 1080p
     a launch has ~16k workgroups, so most of them take the copy.  10 cameras rotate through the
     8 slots (slots 1 and 2 hold an older epoch's granules when reused), rendered back to back
     without a synchronisation, every frame bit-identical to the oracle's HDR and bytes.  C3's

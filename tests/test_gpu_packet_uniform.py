@@ -1,6 +1,6 @@
 """GPU parity of the packet kernel's wave-uniform shortcuts, bit for bit against the C oracle.
 
-packet_direct_kernel (rt_packet.hip), in its variants for scenes of up to 64 spheres, reads the
+packet_direct_kernel (rt_packet_kernel.hpp), in its variants for scenes of up to 64 spheres, reads the
 camera ray's frame constants (W/2, H/2, dz = (cam.z + focal) - cam.z, dz*dz) from the host
 (camera_consts) and sends a wave whose sphere mask is empty straight to the planes, for camera
 rays and for shadow rays.  None of it may change a bit: every frame here is compared with the

@@ -371,7 +371,7 @@ def test_edge_out_of_core_range_vectors(ctx, oracle, scale):
 @pytest.mark.parametrize("offset", [0.0, 1e-300, -1e-200, 1e-13])
 def test_edge_camera_on_or_near_a_plane(ctx, oracle, offset):
     """Planes through (or within a denormal distance of) the camera give camera-ray numerators
-    outside the plane core's range: those planes take the exact division (rt_packet.hip
+    outside the plane core's range: those planes take the exact division (rt_packet_device.hpp
     plane_t); tilted normals give zero / tiny components."""
     sc = _scene(80, 40)
     sc.add_plane((0, offset, -25), (0, 1, 0), Material((0.6, 0.6, 0.6)))  # camera at y = 0
@@ -388,7 +388,7 @@ def _grazing_shadow_scene(gap):
     ball has radius 0) of a floor point lit by a light 0.14 away; a sphere of radius 0.01 sits
     `gap` beyond the segment [so, light] on the side the traced shadow ray deviates to.  The
     ray starts at so = P + n·bias but aims along (light − P), so near the light end it runs
-    ~6e-4 off that segment (rt_packet.hip cull_capsule): with gap = 4e-4 it still passes 2e-4
+    ~6e-4 off that segment (rt_packet_device.hpp cull_capsule): with gap = 4e-4 it still passes 2e-4
     inside the sphere, and the reference shades the pixel black."""
     cam = np.array([0.0, 5.0, 0.0])
     f = 5.0
@@ -421,7 +421,7 @@ def test_edge_shadow_ray_grazing_near_the_light(ctx, oracle, gap):
 
 @pytest.mark.parametrize("gap", [0.0, 5e-4, 2e-3, -3e-4])
 def test_edge_plane_cull_light_near_a_plane(ctx, oracle, gap):
-    """Scenes with ≥ 3 planes cull planes per shadow packet (rt_packet.hip cull_capsule,
+    """Scenes with ≥ 3 planes cull planes per shadow packet (rt_packet_device.hpp cull_capsule,
     kFeatPlanes): lights on, just in front of and just behind a wall (within the bias of the
     shadow rays), tilted planes, and origins on the walls themselves — bit-identical images."""
     sc = _scene(96, 54)
@@ -548,7 +548,7 @@ def _with_camera(sc, k):
 
 def test_packet_image_per_camera(ctx, oracle):
     """The packet kernel's LDS image is formed once per (scene, camera position) on the second
-    render from that camera and then copied by every workgroup (rt_capi.cpp packet_image): 20
+    render from that camera and then copied by every workgroup (rt_packet_host.cpp packet_image): 20
     camera positions on one uploaded scene, each rendered twice (the first render forms the
     image in LDS, the second creates the cached one; past 16 cameras every render forms it in
     LDS), then earlier cameras again (cache hits); every frame equals the oracle's."""
@@ -802,7 +802,7 @@ def test_edge_axis_planes_scene_vs_oracle(ctx, oracle, flags):
 @pytest.mark.parametrize("name,w,h", [("c2", 1920, 1080), ("c3", 1920, 1080), ("c5", 960, 540),
                                       ("c4", 1000, 600)])
 def test_tile_order_is_a_permutation_and_keeps_the_image(ctx, name, w, h):
-    """rt_capi.cpp tile_order: the render that creates a camera's packet image records every
+    """rt_packet_host.cpp tile_order: the render that creates a camera's packet image records every
     wave's duration, the next one builds the dispatch order (rt_packet.hip packet_order_kernel)
     and renders by it.  The order is a permutation of the tiles (every tile rendered exactly
     once) and the image is bit-identical to the unordered renders."""

@@ -7,6 +7,15 @@ FILE is a source under raytracingengine_amd/csrc; the copy (with every replaceme
 each must match) is compiled with the in-tree flags and linked with the in-tree objects of the
 other sources into tools/variants/NAME.so (git-ignored).  Ablation builds render wrong images;
 time them with tools/ab_time.py / tools/pmc_ab.sh only.
+
+When FILE is a header, --src names every source that includes it (without it the tool stops:
+nothing would be recompiled).  The packet kernel's headers:
+
+    ... NAME rt_packet_kernel.hpp 'old' 'new' --src rt_packet.hip,rt_packet_area.hip
+    ... NAME rt_packet_device.hpp 'old' 'new' --src rt_packet.hip,rt_packet_area.hip,rt_gbuffer.hip
+
+--flags replaces the extras of EVERY source listed in --src: with the lines above it would also
+put rt_packet.hip's max-ilp scheduling on rt_packet_area.hip, which is built without it.
 """
 import os, shutil, subprocess, sys, tempfile
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
@@ -30,6 +39,9 @@ while "-D" in args:
     del args[i:i + 2]
 name, fname, reps = args[0], args[1], args[2:]
 assert len(reps) % 2 == 0
+if srcs is None and fname not in B.SOURCES:
+    sys.exit(f"{fname} is not a source of the library (build.py SOURCES): name the sources that "
+             "include it with --src a.hip,b.hip")
 B.build_library()
 tmp = tempfile.mkdtemp()
 src_dir = os.path.join(tmp, "csrc")
