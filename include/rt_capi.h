@@ -468,6 +468,12 @@ rt_status rt_debug_tile_order(rt_context* ctx, const rt_scene* scene, const rt_c
                               uint32_t* order, uint32_t* cost, size_t capacity, uint32_t* tiles,
                               uint32_t* waves, int* state);
 
+/* Test hook (read-only): the packet-kernel frames this context has enqueued so far that read
+ * their camera-cone candidate masks from a per-tile table (*with_table) and those whose waves
+ * formed their own (*without_table).  RTAMD_PK_CONE_TAB=0 in the environment, read per launch,
+ * turns the tables off. */
+rt_status rt_debug_cone_table(rt_context* ctx, uint64_t* with_table, uint64_t* without_table);
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif

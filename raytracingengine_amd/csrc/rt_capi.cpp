@@ -340,6 +340,11 @@ rt_status enqueue_frames(rt_context* ctx, const rt_scene* sc, const rt_camera* c
         st = packet_image(ctx, sc, p, flags, &rec);
         if (st != RT_OK) return st;
     }
+    if (packet) {  // rt_debug_cone_table: which frames read their camera-cone mask from a table
+        for (int f = 0; f < nframes; ++f)
+            ++((nframes > 1 ? p.fr_tab[f] : p.cone_tab) ? ctx->cone_tab_frames
+                                                         : ctx->cone_notab_frames);
+    }
     // the fix-up variant of the packet kernel (undecided shadow rays re-rendered per pixel after
     // the launch) uses the context's fix-up list: ordered across streams like the counters
     const bool fixup = packet && packet_uses_fixup(p, false, sc->max_specular > 0.0);
@@ -803,7 +808,12 @@ rt_status rt_scene_destroy(rt_scene* sc) {
             if (o.built) (void)hipEventDestroy(o.built);
             if (o.verdict) (void)hipHostFree(o.verdict);
         }
+        for (auto& t : im.tabs) {
+            t.buf.release();
+            if (t.ready) (void)hipEventDestroy(t.ready);
+        }
     }
+    for (auto& b : sc->pk_batch_tab) b.release();
     delete sc;
     return RT_OK;
 }
@@ -1110,6 +1120,14 @@ rt_status rt_debug_tile_order(rt_context* ctx, const rt_scene* sc, const rt_came
         }
         return RT_OK;
     }
+    return RT_OK;
+}
+
+rt_status rt_debug_cone_table(rt_context* ctx, uint64_t* with_table, uint64_t* without_table) {
+    if (!ctx || !with_table || !without_table)
+        return fail(RT_ERR_INVALID_ARG, "NULL argument to rt_debug_cone_table");
+    *with_table = ctx->cone_tab_frames;
+    *without_table = ctx->cone_notab_frames;
     return RT_OK;
 }
 

@@ -80,6 +80,8 @@ struct rt_context {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> free_events;
     double timed_ms = 0.0;
     uint64_t launches = 0;
+    // packet-kernel frames enqueued with / without a camera-cone table (rt_debug_cone_table)
+    uint64_t cone_tab_frames = 0, cone_notab_frames = 0;
     // rt_render_multi: RCCL communicators over the devices of the last context list this
     // context led (rt_multi.cpp); destroyed with the context
     std::vector<rt_context*> group_ctxs;
@@ -130,6 +132,21 @@ struct rt_scene {
         };
         std::vector<TileOrder> ords;
         int last_ord = -1;  // the entry of the latest launch (rt_debug_tile_order)
+        // Camera-cone mask tables of this camera (rt_cone_table.hpp), one per launch shape and
+        // camera-ray constants (cone_table_key: the focal length is the render call's; up to
+        // kMaxConeTabs, later shapes or focal lengths go without): written once by
+        // packet_cone_table_kernel on the stream of the render that created it, never rewritten;
+        // renders on other streams wait for `ready` until it has completed.  Dropped with the
+        // image entry.
+        struct ConeTab {
+            static constexpr size_t kKeyWords = 16;
+            uint32_t key[kKeyWords] = {};
+            rtamd::DeviceBuffer buf;
+            hipEvent_t ready = nullptr;
+            hipStream_t stream = nullptr;
+            bool done = false;
+        };
+        std::vector<ConeTab> tabs;
     };
     mutable std::vector<PkImage> pk_images;
     mutable std::vector<std::array<double, 3>> pk_seen;  // cameras rendered once, no image yet
@@ -145,6 +162,9 @@ struct rt_scene {
     mutable hipEvent_t pk_batch_done[kPkBatchRing] = {nullptr, nullptr, nullptr, nullptr};
     mutable bool pk_batch_used[kPkBatchRing] = {false, false, false, false};
     mutable int pk_batch_next = 0;
+    // ... and the cone tables of those frames, one buffer per ring entry (the table's size is
+    // the launch shape's, so an entry grows on demand, after the batch that last read it)
+    mutable rtamd::DeviceBuffer pk_batch_tab[kPkBatchRing];
 };
 
 namespace rtamd {

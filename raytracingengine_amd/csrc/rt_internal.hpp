@@ -130,7 +130,16 @@ struct TraceParams {
     // see the layout they were tuned with)
     double half_w, half_h, cam_dz, cam_dz2;
     double fr_dz[kPkMaxBatch][2];
+    // packet kernel, single-sample variants of up to 64 spheres: the camera-cone candidate mask
+    // of every wave tile (rt_cone_table.hpp), one 64-bit word per tile at
+    // (tby · gx + tbx) · waves + wave, formed by packet_cone_table_kernel before the launch; null:
+    // the wave forms its own.  fr_tab[f]: frame f's of a batch (after fr_dz, as fr_dz after fr[])
+    const unsigned long long* cone_tab;
+    const unsigned long long* fr_tab[kPkMaxBatch];
 };
+// the runtime passes at most 4 KiB of kernel arguments (packet_image_batch_kernel and
+// packet_cone_table_kernel take a job list of kPkMaxBatch pointers and ints next to it)
+static_assert(sizeof(TraceParams) + 12 * kPkMaxBatch + 32 <= 4096, "kernel arguments above 4 KiB");
 
 // Camera::getRay's frame constants (Math.h:99-121): the single IEEE double operations of the
 // device expression, in its order, so a kernel that reads them computes the bits it computed
@@ -191,6 +200,18 @@ struct PkImageJobs {
 };
 hipError_t launch_packet_image_batch(const TraceParams& p, const PkImageJobs& jobs,
                                      hipStream_t stream);
+// The camera-cone tables (TraceParams.cone_tab / fr_tab) one launch forms: job j writes the
+// table of frame frame[j] (-1: the one-frame launch's camera, p.cam_pos / p.pk_image) to dst[j],
+// reading the frame's packet image, formed earlier on the stream.
+struct PkConeJobs {
+    unsigned long long* dst[kPkMaxBatch];
+    int32_t frame[kPkMaxBatch];
+    int32_t n;
+};
+hipError_t launch_packet_cone_tables(const TraceParams& p, const PkConeJobs& jobs,
+                                     hipStream_t stream);
+// Whether p's launch is served by a variant that reads a cone table.
+bool packet_reads_cone_table(const TraceParams& p, bool any_specular);
 // The packet kernel's launch shape for p (grid of workgroups, waves per workgroup), and the
 // costliest-first tile order built from the wave durations a launch of that shape recorded.
 void packet_grid(const TraceParams& p, uint32_t& gx, uint32_t& gy, uint32_t& waves);

@@ -3,6 +3,7 @@
 // (rt_packet_area.hip) with the dispatch that picks one, and the auxiliary kernels of the
 // packet path with their launchers — the camera image (one, or a batch's), the fix-up of
 // queued pixels and the costliest-first tile order.
+#include "rt_cone_table.hpp"
 #include "rt_packet_kernel.hpp"
 
 #pragma clang fp contract(off)
@@ -41,6 +42,57 @@ hipError_t launch_packet_image_batch(const TraceParams& p, const PkImageJobs& jo
             return hipErrorInvalidValue;
     hipLaunchKernelGGL(packet_image_batch_kernel, dim3(static_cast<unsigned>(jobs.n)),
                        dim3(256), 0, stream, p, jobs);
+    return hipGetLastError();
+}
+
+// The camera-cone candidate masks of a launch's wave tiles (rt_cone_table.hpp), one lane per
+// tile and one grid row per job: a one-frame launch's camera, or every frame of a batch that
+// has no cached table.  The per-sphere terms are the packet image's (cone_terms), formed
+// earlier on the stream.  Tables are indexed by tile — (tby · gx + tbx) · waves + wave — not by
+// dispatch position: the tile order permutes dispatch, not tiles.
+constexpr int kConeThreads = 256;
+__global__ __launch_bounds__(kConeThreads) void packet_cone_table_kernel(TraceParams P,
+                                                                         PkConeJobs J, uint32_t gx,
+                                                                         uint32_t gy,
+                                                                         uint32_t waves) {
+    __shared__ float s_terms[64 * 8];
+    const int f = J.frame[blockIdx.y];
+    const double* camp = f < 0 ? P.cam_pos : P.fr[f].cam;
+    const double* img = f < 0 ? P.pk_image : P.fr[f].img;
+    const double dz = f < 0 ? P.cam_dz : P.fr_dz[f][0];
+    const int ns = P.ns < 64 ? P.ns : 64;  // (the launcher checked P.ns <= 64)
+    for (int i = threadIdx.x; i < 8 * ns; i += kConeThreads)
+        s_terms[i] = reinterpret_cast<const float*>(img + kPkSph * (i >> 3) + 4)[i & 7];
+    __syncthreads();
+    const uint32_t t = blockIdx.x * kConeThreads + threadIdx.x;
+    if (t >= gx * gy * waves) return;
+    const uint32_t wave = t % waves, wg = t / waves, tbx = wg % gx, tby = wg / gx;
+    const uint32_t x0 = tbx * (kPkW * kWgWavesX) + (wave % kWgWavesX) * kPkW;
+    const uint32_t yl0 = tby * (kPkH * (waves / kWgWavesX)) + (wave / kWgWavesX) * kPkH;
+    const ConeRowPlan rp{P.row0, P.rows, P.row_block, P.row_stride};
+    const ConeBound B = cone_tile_bound(cone_tile_rect(x0, yl0, P.width, rp), P.half_w, P.half_h,
+                                        camp[0], camp[1], dz);
+    J.dst[blockIdx.y][t] = cone_tile_mask(B, s_terms, 8, ns);
+}
+
+hipError_t launch_packet_cone_tables(const TraceParams& p, const PkConeJobs& jobs,
+                                     hipStream_t stream) {
+    if (jobs.n <= 0) return hipSuccess;
+    if (jobs.n > kPkMaxBatch || p.ns > 64 || p.width == 0 || p.rows == 0)
+        return hipErrorInvalidValue;
+    for (int j = 0; j < jobs.n; ++j) {
+        const int f = jobs.frame[j];
+        if (!jobs.dst[j] || f < -1 || f >= static_cast<int>(p.nframes) ||
+            !(f < 0 ? p.pk_image : p.fr[f].img))
+            return hipErrorInvalidValue;
+    }
+    uint32_t gx, gy, waves;
+    packet_grid(p, gx, gy, waves);
+    const uint32_t tiles = gx * gy * waves;
+    hipLaunchKernelGGL(packet_cone_table_kernel,
+                       dim3((tiles + kConeThreads - 1) / kConeThreads,
+                            static_cast<unsigned>(jobs.n)),
+                       dim3(kConeThreads), 0, stream, p, jobs, gx, gy, waves);
     return hipGetLastError();
 }
 
@@ -232,6 +284,14 @@ static int packet_features(const TraceParams& p, bool any_specular) {
     // the plane cull has its own lean variant; combined with other features the general one
     if (p.np >= 3 && feat == 0) feat = kFeatPlanes;
     return feat;
+}
+
+// The variants that read a cone table (packet_direct_kernel's kTab): single sample, up to 64
+// spheres, no feature — the marching one and its fix-up twin (C2's two).  The counting pass and
+// a launch that records tile costs take the general variant, which forms its own masks.
+bool packet_reads_cone_table(const TraceParams& p, bool any_specular) {
+    return p.aa == 1 && !p.tile_cost && p.ns >= 1 && p.ns <= 64 && p.max_rec > 0 &&
+           packet_features(p, any_specular) == 0;
 }
 
 // The fix-up variant serves the single-sample, ≤ 64-sphere, no-feature launches (C2) of frame

@@ -473,6 +473,7 @@ __device__ __forceinline__ void plane_t_core(double num, double denom, int p, bo
 // pushed nearer-first along the node's split axis by the lanes' majority direction.
 typedef const __attribute__((address_space(4))) int32_t* pk_cip;
 typedef const __attribute__((address_space(4))) double* pk_cdp;
+typedef const __attribute__((address_space(4))) unsigned long long* pk_culp;
 __device__ __forceinline__ void bvh_wave(const PacketScene& S, d3 o, d3 d, bool& found,
                                          double& best, int& kind, int& idx) {
     const d3 inv = mk(d.x != 0.0 ? 1.0 / d.x : 0.0, d.y != 0.0 ? 1.0 / d.y : 0.0,

@@ -207,6 +207,115 @@ rt_status packet_image_entry(rt_context* ctx, const rt_scene* sc, const double* 
     return RT_OK;
 }
 
+// Camera-cone tables (rt_cone_table.hpp; TraceParams.cone_tab / fr_tab).  A table belongs to a
+// camera, its ray constants and a launch shape (cone_table_key): a cached camera keeps up to
+// kMaxConeTabs of them next to its image (later shapes or focal lengths go without), each
+// formed once by a small launch on the stream that first needs it and guarded by an event for
+// the others; a batch frame without a cached image gets one in the
+// batch's ring entry, formed by one launch per batch.  A one-frame launch of a camera seen for
+// the first time (the publish-slot path) gets none: a setup launch per frame costs more than
+// the frame saves.  RTAMD_PK_CONE_TAB=0 (read per launch): no tables (A/B runs, tests).
+constexpr size_t kMaxConeTabs = 8;
+// The ring's table memory per entry (kPkBatchRing entries): a 32-frame 1080p batch takes 8.3 MB
+// (259 KB a frame), a 4K frame 1 MB; frames past the cap go without a table.
+constexpr size_t kConeRingBytes = size_t(16) << 20;
+
+bool cone_tables_wanted(const rt_scene* sc, const TraceParams& p) {
+    const char* e = std::getenv("RTAMD_PK_CONE_TAB");
+    if (e && std::atoi(e) == 0) return false;
+    return packet_reads_cone_table(p, sc->max_specular > 0.0);
+}
+
+// A table's key: everything its masks depend on besides the scene and the camera position (the
+// cache entry's) — the launch shape (tile_order's fields, the row plan's block and stride as
+// words of their own: a collision here would be wrong masks, not another permutation) and the
+// camera-ray constants dz = (cam.z + focal) − cam.z, W/2 and H/2 bit for bit: the focal length
+// is the render call's, not the scene's, so one position may be rendered at several.
+constexpr size_t kConeKeyWords = rt_scene::PkImage::ConeTab::kKeyWords;
+size_t cone_table_key(const TraceParams& p, double dz, uint32_t (&key)[kConeKeyWords]) {
+    uint32_t gx, gy, waves;
+    packet_grid(p, gx, gy, waves);
+    const uint32_t k[9] = {gx, gy, waves, p.width, p.height, p.rows, p.row0, p.row_block,
+                           p.row_stride};
+    const double c[3] = {dz, p.half_w, p.half_h};
+    std::memset(key, 0, sizeof key);
+    std::memcpy(key, k, sizeof k);
+    std::memcpy(key + 9, c, sizeof c);
+    static_assert(sizeof k + sizeof c <= sizeof(uint32_t) * kConeKeyWords, "cone table key");
+    return sizeof(unsigned long long) * gx * gy * waves;
+}
+
+// The cached camera's table for p's launch shape: *tab = the existing one (this stream ordered
+// after the launch that formed it), or a new entry whose table the caller forms (*fresh) and
+// whose event it records; null when the camera's table list is full.
+rt_status cone_table_entry(rt_context* ctx, rt_scene::PkImage& im, const TraceParams& p,
+                           double dz, rt_scene::PkImage::ConeTab** tab, bool* fresh) {
+    *tab = nullptr;
+    *fresh = false;
+    uint32_t key[kConeKeyWords];
+    const size_t bytes = cone_table_key(p, dz, key);
+    for (auto& t : im.tabs) {
+        if (std::memcmp(t.key, key, sizeof key) != 0) continue;
+        if (!t.done && t.stream != ctx->stream) {
+            const hipError_t q = hipEventQuery(t.ready);
+            if (q == hipSuccess) t.done = true;
+            else if (q == hipErrorNotReady) RT_HIP(hipStreamWaitEvent(ctx->stream, t.ready, 0));
+            else return hip_fail(q, "hipEventQuery");
+        }
+        *tab = &t;
+        return RT_OK;
+    }
+    if (im.tabs.size() >= kMaxConeTabs) return RT_OK;
+    // never reallocated: a batch holds entries of earlier frames while adding one
+    if (im.tabs.capacity() < kMaxConeTabs) im.tabs.reserve(kMaxConeTabs);
+    im.tabs.emplace_back();
+    auto& t = im.tabs.back();
+    std::memcpy(t.key, key, sizeof key);
+    t.stream = ctx->stream;
+    hipError_t e = t.buf.ensure(bytes);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&t.ready, hipEventDisableTiming);
+    if (e != hipSuccess) {
+        t.buf.release();
+        im.tabs.pop_back();
+        return hip_fail(e, "cone table entry");
+    }
+    *tab = &t;
+    *fresh = true;
+    return RT_OK;
+}
+
+void cone_table_drop(rt_scene::PkImage& im) {  // the entry cone_table_entry just added
+    auto& t = im.tabs.back();
+    t.buf.release();
+    if (t.ready) (void)hipEventDestroy(t.ready);
+    im.tabs.pop_back();
+}
+
+// One-frame launches with an image entry (p.pk_image set, formed earlier on the stream).
+rt_status cone_table_single(rt_context* ctx, const rt_scene* sc, rt_scene::PkImage& im,
+                            TraceParams& p) {
+    if (!cone_tables_wanted(sc, p)) return RT_OK;
+    rt_scene::PkImage::ConeTab* t = nullptr;
+    bool fresh = false;
+    const rt_status st = cone_table_entry(ctx, im, p, p.cam_dz, &t, &fresh);
+    if (st != RT_OK || !t) return st;
+    if (fresh) {
+        PkConeJobs jobs;
+        std::memset(&jobs, 0, sizeof jobs);
+        jobs.dst[0] = static_cast<unsigned long long*>(t->buf.ptr);
+        jobs.frame[0] = -1;
+        jobs.n = 1;
+        hipError_t e = launch_packet_cone_tables(p, jobs, ctx->stream);
+        if (e == hipSuccess) e = hipEventRecord(t->ready, ctx->stream);
+        if (e != hipSuccess) {
+            cone_table_drop(im);
+            return hip_fail(e, "cone table setup");
+        }
+    }
+    p.cone_tab = static_cast<const unsigned long long*>(t->buf.ptr);
+    return RT_OK;
+}
+
 }  // namespace
 
 // One-frame launches: the cached image; on a camera's second sighting a one-workgroup setup
@@ -219,7 +328,8 @@ rt_status packet_image(rt_context* ctx, const rt_scene* sc, TraceParams& p, int 
     if (st != RT_OK) return st;
     if (found) {
         p.pk_image = static_cast<const double*>(found->buf.ptr);
-        return tile_order(ctx, *found, p, flags, rec);
+        st = tile_order(ctx, *found, p, flags, rec);
+        return st != RT_OK ? st : cone_table_single(ctx, sc, *found, p);
     }
     if (!packet_second_sighting(sc, p.cam_pos)) {
         const rt_status st2 = packet_publish_slot(ctx, sc, p);
@@ -237,7 +347,8 @@ rt_status packet_image(rt_context* ctx, const rt_scene* sc, TraceParams& p, int 
         return hip_fail(e, "packet image setup");
     }
     p.pk_image = static_cast<const double*>(im->buf.ptr);
-    return tile_order(ctx, *im, p, flags, rec);
+    st = tile_order(ctx, *im, p, flags, rec);
+    return st != RT_OK ? st : cone_table_single(ctx, sc, *im, p);
 }
 
 // A frame batch's image sources (p.fr[f].img for every frame, before the batch launch): a
@@ -345,8 +456,75 @@ rt_status packet_batch_images(rt_context* ctx, const rt_scene* sc, const rt_came
         if (kind[f] == kPromote) e = hipEventRecord(ent[f]->ready, ctx->stream);
     if (e != hipSuccess) return hip_fail(e, "packet batch images");  // the rollback drops them
     rollback.armed = false;  // every promoted entry now has its image and its recorded event
-    if (kind[0] == kCached) return tile_order(ctx, *ent[0], p, flags, rec, !same_cam);
-    return scene_tile_order(ctx, sc, p, flags, rec);
+    const rt_status ost = kind[0] == kCached ? tile_order(ctx, *ent[0], p, flags, rec, !same_cam)
+                                             : scene_tile_order(ctx, sc, p, flags, rec);
+    if (ost != RT_OK || !cone_tables_wanted(sc, p)) return ost;
+    // The frames' cone tables, after their images on the stream: a cached or promoted camera's
+    // from (or into) its entry, a ring frame's into the ring entry's table buffer up to its
+    // cap, a duplicate's shared; every table that does not exist yet by ONE launch.
+    uint32_t key[kConeKeyWords];
+    const size_t tab_bytes = (cone_table_key(p, 0.0, key) + 255) & ~size_t(255);  // (the size only)
+    char* ring_tab = nullptr;
+    size_t ring_room = 0;
+    if (any_ring) {
+        size_t n_ring = 0;
+        for (int f = 0; f < nframes; ++f) n_ring += kind[f] == kRing;
+        const size_t fit = std::min(n_ring, kConeRingBytes / tab_bytes);
+        auto& buf = sc->pk_batch_tab[*batch_ring];
+        if (fit > 0 && buf.bytes < fit * tab_bytes) {
+            // the stream already waits for the batch that last read this ring entry; freeing
+            // its table buffer needs that batch complete on the host's side too
+            if (sc->pk_batch_used[*batch_ring])
+                RT_HIP(hipEventSynchronize(sc->pk_batch_done[*batch_ring]));
+            RT_HIP(buf.ensure(fit * tab_bytes));
+        }
+        ring_tab = static_cast<char*>(buf.ptr);
+        ring_room = fit;
+    }
+    PkConeJobs cj;
+    std::memset(&cj, 0, sizeof cj);
+    rt_scene::PkImage* made[kPkMaxBatch];  // entries that got a fresh table (newest last)
+    rt_scene::PkImage::ConeTab* made_tab[kPkMaxBatch];
+    int n_made = 0;
+    rt_status st = RT_OK;
+    for (int f = 0; f < nframes && st == RT_OK; ++f) {
+        p.fr_tab[f] = nullptr;
+        unsigned long long* dst = nullptr;
+        if (kind[f] == kDup) {
+            p.fr_tab[f] = p.fr_tab[dup_of[f]];
+            continue;
+        }
+        if (kind[f] == kRing) {
+            if (ring_room == 0) continue;  // past the cap: the wave forms its own mask
+            --ring_room;
+            dst = reinterpret_cast<unsigned long long*>(ring_tab);
+            ring_tab += tab_bytes;
+        } else {
+            rt_scene::PkImage::ConeTab* t = nullptr;
+            bool fresh = false;
+            st = cone_table_entry(ctx, *ent[f], p, p.fr_dz[f][0], &t, &fresh);
+            if (st != RT_OK || !t) continue;
+            p.fr_tab[f] = static_cast<const unsigned long long*>(t->buf.ptr);
+            if (!fresh) continue;
+            made[n_made] = ent[f];
+            made_tab[n_made] = t;
+            ++n_made;
+            dst = static_cast<unsigned long long*>(t->buf.ptr);
+        }
+        p.fr_tab[f] = dst;
+        cj.dst[cj.n] = dst;
+        cj.frame[cj.n] = f;
+        ++cj.n;
+    }
+    if (st == RT_OK) {
+        hipError_t ce = launch_packet_cone_tables(p, cj, ctx->stream);
+        for (int i = 0; i < n_made && ce == hipSuccess; ++i)
+            ce = hipEventRecord(made_tab[i]->ready, ctx->stream);
+        if (ce != hipSuccess) st = hip_fail(ce, "packet batch cone tables");
+    }
+    if (st != RT_OK)  // a table never formed must not be found by a later render
+        for (int i = n_made - 1; i >= 0; --i) cone_table_drop(*made[i]);
+    return st;
 }
 
 }  // namespace rtamd

@@ -369,6 +369,11 @@ __global__ __launch_bounds__(64 * kWgWavesX * WGY, pk_waves(MAXC, FEAT, COUNT, M
     // (the plane-only copy of pk_occlusion alone put 8 B more per lane into scratch), and the
     // variants of more than 64 spheres lost time with such branches before.
     constexpr bool kLean = MAXC == 1 && (FEAT & kFeatArea) == 0;
+    // The single-sample variants of that kind without another feature (C2's two) read their
+    // camera-cone mask from the frame's table when it has one (rt_cone_table.hpp): a
+    // wave-uniform run-time test of the pointer, so the variants keep their names.
+    constexpr bool kTab = kLean && !MULTI && !COUNT && (FEAT == 0 || FEAT == kFeatFix);
+    const unsigned long long* cone_tab = kTab ? P.cone_tab : nullptr;
     double cam_dz = P.cam_dz, cam_dz2 = P.cam_dz2;
     if (P.nframes) {
         const PkFrame& F = P.fr[blockIdx.z];
@@ -379,6 +384,7 @@ __global__ __launch_bounds__(64 * kWgWavesX * WGY, pk_waves(MAXC, FEAT, COUNT, M
         pk_pub = F.pub;
         pk_epoch = F.epoch;
         frame_off = static_cast<uint64_t>(blockIdx.z) * P.frame_px;
+        if constexpr (kTab) cone_tab = P.fr_tab[blockIdx.z];
     }
     const d3 cam = mk(camp[0], camp[1], camp[2]);
     constexpr int kThreads = 64 * kWgWavesX * WGY;
@@ -507,15 +513,27 @@ __global__ __launch_bounds__(64 * kWgWavesX * WGY, pk_waves(MAXC, FEAT, COUNT, M
             col = sky(d);  // TraceRay at depth >= maxRecursion (Scene.h:132-134)
         } else {
             if (COUNT && valid) cnt.trace++;
-            // camera cone: axis = the tile's centre-lane direction (exact copy), half-angle
-            // from the wave minimum of the per-lane cosines in FP32 (|cos| ≤ 1 + 2ε, so the
-            // conversion is off by ≤ 6e-8, inside the 1e-7 taken off)
-            const d3 axis = lane_d3(d, (kPkH / 2) * kPkW + kPkW / 2);
-            const double cos_min =
-                static_cast<double>(wave_red<0>(static_cast<float>(dot(d, axis)))) - 1e-7;
-            const bool ok = isfinite(cos_min) && cos_min > 0.0;  // cones narrower than 90°
-            const Masks<MAXC> M = ok ? cull_cone<MAXC>(S, axis, cos_min)
-                                     : all_candidates<MAXC>(ns);
+            // (a lambda: the variants without a table compile to the code they had)
+            const Masks<MAXC> M = [&] {
+                if constexpr (kTab) {
+                    if (cone_tab) {  // uniform: this tile's mask, one scalar load
+                        Masks<MAXC> T;
+                        const uint32_t w =
+                            __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(wave));
+                        T.m[0] = ((pk_culp)cone_tab)[(tby * gridDim.x + tbx) * (kWgWavesX * WGY) + w];
+                        T.pm = ~0ull;
+                        return T;
+                    }
+                }
+                // camera cone: axis = the tile's centre-lane direction (exact copy), half-angle
+                // from the wave minimum of the per-lane cosines in FP32 (|cos| ≤ 1 + 2ε, so the
+                // conversion is off by ≤ 6e-8, inside the 1e-7 taken off)
+                const d3 axis = lane_d3(d, (kPkH / 2) * kPkW + kPkW / 2);
+                const double cos_min =
+                    static_cast<double>(wave_red<0>(static_cast<float>(dot(d, axis)))) - 1e-7;
+                const bool ok = isfinite(cos_min) && cos_min > 0.0;  // cones narrower than 90°
+                return ok ? cull_cone<MAXC>(S, axis, cos_min) : all_candidates<MAXC>(ns);
+            }();
             PkHit h;
             h.t = 0.0;
             h.prim = 0;
