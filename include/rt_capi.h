@@ -474,6 +474,12 @@ rt_status rt_debug_tile_order(rt_context* ctx, const rt_scene* scene, const rt_c
  * turns the tables off. */
 rt_status rt_debug_cone_table(rt_context* ctx, uint64_t* with_table, uint64_t* without_table);
 
+/* Test hook (read-only): the same count for the shadow-cull masks — frames enqueued with a
+ * per-tile, per-light shadow table (*with_table; a tile without a word still forms its own mask)
+ * and without one (*without_table).  RTAMD_PK_SHADOW_TAB=0 in the environment, read per launch,
+ * turns the shadow tables off, independently of RTAMD_PK_CONE_TAB. */
+rt_status rt_debug_shadow_table(rt_context* ctx, uint64_t* with_table, uint64_t* without_table);
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif

@@ -344,6 +344,9 @@ rt_status enqueue_frames(rt_context* ctx, const rt_scene* sc, const rt_camera* c
         for (int f = 0; f < nframes; ++f)
             ++((nframes > 1 ? p.fr_tab[f] : p.cone_tab) ? ctx->cone_tab_frames
                                                          : ctx->cone_notab_frames);
+        for (int f = 0; f < nframes; ++f)  // rt_debug_shadow_table
+            ++((nframes > 1 ? p.fr_stab[f] : p.shadow_tab) ? ctx->shadow_tab_frames
+                                                            : ctx->shadow_notab_frames);
     }
     // the fix-up variant of the packet kernel (undecided shadow rays re-rendered per pixel after
     // the launch) uses the context's fix-up list: ordered across streams like the counters
@@ -1128,6 +1131,14 @@ rt_status rt_debug_cone_table(rt_context* ctx, uint64_t* with_table, uint64_t* w
         return fail(RT_ERR_INVALID_ARG, "NULL argument to rt_debug_cone_table");
     *with_table = ctx->cone_tab_frames;
     *without_table = ctx->cone_notab_frames;
+    return RT_OK;
+}
+
+rt_status rt_debug_shadow_table(rt_context* ctx, uint64_t* with_table, uint64_t* without_table) {
+    if (!ctx || !with_table || !without_table)
+        return fail(RT_ERR_INVALID_ARG, "NULL argument to rt_debug_shadow_table");
+    *with_table = ctx->shadow_tab_frames;
+    *without_table = ctx->shadow_notab_frames;
     return RT_OK;
 }
 

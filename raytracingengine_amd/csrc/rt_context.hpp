@@ -82,6 +82,8 @@ struct rt_context {
     uint64_t launches = 0;
     // packet-kernel frames enqueued with / without a camera-cone table (rt_debug_cone_table)
     uint64_t cone_tab_frames = 0, cone_notab_frames = 0;
+    // ... and with / without a shadow-cull table (rt_debug_shadow_table)
+    uint64_t shadow_tab_frames = 0, shadow_notab_frames = 0;
     // rt_render_multi: RCCL communicators over the devices of the last context list this
     // context led (rt_multi.cpp); destroyed with the context
     std::vector<rt_context*> group_ctxs;
@@ -137,9 +139,10 @@ struct rt_scene {
         // kMaxConeTabs, later shapes or focal lengths go without): written once by
         // packet_cone_table_kernel on the stream of the render that created it, never rewritten;
         // renders on other streams wait for `ready` until it has completed.  Dropped with the
-        // image entry.
+        // image entry.  The buffer also holds the shadow-cull words formed from the cone masks
+        // (rt_shadow_table.hpp), after them: nl per tile when the scene gets any.
         struct ConeTab {
-            static constexpr size_t kKeyWords = 16;
+            static constexpr size_t kKeyWords = 20;
             uint32_t key[kKeyWords] = {};
             rtamd::DeviceBuffer buf;
             hipEvent_t ready = nullptr;

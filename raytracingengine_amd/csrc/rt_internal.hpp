@@ -136,6 +136,12 @@ struct TraceParams {
     // the wave forms its own.  fr_tab[f]: frame f's of a batch (after fr_dz, as fr_dz after fr[])
     const unsigned long long* cone_tab;
     const unsigned long long* fr_tab[kPkMaxBatch];
+    // the same variants: the shadow-cull candidate masks of every wave tile (rt_shadow_table.hpp),
+    // nl 64-bit words per tile at ((tby · gx + tbx) · waves + wave) · nl + light, formed by the
+    // same launch into the same buffer after the cone table's words; a word of all ones or a null
+    // pointer: the wave forms its own mask (origin_ball + cull_capsule).  fr_stab[f]: frame f's
+    const unsigned long long* shadow_tab;
+    const unsigned long long* fr_stab[kPkMaxBatch];
 };
 // the runtime passes at most 4 KiB of kernel arguments (packet_image_batch_kernel and
 // packet_cone_table_kernel take a job list of kPkMaxBatch pointers and ints next to it)
@@ -207,11 +213,16 @@ struct PkConeJobs {
     unsigned long long* dst[kPkMaxBatch];
     int32_t frame[kPkMaxBatch];
     int32_t n;
+    // > 0: the shadow-cull words too (rt_shadow_table.hpp), shadow_nl per tile, written after
+    // the job's cone words: dst[j] + tiles
+    int32_t shadow_nl;
 };
 hipError_t launch_packet_cone_tables(const TraceParams& p, const PkConeJobs& jobs,
                                      hipStream_t stream);
 // Whether p's launch is served by a variant that reads a cone table.
 bool packet_reads_cone_table(const TraceParams& p, bool any_specular);
+// Lights per tile of the shadow table such a launch's scene gets (0: none, rt_shadow_table.hpp).
+int packet_shadow_table_lights(const TraceParams& p);
 // The packet kernel's launch shape for p (grid of workgroups, waves per workgroup), and the
 // costliest-first tile order built from the wave durations a launch of that shape recorded.
 void packet_grid(const TraceParams& p, uint32_t& gx, uint32_t& gy, uint32_t& waves);

@@ -5,6 +5,7 @@
 // queued pixels and the costliest-first tile order.
 #include "rt_cone_table.hpp"
 #include "rt_packet_kernel.hpp"
+#include "rt_shadow_table.hpp"
 
 #pragma clang fp contract(off)
 
@@ -50,12 +51,19 @@ hipError_t launch_packet_image_batch(const TraceParams& p, const PkImageJobs& jo
 // has no cached table.  The per-sphere terms are the packet image's (cone_terms), formed
 // earlier on the stream.  Tables are indexed by tile — (tby · gx + tbx) · waves + wave — not by
 // dispatch position: the tile order permutes dispatch, not tiles.
+// With J.shadow_nl > 0 the same lane goes on to the tile's shadow-cull words
+// (rt_shadow_table.hpp), which depend on the cone mask it just formed: nl words per tile after
+// the job's cone words, so a batch of new cameras pays no launch of its own for them.
+// The kernel waits more than it issues (dependent FP64 chains, one lane per tile), so it is
+// built for 5 waves per SIMD (96 VGPRs, 88 B of scratch; by itself it compiles to 3): the
+// measured times are in DESIGN §4 and profiles/shadow_table_pmc.txt.
 constexpr int kConeThreads = 256;
-__global__ __launch_bounds__(kConeThreads) void packet_cone_table_kernel(TraceParams P,
+__global__ __launch_bounds__(kConeThreads, 5) void packet_cone_table_kernel(TraceParams P,
                                                                          PkConeJobs J, uint32_t gx,
                                                                          uint32_t gy,
                                                                          uint32_t waves) {
     __shared__ float s_terms[64 * 8];
+    __shared__ double s_ctr[64 * 3];  // the sphere centres, for the shadow words
     const int f = J.frame[blockIdx.y];
     const double* camp = f < 0 ? P.cam_pos : P.fr[f].cam;
     const double* img = f < 0 ? P.pk_image : P.fr[f].img;
@@ -63,6 +71,9 @@ __global__ __launch_bounds__(kConeThreads) void packet_cone_table_kernel(TracePa
     const int ns = P.ns < 64 ? P.ns : 64;  // (the launcher checked P.ns <= 64)
     for (int i = threadIdx.x; i < 8 * ns; i += kConeThreads)
         s_terms[i] = reinterpret_cast<const float*>(img + kPkSph * (i >> 3) + 4)[i & 7];
+    if (J.shadow_nl > 0)
+        for (int i = threadIdx.x; i < 3 * ns; i += kConeThreads)
+            s_ctr[i] = img[kPkSph * (i / 3) + i % 3];
     __syncthreads();
     const uint32_t t = blockIdx.x * kConeThreads + threadIdx.x;
     if (t >= gx * gy * waves) return;
@@ -70,15 +81,31 @@ __global__ __launch_bounds__(kConeThreads) void packet_cone_table_kernel(TracePa
     const uint32_t x0 = tbx * (kPkW * kWgWavesX) + (wave % kWgWavesX) * kPkW;
     const uint32_t yl0 = tby * (kPkH * (waves / kWgWavesX)) + (wave / kWgWavesX) * kPkH;
     const ConeRowPlan rp{P.row0, P.rows, P.row_block, P.row_stride};
-    const ConeBound B = cone_tile_bound(cone_tile_rect(x0, yl0, P.width, rp), P.half_w, P.half_h,
-                                        camp[0], camp[1], dz);
-    J.dst[blockIdx.y][t] = cone_tile_mask(B, s_terms, 8, ns);
+    const ConeRect q = cone_tile_rect(x0, yl0, P.width, rp);
+    const ConeBound B = cone_tile_bound(q, P.half_w, P.half_h, camp[0], camp[1], dz);
+    const uint64_t cone = cone_tile_mask(B, s_terms, 8, ns);
+    J.dst[blockIdx.y][t] = cone;
+    if (J.shadow_nl <= 0) return;
+    // (the launcher checked shadow_nl == P.nl <= kShadowTabLights, P.np <= 2 and ns <= 63: no
+    // chunk bounds, so the image's planes follow its ns sphere records)
+    unsigned long long* sw = J.dst[blockIdx.y] + static_cast<size_t>(gx) * gy * waves +
+                             static_cast<size_t>(t) * J.shadow_nl;
+    // (two planes at most: scenes of three or more take the plane-culling variant, no table)
+    ShadowBound<2> SB;
+    SB.n = 0;
+    SB.ok = false;
+    if (cone == 0)
+        SB = shadow_tile_bound<2>(q, P.half_w, P.half_h, camp, dz, img + kPkSph * ns, P.np, P.bias);
+    for (int l = 0; l < J.shadow_nl; ++l)
+        sw[l] = shadow_tile_word(SB, P.lt + kLtStride * l, P.bias, s_ctr, 3, s_terms + 7, 8, ns);
 }
 
 hipError_t launch_packet_cone_tables(const TraceParams& p, const PkConeJobs& jobs,
                                      hipStream_t stream) {
     if (jobs.n <= 0) return hipSuccess;
     if (jobs.n > kPkMaxBatch || p.ns > 64 || p.width == 0 || p.rows == 0)
+        return hipErrorInvalidValue;
+    if (jobs.shadow_nl != 0 && jobs.shadow_nl != packet_shadow_table_lights(p))
         return hipErrorInvalidValue;
     for (int j = 0; j < jobs.n; ++j) {
         const int f = jobs.frame[j];
@@ -292,6 +319,11 @@ static int packet_features(const TraceParams& p, bool any_specular) {
 bool packet_reads_cone_table(const TraceParams& p, bool any_specular) {
     return p.aa == 1 && !p.tile_cost && p.ns >= 1 && p.ns <= 64 && p.max_rec > 0 &&
            packet_features(p, any_specular) == 0;
+}
+
+int packet_shadow_table_lights(const TraceParams& p) {
+    // (np <= 2 is what the variants that read a table render: packet_features)
+    return p.np <= 2 ? shadow_table_lights(p.ns, p.np, p.nl, p.al_samples > 0) : 0;
 }
 
 // The fix-up variant serves the single-sample, ≤ 64-sphere, no-feature launches (C2) of frame

@@ -215,24 +215,50 @@ rt_status packet_image_entry(rt_context* ctx, const rt_scene* sc, const double* 
 // batch's ring entry, formed by one launch per batch.  A one-frame launch of a camera seen for
 // the first time (the publish-slot path) gets none: a setup launch per frame costs more than
 // the frame saves.  RTAMD_PK_CONE_TAB=0 (read per launch): no tables (A/B runs, tests).
+// The shadow-cull words (rt_shadow_table.hpp; TraceParams.shadow_tab / fr_stab) live and die
+// with the cone table they are formed from: the same launch writes them into the same buffer
+// after the cone words (nl per tile, for the scenes packet_shadow_table_lights accepts), under
+// the same key, cache entry, ring entry and caps.  Unlike the cone masks they depend on the
+// render call's bias (it enters every ball's radius), so the key of a table that holds them
+// carries the bias bit for bit and how many words per tile it holds: one position rendered at
+// two biases has two tables, as at two focal lengths.  RTAMD_PK_SHADOW_TAB=0 (read per launch):
+// no shadow words are formed or handed to the kernel (the table kernel does the cone table's
+// work only, and a cached table formed that way is one of its own, whatever the bias).  With
+// RTAMD_PK_CONE_TAB=0 alone the cone words are still formed — the shadow words depend on them —
+// but only the shadow pointers reach the kernel.
 constexpr size_t kMaxConeTabs = 8;
-// The ring's table memory per entry (kPkBatchRing entries): a 32-frame 1080p batch takes 8.3 MB
-// (259 KB a frame), a 4K frame 1 MB; frames past the cap go without a table.
+// The ring's table memory per entry (kPkBatchRing entries), counted in cone words: a 32-frame
+// 1080p batch takes 8.3 MB (259 KB a frame), a 4K frame 1 MB; frames past the cap go without a
+// table.  The shadow words come on top (nl times as much, 16.6 MB for a 32-frame C2 batch).
 constexpr size_t kConeRingBytes = size_t(16) << 20;
 
-bool cone_tables_wanted(const rt_scene* sc, const TraceParams& p) {
+struct TabsWanted {
+    bool cone, shadow;
+    int shadow_nl;  // shadow words per tile this launch's tables hold (0: cone masks only)
+    bool any() const { return cone || shadow; }
+};
+TabsWanted tables_wanted(const rt_scene* sc, const TraceParams& p) {
+    TabsWanted w{false, false, 0};
+    if (!packet_reads_cone_table(p, sc->max_specular > 0.0)) return w;
     const char* e = std::getenv("RTAMD_PK_CONE_TAB");
-    if (e && std::atoi(e) == 0) return false;
-    return packet_reads_cone_table(p, sc->max_specular > 0.0);
+    w.cone = !(e && std::atoi(e) == 0);
+    e = std::getenv("RTAMD_PK_SHADOW_TAB");
+    w.shadow = packet_shadow_table_lights(p) > 0 && !(e && std::atoi(e) == 0);
+    w.shadow_nl = w.shadow ? packet_shadow_table_lights(p) : 0;
+    return w;
 }
 
 // A table's key: everything its masks depend on besides the scene and the camera position (the
 // cache entry's) — the launch shape (tile_order's fields, the row plan's block and stride as
 // words of their own: a collision here would be wrong masks, not another permutation) and the
 // camera-ray constants dz = (cam.z + focal) − cam.z, W/2 and H/2 bit for bit: the focal length
-// is the render call's, not the scene's, so one position may be rendered at several.
+// is the render call's, not the scene's, so one position may be rendered at several.  A table
+// with shadow words (shadow_nl > 0 per tile) also carries that count and the render call's
+// bias bit for bit: the words formed at one bias are wrong masks at a larger one.  Returns the
+// table's size.
 constexpr size_t kConeKeyWords = rt_scene::PkImage::ConeTab::kKeyWords;
-size_t cone_table_key(const TraceParams& p, double dz, uint32_t (&key)[kConeKeyWords]) {
+size_t cone_table_key(const TraceParams& p, double dz, int shadow_nl,
+                      uint32_t (&key)[kConeKeyWords], size_t* tiles = nullptr) {
     uint32_t gx, gy, waves;
     packet_grid(p, gx, gy, waves);
     const uint32_t k[9] = {gx, gy, waves, p.width, p.height, p.rows, p.row0, p.row_block,
@@ -241,19 +267,28 @@ size_t cone_table_key(const TraceParams& p, double dz, uint32_t (&key)[kConeKeyW
     std::memset(key, 0, sizeof key);
     std::memcpy(key, k, sizeof k);
     std::memcpy(key + 9, c, sizeof c);
-    static_assert(sizeof k + sizeof c <= sizeof(uint32_t) * kConeKeyWords, "cone table key");
-    return sizeof(unsigned long long) * gx * gy * waves;
+    static_assert(sizeof k + sizeof c + sizeof(uint32_t) + sizeof(double) <=
+                      sizeof(uint32_t) * kConeKeyWords, "cone table key");
+    // (lights and planes are the scene's, like the spheres: not part of the key)
+    if (shadow_nl > 0) {
+        key[15] = static_cast<uint32_t>(shadow_nl);
+        std::memcpy(key + 16, &p.bias, sizeof p.bias);
+    }
+    const size_t n = static_cast<size_t>(gx) * gy * waves;
+    if (tiles) *tiles = n;
+    return sizeof(unsigned long long) * n * (1 + static_cast<size_t>(shadow_nl > 0 ? shadow_nl : 0));
 }
 
 // The cached camera's table for p's launch shape: *tab = the existing one (this stream ordered
 // after the launch that formed it), or a new entry whose table the caller forms (*fresh) and
 // whose event it records; null when the camera's table list is full.
 rt_status cone_table_entry(rt_context* ctx, rt_scene::PkImage& im, const TraceParams& p,
-                           double dz, rt_scene::PkImage::ConeTab** tab, bool* fresh) {
+                           double dz, int shadow_nl, rt_scene::PkImage::ConeTab** tab,
+                           bool* fresh) {
     *tab = nullptr;
     *fresh = false;
     uint32_t key[kConeKeyWords];
-    const size_t bytes = cone_table_key(p, dz, key);
+    const size_t bytes = cone_table_key(p, dz, shadow_nl, key);
     for (auto& t : im.tabs) {
         if (std::memcmp(t.key, key, sizeof key) != 0) continue;
         if (!t.done && t.stream != ctx->stream) {
@@ -294,10 +329,11 @@ void cone_table_drop(rt_scene::PkImage& im) {  // the entry cone_table_entry jus
 // One-frame launches with an image entry (p.pk_image set, formed earlier on the stream).
 rt_status cone_table_single(rt_context* ctx, const rt_scene* sc, rt_scene::PkImage& im,
                             TraceParams& p) {
-    if (!cone_tables_wanted(sc, p)) return RT_OK;
+    const TabsWanted want = tables_wanted(sc, p);
+    if (!want.any()) return RT_OK;
     rt_scene::PkImage::ConeTab* t = nullptr;
     bool fresh = false;
-    const rt_status st = cone_table_entry(ctx, im, p, p.cam_dz, &t, &fresh);
+    const rt_status st = cone_table_entry(ctx, im, p, p.cam_dz, want.shadow_nl, &t, &fresh);
     if (st != RT_OK || !t) return st;
     if (fresh) {
         PkConeJobs jobs;
@@ -305,6 +341,7 @@ rt_status cone_table_single(rt_context* ctx, const rt_scene* sc, rt_scene::PkIma
         jobs.dst[0] = static_cast<unsigned long long*>(t->buf.ptr);
         jobs.frame[0] = -1;
         jobs.n = 1;
+        jobs.shadow_nl = want.shadow_nl;
         hipError_t e = launch_packet_cone_tables(p, jobs, ctx->stream);
         if (e == hipSuccess) e = hipEventRecord(t->ready, ctx->stream);
         if (e != hipSuccess) {
@@ -312,7 +349,12 @@ rt_status cone_table_single(rt_context* ctx, const rt_scene* sc, rt_scene::PkIma
             return hip_fail(e, "cone table setup");
         }
     }
-    p.cone_tab = static_cast<const unsigned long long*>(t->buf.ptr);
+    uint32_t key[kConeKeyWords];
+    size_t tiles = 0;
+    (void)cone_table_key(p, p.cam_dz, want.shadow_nl, key, &tiles);
+    const unsigned long long* words = static_cast<const unsigned long long*>(t->buf.ptr);
+    if (want.cone) p.cone_tab = words;
+    if (want.shadow) p.shadow_tab = words + tiles;
     return RT_OK;
 }
 
@@ -458,18 +500,22 @@ rt_status packet_batch_images(rt_context* ctx, const rt_scene* sc, const rt_came
     rollback.armed = false;  // every promoted entry now has its image and its recorded event
     const rt_status ost = kind[0] == kCached ? tile_order(ctx, *ent[0], p, flags, rec, !same_cam)
                                              : scene_tile_order(ctx, sc, p, flags, rec);
-    if (ost != RT_OK || !cone_tables_wanted(sc, p)) return ost;
+    const TabsWanted want = tables_wanted(sc, p);
+    if (ost != RT_OK || !want.any()) return ost;
     // The frames' cone tables, after their images on the stream: a cached or promoted camera's
     // from (or into) its entry, a ring frame's into the ring entry's table buffer up to its
     // cap, a duplicate's shared; every table that does not exist yet by ONE launch.
     uint32_t key[kConeKeyWords];
-    const size_t tab_bytes = (cone_table_key(p, 0.0, key) + 255) & ~size_t(255);  // (the size only)
+    size_t tiles = 0;
+    const size_t tab_bytes =  // (the sizes only)
+        (cone_table_key(p, 0.0, want.shadow_nl, key, &tiles) + 255) & ~size_t(255);
+    const size_t cone_bytes = (sizeof(unsigned long long) * tiles + 255) & ~size_t(255);
     char* ring_tab = nullptr;
     size_t ring_room = 0;
     if (any_ring) {
         size_t n_ring = 0;
         for (int f = 0; f < nframes; ++f) n_ring += kind[f] == kRing;
-        const size_t fit = std::min(n_ring, kConeRingBytes / tab_bytes);
+        const size_t fit = std::min(n_ring, kConeRingBytes / cone_bytes);
         auto& buf = sc->pk_batch_tab[*batch_ring];
         if (fit > 0 && buf.bytes < fit * tab_bytes) {
             // the stream already waits for the batch that last read this ring entry; freeing
@@ -483,15 +529,23 @@ rt_status packet_batch_images(rt_context* ctx, const rt_scene* sc, const rt_came
     }
     PkConeJobs cj;
     std::memset(&cj, 0, sizeof cj);
+    cj.shadow_nl = want.shadow_nl;
+    // the kernel's pointers of a frame whose table is (or will be) at `words`
+    auto hand = [&](int f, const unsigned long long* words) {
+        p.fr_tab[f] = want.cone ? words : nullptr;
+        p.fr_stab[f] = want.shadow ? words + tiles : nullptr;
+    };
     rt_scene::PkImage* made[kPkMaxBatch];  // entries that got a fresh table (newest last)
     rt_scene::PkImage::ConeTab* made_tab[kPkMaxBatch];
     int n_made = 0;
     rt_status st = RT_OK;
     for (int f = 0; f < nframes && st == RT_OK; ++f) {
         p.fr_tab[f] = nullptr;
+        p.fr_stab[f] = nullptr;
         unsigned long long* dst = nullptr;
         if (kind[f] == kDup) {
             p.fr_tab[f] = p.fr_tab[dup_of[f]];
+            p.fr_stab[f] = p.fr_stab[dup_of[f]];
             continue;
         }
         if (kind[f] == kRing) {
@@ -502,16 +556,16 @@ rt_status packet_batch_images(rt_context* ctx, const rt_scene* sc, const rt_came
         } else {
             rt_scene::PkImage::ConeTab* t = nullptr;
             bool fresh = false;
-            st = cone_table_entry(ctx, *ent[f], p, p.fr_dz[f][0], &t, &fresh);
+            st = cone_table_entry(ctx, *ent[f], p, p.fr_dz[f][0], want.shadow_nl, &t, &fresh);
             if (st != RT_OK || !t) continue;
-            p.fr_tab[f] = static_cast<const unsigned long long*>(t->buf.ptr);
+            hand(f, static_cast<const unsigned long long*>(t->buf.ptr));
             if (!fresh) continue;
             made[n_made] = ent[f];
             made_tab[n_made] = t;
             ++n_made;
             dst = static_cast<unsigned long long*>(t->buf.ptr);
         }
-        p.fr_tab[f] = dst;
+        hand(f, dst);
         cj.dst[cj.n] = dst;
         cj.frame[cj.n] = f;
         ++cj.n;

@@ -175,12 +175,18 @@ __device__ __forceinline__ Masks<MAXC> shadow_masks(const PacketScene& S, bool c
 
 // One light of directLightning (Scene.h:86-124) for the whole wave: every lane calls it
 // (uniform control flow for the packet reductions); `active` lanes shade.
-template <int MAXC, int FEAT, bool COUNT>
+// TAB (packet_direct_kernel's kTab variants): `stab`, when set, points at this tile's and this
+// light's word of the frame's shadow table (rt_shadow_table.hpp) — a superset of the spheres any
+// shadow ray of the tile can meet, formed from the scene, the camera and the tile alone.  Masks
+// only shrink by provable misses, so a superset mask leaves every lane's classification as it
+// is.  The other instantiations compile to the code they had.
+template <int MAXC, int FEAT, bool COUNT, bool TAB = false>
 __device__ __forceinline__ void pk_light(const PacketScene& S, bool active, d3 P, d3 n, d3 view,
                                          const PkHit& h, d3 lpos, d3 E, d3 lcenter, double lrad,
                                          double bias, int nchunks, d3& diff, d3& spec,
                                          Counts& cnt, const Masks<MAXC>* pre = nullptr,
-                                         bool* fix = nullptr) {
+                                         bool* fix = nullptr,
+                                         const unsigned long long* stab = nullptr) {
     double dist = 0.0, inv_d2 = 0.0;
     d3 L = mk(0.0, 0.0, 0.0);
     if (active) light_dir(lpos - P, dist, L, inv_d2);  // skipped by waves with no hit lane
@@ -195,8 +201,21 @@ __device__ __forceinline__ void pk_light(const PacketScene& S, bool active, d3 P
     // lanes that cast no ray only take part in them
     int occ = 0;
     Masks<MAXC> M;
+    bool tabled = false;
+    if constexpr (TAB) {
+        if (stab) {  // uniform: one scalar load; all ones: the tile has no word
+            const unsigned long long w = *(pk_culp)stab;
+            if (w != ~0ull) {
+                M.m[0] = w;
+                M.pm = ~0ull;
+                tabled = true;
+            }
+        }
+    }
     if (pre) {
         M = *pre;
+        if (need) occ = pk_occlusion<MAXC, FEAT>(S, M, nchunks, so, L, dist - bias, bias);
+    } else if (TAB && tabled) {
         if (need) occ = pk_occlusion<MAXC, FEAT>(S, M, nchunks, so, L, dist - bias, bias);
     } else {
         const OriginBall B = origin_ball(need, so);
@@ -374,6 +393,7 @@ __global__ __launch_bounds__(64 * kWgWavesX * WGY, pk_waves(MAXC, FEAT, COUNT, M
     // wave-uniform run-time test of the pointer, so the variants keep their names.
     constexpr bool kTab = kLean && !MULTI && !COUNT && (FEAT == 0 || FEAT == kFeatFix);
     const unsigned long long* cone_tab = kTab ? P.cone_tab : nullptr;
+    const unsigned long long* shadow_tab = kTab ? P.shadow_tab : nullptr;
     double cam_dz = P.cam_dz, cam_dz2 = P.cam_dz2;
     if (P.nframes) {
         const PkFrame& F = P.fr[blockIdx.z];
@@ -384,7 +404,10 @@ __global__ __launch_bounds__(64 * kWgWavesX * WGY, pk_waves(MAXC, FEAT, COUNT, M
         pk_pub = F.pub;
         pk_epoch = F.epoch;
         frame_off = static_cast<uint64_t>(blockIdx.z) * P.frame_px;
-        if constexpr (kTab) cone_tab = P.fr_tab[blockIdx.z];
+        if constexpr (kTab) {
+            cone_tab = P.fr_tab[blockIdx.z];
+            shadow_tab = P.fr_stab[blockIdx.z];
+        }
     }
     const d3 cam = mk(camp[0], camp[1], camp[2]);
     constexpr int kThreads = 64 * kWgWavesX * WGY;
@@ -581,11 +604,29 @@ __global__ __launch_bounds__(64 * kWgWavesX * WGY, pk_waves(MAXC, FEAT, COUNT, M
             // them in LDS (6 doubles per lane) in the ≤ 64-sphere variants cut the spills (C5
             // 116 → 44 B/lane, C2 44 → 12) but the reloads cost more: C5 414 → 434 µs, C2
             // 38.3 → 38.9 µs per frame (profiles/r04_ab_park.txt, r04_park_traffic.json).
-            for (int l = 0; l < nl; ++l) {
-                d3 L, E;
-                pk_light_record<MAXC>(S, P, l, L, E);
-                pk_light<MAXC, FEAT, COUNT>(S, hit, hp, n, view, h, L, E, L, 0.0, bias, nchunks,
-                                            diff, spec, cnt, nullptr, &fix);
+            if constexpr (kTab) {
+                // this tile's shadow-table words, one per light (a uniform address)
+                const unsigned long long* stab = nullptr;
+                if (shadow_tab) {
+                    const uint32_t w =
+                        __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(wave));
+                    stab = shadow_tab + static_cast<size_t>(
+                               (tby * gridDim.x + tbx) * (kWgWavesX * WGY) + w) * nl;
+                }
+                for (int l = 0; l < nl; ++l) {
+                    d3 L, E;
+                    pk_light_record<MAXC>(S, P, l, L, E);
+                    pk_light<MAXC, FEAT, COUNT, true>(S, hit, hp, n, view, h, L, E, L, 0.0, bias,
+                                                      nchunks, diff, spec, cnt, nullptr, &fix,
+                                                      stab ? stab + l : nullptr);
+                }
+            } else {
+                for (int l = 0; l < nl; ++l) {
+                    d3 L, E;
+                    pk_light_record<MAXC>(S, P, l, L, E);
+                    pk_light<MAXC, FEAT, COUNT>(S, hit, hp, n, view, h, L, E, L, 0.0, bias,
+                                                nchunks, diff, spec, cnt, nullptr, &fix);
+                }
             }
             if constexpr ((FEAT & kFeatArea) != 0) {
                 if (P.al_samples > 0) {

@@ -1,0 +1,279 @@
+// rt_shadow_table.hpp — the shadow-cull candidate mask of one wave tile and one point light,
+// formed outside the packet kernel (rt_packet.hip packet_cone_table_kernel, the same lane per tile
+// that forms the tile's camera-cone mask) and read by pk_light (rt_packet_kernel.hpp) with one
+// scalar load instead of origin_ball + cull_capsule in every casting wave.
+//
+// Plain C++: no device builtin, so a host program can call every function here
+// (tests/test_shadow_table_host.py builds one and checks the words against FP64 intersections of
+// the oracle's shadow rays).  Contraction: the library and the host test are both built with
+// -ffp-contract=off (build.py's HIP_FLAGS cover every translation unit, whatever the place of a
+// `#pragma clang fp contract` relative to this header), so the device forms the host's words;
+// nothing here relies on that — an FMA's rounding is far inside every slack below.
+//
+// Which tiles get a word.  pk_light's mask is formed from the wave's hit points; a conservative
+// one follows from the scene, the camera and the tile alone when the tile can only see planes:
+// its camera-cone mask (rt_cone_table.hpp) is empty, so no camera ray of the tile meets a sphere
+// and every shadow origin lies on a plane.  Every ray of the tile is unit(v) for a v of the
+// rectangle spanned by the four corner vectors in the plane z = dz (rt_cone_table.hpp's header).
+//
+// Classification.  Plane i (point p, normal n, num = (p − cam)·n as the packet image holds it) is
+// met by the ray along v at t·|v| = num / (n·v): g(v) = (n·v)/num is 1/t of the unnormalised ray
+// and linear in v, so its sign and any linear comparison of two planes' g over the rectangle are
+// decided at the four corners.
+//   never hit:  (n·v)·sign(num) ≤ 0 at every corner, as computed.  The exact value is then
+//               ≤ 1e-15·Σ|n_k v_k| over the rectangle and the kernel's n·d ≤ 2e-15·|n|₁ on the
+//               hit side, under plane_t's acceptance |n·d| > 1e-6 (|n|₁ ≤ 2 is required below);
+//               on the other side t < 0, and |num| ≥ 2^-900 keeps it from rounding to −0.
+//   always hit: (n·v)·sign(num) > 1e-12·Σ|n_k v_k| at every corner, and
+//               min_corner |n·v| / max_corner |v| ≥ 2e-6: n·v is linear and of one sign, |v| is
+//               convex, so every ray of the tile has |n·d| ≥ 2e-6 exactly and > 1e-6 as the kernel
+//               computes it — plane_t accepts the plane for every ray, with t > 0.
+//   anything else (a horizon inside the tile, |num| outside [2^-200, 2^200], |n|₁ > 2 or
+//   < 2^-20, a non-finite value): no word for the tile.
+// Hidden planes.  An always-hit plane j is left out when some always-hit plane i has
+// g_i ≥ g_j·(1 + 1e-9) at every corner: then t_i ≤ t_j/(1 + 1e-9) for every ray, the kernel's
+// quotients (each within 1e-9 relative of exact, below) keep t_i < t_j, and plane_t's strict
+// t < best never ends on j.  Planes the margin cannot order are both kept.  Without this rule a
+// wall's patch "below the floor" keeps five times the candidates.
+//
+// The ball of a kept plane.  The tile's hit points on it are the central projection of the
+// rectangle onto the plane — a projective map that sends the rectangle (on one side of the
+// plane's horizon: always hit) to the convex hull of the four projected corners
+// h_k = cam + v_k·(num / n·v_k).  The ball around their mean c with R = max |h_k − c| holds that
+// hull (R through an FP32 square root rounded up).  Rounding budget: with |n|₁ ≤ 2 and |n·d| ≥ 2e-6 the kernel's denominator carries
+// ≤ 5e-16·2 / 2e-6 = 5e-10 relative error, so its hit point cam + d·t is within 6e-10·|h − cam|
+// of the exact one, and so are the h_k formed here; R takes 1e-8·(|cam|₁ + |c|₁ + R) for both
+// (8× their sum), is rounded up to FP32 by the (1 + 1e-5) origin_ball applies, and gains
+// |bias|·1.001 for so = hp + n·bias with |n| ≤ 1 + 2ε (the oriented unit normal).
+//
+// The word is the OR over the kept planes of shadow_keeps — cull_capsule's sphere test
+// (rt_packet_device.hpp) at (c, R, light, RL = 0, bias) with the same FP32 expressions, slack,
+// `huge`, `far` and NaN rules; 1.0f / sl2 stands for v_rcp_f32 (within an ulp, inside the slack;
+// a denormal sl2 gives a large or infinite quotient, and then an inf or NaN distance keeps the
+// sphere).  A real word never has a bit ≥ ns set, so all-ones (ns ≤ 63) says "no word": the
+// wave forms its own mask.  Tables are built for at most kShadowTabLights point lights,
+// kShadowTabPlanes planes and 63 spheres, and never with an area light.
+#pragma once
+
+#include <math.h>
+#include <stdint.h>
+
+#include "rt_cone_table.hpp"
+
+#if defined(__clang__)
+#define RT_ST_UNROLL _Pragma("unroll")
+#else
+#define RT_ST_UNROLL
+#endif
+
+namespace rtamd {
+
+constexpr int kShadowTabLights = 4;
+constexpr int kShadowTabPlanes = 8;
+constexpr unsigned long long kShadowNoWord = ~0ull;
+
+// Lights per tile a scene's table holds (0: no shadow table for this scene).
+RT_CT_HD inline int shadow_table_lights(int ns, int np, int nl, bool area_light) {
+    return (!area_light && ns >= 1 && ns <= 63 && np >= 1 && np <= kShadowTabPlanes && nl >= 1 &&
+            nl <= kShadowTabLights)
+               ? nl
+               : 0;
+}
+
+struct ShadowBall {
+    double c[3];
+    float R;  // holds every shadow origin of the tile on its plane (bias included)
+};
+template <int kMaxPlanes = kShadowTabPlanes>
+struct ShadowBound {
+    ShadowBall ball[kMaxPlanes];
+    int n;    // kept planes
+    bool ok;  // false: no word for the tile
+};
+
+// The tile's origin balls.  planes: np records of 8 doubles px py pz nx ny nz num flag (the
+// packet image's: num = (p − cam)·n, flag ≠ 0 when 2^-900 ≤ |num| ≤ 2^400 and |n|₁ ≤ 2^90).
+// kCorners = 4 and kHideCorners = 4 are the bound; other values exist for the host test's
+// mutants only, as kBiasInR = false does.  kMaxPlanes: the caller's cap on np (the table kernel's
+// is 2 — scenes of three planes or more take the plane-culling variant, which reads no table —
+// so its loops unroll and its arrays stay in registers).  Divisions are kept to the four
+// t_k = num / n·v_k of a kept plane: the classification compares n·v, the hidden-plane rule
+// cross-multiplies.
+template <int kMaxPlanes = kShadowTabPlanes, int kCorners = 4, int kHideCorners = 4,
+          bool kBiasInR = true>
+RT_CT_HD inline ShadowBound<kMaxPlanes> shadow_tile_bound(const ConeRect& q, double half_w,
+                                                          double half_h, const double* cam,
+                                                          double dz, const double* planes, int np,
+                                                          double bias) {
+    ShadowBound<kMaxPlanes> B;
+    B.n = 0;
+    B.ok = false;
+    if (np < 1 || np > kMaxPlanes) return B;
+    double v[4][3], vl2_max = 0.0;
+    for (int k = 0; k < 4; ++k) {  // the kernel's expression (cone_tile_bound)
+        v[k][0] = (static_cast<double>((k & 1) ? q.x_hi : q.x_lo) - half_w) - cam[0];
+        v[k][1] = (half_h - static_cast<double>((k & 2) ? q.y_hi : q.y_lo)) - cam[1];
+        v[k][2] = dz;
+        const double l2 = v[k][0] * v[k][0] + v[k][1] * v[k][1] + dz * dz;
+        if (!(l2 > 0.0) || !isfinite(l2)) return B;
+        if (l2 > vl2_max) vl2_max = l2;
+    }
+    if (!(dz != 0.0) || !isfinite(dz) || !isfinite(bias)) return B;
+    const double cam1 = fabs(cam[0]) + fabs(cam[1]) + fabs(cam[2]);
+    if (!isfinite(cam1)) return B;
+    // e[i][k] = (n_i·v_k)·sign(num_i), > 0 on the hit side; g_i(v_k) = e[i][k] / an[i]
+    double e[kMaxPlanes][4], an[kMaxPlanes];
+    bool hit[kMaxPlanes];
+    RT_ST_UNROLL
+    for (int i = 0; i < kMaxPlanes; ++i) {
+        if (i >= np) break;
+        const double* p = planes + 8 * i;
+        const double num = p[6];
+        const double n1 = fabs(p[3]) + fabs(p[4]) + fabs(p[5]);
+        if (!(p[7] != 0.0) || !(n1 <= 2.0) || !(n1 >= 0x1p-20) || !(num != 0.0) || !isfinite(num))
+            return B;
+        // (the cross-multiplied products of the hidden-plane rule stay finite and normal)
+        if (!(fabs(num) <= 0x1p200) || !(fabs(num) >= 0x1p-200)) return B;
+        an[i] = fabs(num);
+        int n_hit = 0, n_miss = 0;
+        double e_min = INFINITY;
+        for (int k = 0; k < 4; ++k) {
+            const double a = p[3] * v[k][0], b = p[4] * v[k][1], c = p[5] * v[k][2];
+            const double ek = num > 0.0 ? (a + b) + c : -((a + b) + c);
+            const double mag = (fabs(a) + fabs(b)) + fabs(c);
+            if (!isfinite(ek) || !(fabs(ek) <= 0x1p200)) return B;
+            if (ek > 1e-12 * mag) ++n_hit;
+            else if (ek <= 0.0) ++n_miss;
+            if (fabs(ek) < e_min) e_min = fabs(ek);
+            e[i][k] = ek;
+        }
+        if (n_miss == 4) {
+            hit[i] = false;
+        } else if (n_hit == 4 && e_min * e_min >= 4e-12 * vl2_max) {  // |n·v| ≥ 2e-6·|v|
+            hit[i] = true;
+        } else {
+            return B;
+        }
+    }
+    RT_ST_UNROLL
+    for (int j = 0; j < kMaxPlanes; ++j) {
+        if (j >= np) break;
+        if (!hit[j]) continue;
+        bool hidden = false;
+    RT_ST_UNROLL
+        for (int i = 0; i < kMaxPlanes; ++i) {
+            if (i >= np || hidden) break;
+            if (i == j || !hit[i]) continue;
+            // g_i ≥ g_j·(1 + 1e-9), all four factors positive and ≤ 2^200; a product under the
+            // normal range orders nothing
+            int ahead = 0;
+            for (int k = 0; k < kHideCorners; ++k) {
+                const double lhs = e[i][k] * an[j], rhs = e[j][k] * an[i];
+                ahead += lhs >= rhs * (1.0 + 1e-9) && rhs >= 0x1p-900;
+            }
+            hidden = ahead == kHideCorners;
+        }
+        if (hidden) continue;
+        ShadowBall& S = B.ball[B.n];
+        double h[4][3];
+        S.c[0] = S.c[1] = S.c[2] = 0.0;
+        // t_k = num / n·v_k through ONE division: an · Π_{m≠k} e_m / Π e_m (each factor in
+        // (0, 2^200], the products normal or the tile has no word; a few ulps, inside the 1e-8)
+        const double e01 = e[j][0] * e[j][1], e23 = e[j][2] * e[j][3];
+        const double scale = an[j] / (e01 * e23);
+        if (!(e01 * e23 >= 0x1p-900) || !isfinite(scale)) return B;
+        const double tk[4] = {scale * (e[j][1] * e23), scale * (e[j][0] * e23),
+                              scale * (e01 * e[j][3]), scale * (e01 * e[j][2])};
+        for (int k = 0; k < kCorners; ++k) {
+            const double t = tk[k];
+            for (int a = 0; a < 3; ++a) {
+                h[k][a] = cam[a] + v[k][a] * t;
+                S.c[a] += h[k][a] / kCorners;
+            }
+        }
+        double r2 = 0.0;
+        for (int k = 0; k < kCorners; ++k) {
+            const double dx = h[k][0] - S.c[0], dy = h[k][1] - S.c[1], dz_ = h[k][2] - S.c[2];
+            const double d2 = dx * dx + dy * dy + dz_ * dz_;
+            if (d2 > r2) r2 = d2;
+        }
+        // (an FP32 square root rounded up: R is only ever an upper bound)
+        const double R = static_cast<double>(sqrtf(static_cast<float>(r2) * (1.0f + 1e-6f)) *
+                                             (1.0f + 1e-6f));
+        const double c1 = fabs(S.c[0]) + fabs(S.c[1]) + fabs(S.c[2]);
+        const double Rm = R + 1e-8 * ((cam1 + c1) + R);
+        if (!isfinite(Rm) || !isfinite(c1)) return B;
+        S.R = static_cast<float>(Rm) * (1.0f + 1e-5f);
+        if (kBiasInR) S.R += static_cast<float>(fabs(bias)) * (1.0f + 1e-6f) * 1.001f;
+        if (!isfinite(S.R)) return B;
+        ++B.n;
+    }
+    B.ok = true;
+    return B;
+}
+
+// cull_capsule's sphere test for RL = 0: origins in the ball (c, R), rays towards L.  The
+// segment's terms are formed once for a ball and a light (as cull_capsule forms them once for a
+// wave), then each sphere — centre s, culling radius r (cone_terms' float 7) — is tested.
+struct ShadowSeg {
+    float sx, sy, sz, sl2, inv_sl2, Rc;
+    bool huge;
+};
+RT_CT_HD inline ShadowSeg shadow_seg(const double* c, float R, const double* L, double bias) {
+    ShadowSeg G;
+    G.sx = static_cast<float>(L[0] - c[0]);
+    G.sy = static_cast<float>(L[1] - c[1]);
+    G.sz = static_cast<float>(L[2] - c[2]);
+    G.sl2 = G.sx * G.sx + G.sy * G.sy + G.sz * G.sz;
+    G.inv_sl2 = 1.0f / G.sl2;  // only read when sl2 > 0
+    G.huge = !(G.sl2 <= 0x1p120f);
+    G.Rc = (R > 0.0f ? R : 0.0f) + static_cast<float>(fabs(bias)) * (1.0f + 1e-6f) * 1.001f;
+    return G;
+}
+RT_CT_HD inline bool shadow_seg_keeps(const ShadowSeg& G, const double* c, const double* s,
+                                      float r) {
+    const float vx = static_cast<float>(s[0] - c[0]), vy = static_cast<float>(s[1] - c[1]),
+                vz = static_cast<float>(s[2] - c[2]);
+    const float vs = vx * G.sx + vy * G.sy + vz * G.sz;
+    const float vv = vx * vx + vy * vy + vz * vz;
+    float d2;
+    if (!(vs > 0.0f) || !(G.sl2 > 0.0f)) {
+        d2 = vv;
+    } else if (!(vs < G.sl2)) {
+        const float wx = vx - G.sx, wy = vy - G.sy, wz = vz - G.sz;
+        d2 = wx * wx + wy * wy + wz * wz;
+    } else {
+        d2 = vv - (vs * vs) * G.inv_sl2;
+    }
+    const float lim = (r + G.Rc) * (1.0f + 1e-4f);
+    const float far = 1e5f * r - G.Rc;
+    return !(d2 > lim * lim + 2e-5f * (vv + G.sl2)) || !(far > 0.0f) || !(vv <= far * far) ||
+           G.huge;
+}
+RT_CT_HD inline bool shadow_keeps(const double* c, float R, const double* L, double bias,
+                                  const double* s, float r) {
+    return shadow_seg_keeps(shadow_seg(c, R, L, bias), c, s, r);
+}
+
+// The tile's word for a light at L over spheres [0, ns), ns ≤ 63: sphere i's centre is
+// sph + sph_stride · i (doubles) and its culling radius rad[rad_stride · i] (floats).
+template <int kMaxPlanes>
+RT_CT_HD inline unsigned long long shadow_tile_word(const ShadowBound<kMaxPlanes>& B,
+                                                    const double* L, double bias,
+                                                    const double* sph, int sph_stride,
+                                                    const float* rad, int rad_stride, int ns) {
+    if (!B.ok || ns > 63) return kShadowNoWord;
+    unsigned long long m = 0;
+    RT_ST_UNROLL
+    for (int b = 0; b < kMaxPlanes; ++b) {
+        if (b >= B.n) break;
+        const ShadowSeg G = shadow_seg(B.ball[b].c, B.ball[b].R, L, bias);
+        for (int i = 0; i < ns; ++i)
+            if (shadow_seg_keeps(G, B.ball[b].c, sph + static_cast<long>(sph_stride) * i,
+                                 rad[static_cast<long>(rad_stride) * i]))
+                m |= 1ull << i;
+    }
+    return m;
+}
+
+}  // namespace rtamd
