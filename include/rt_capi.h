@@ -480,6 +480,13 @@ rt_status rt_debug_cone_table(rt_context* ctx, uint64_t* with_table, uint64_t* w
  * turns the shadow tables off, independently of RTAMD_PK_CONE_TAB. */
 rt_status rt_debug_shadow_table(rt_context* ctx, uint64_t* with_table, uint64_t* without_table);
 
+/* Test hook (read-only): the same count for the tile class words — frames enqueued with a class
+ * word per tile next to their cone and shadow tables (*with_words: the fix-up variant of the
+ * packet kernel renders the tiles that see one plane or only sky on its uniform path) and
+ * without (*without_words).  They exist only where both tables are formed and passed;
+ * RTAMD_PK_TILE_CLASS=0 in the environment, read per launch, turns them off. */
+rt_status rt_debug_tile_class(rt_context* ctx, uint64_t* with_words, uint64_t* without_words);
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif

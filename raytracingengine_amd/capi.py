@@ -62,6 +62,7 @@ EXPORTED = [
     "rt_render_gather_batch", "rt_render_gather_all_batch", "rt_gbuffer", "rt_gbuffer_device",
     "rt_debug_cone_table",
     "rt_debug_shadow_table",
+    "rt_debug_tile_class",
 ]
 
 
@@ -190,6 +191,7 @@ def load_library(path: str = LIB_PATH):
         "rt_debug_tile_order": [vp, vp, vp, vp, vp, ctypes.c_size_t, vp, vp, vp],
         "rt_debug_cone_table": [vp, vp, vp],
         "rt_debug_shadow_table": [vp, vp, vp],
+        "rt_debug_tile_class": [vp, vp, vp],
         "rt_debug_assemble_rows": [vp, vp, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_uint32,
                                    ctypes.c_uint32, ctypes.c_uint32, vp],
     }.items():
@@ -326,6 +328,12 @@ class Context:
         """Packet-kernel frames enqueued so far (with, without) a shadow-cull table."""
         a, b = ctypes.c_uint64(), ctypes.c_uint64()
         _check(_lib.rt_debug_shadow_table(self._h, ctypes.byref(a), ctypes.byref(b)))
+        return a.value, b.value
+
+    def debug_tile_class(self) -> tuple[int, int]:
+        """Packet-kernel frames enqueued so far (with, without) tile class words."""
+        a, b = ctypes.c_uint64(), ctypes.c_uint64()
+        _check(_lib.rt_debug_tile_class(self._h, ctypes.byref(a), ctypes.byref(b)))
         return a.value, b.value
 
     def debug_vec_ops(self, v: np.ndarray) -> np.ndarray:

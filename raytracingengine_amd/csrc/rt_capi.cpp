@@ -347,6 +347,9 @@ rt_status enqueue_frames(rt_context* ctx, const rt_scene* sc, const rt_camera* c
         for (int f = 0; f < nframes; ++f)  // rt_debug_shadow_table
             ++((nframes > 1 ? p.fr_stab[f] : p.shadow_tab) ? ctx->shadow_tab_frames
                                                             : ctx->shadow_notab_frames);
+        for (int f = 0; f < nframes; ++f)  // rt_debug_tile_class
+            ++((nframes > 1 ? p.fr_ctab[f] : p.class_tab) ? ctx->tile_class_frames
+                                                          : ctx->tile_noclass_frames);
     }
     // the fix-up variant of the packet kernel (undecided shadow rays re-rendered per pixel after
     // the launch) uses the context's fix-up list: ordered across streams like the counters
@@ -1139,6 +1142,14 @@ rt_status rt_debug_shadow_table(rt_context* ctx, uint64_t* with_table, uint64_t*
         return fail(RT_ERR_INVALID_ARG, "NULL argument to rt_debug_shadow_table");
     *with_table = ctx->shadow_tab_frames;
     *without_table = ctx->shadow_notab_frames;
+    return RT_OK;
+}
+
+rt_status rt_debug_tile_class(rt_context* ctx, uint64_t* with_words, uint64_t* without_words) {
+    if (!ctx || !with_words || !without_words)
+        return fail(RT_ERR_INVALID_ARG, "NULL argument to rt_debug_tile_class");
+    *with_words = ctx->tile_class_frames;
+    *without_words = ctx->tile_noclass_frames;
     return RT_OK;
 }
 

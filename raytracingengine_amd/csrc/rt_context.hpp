@@ -84,6 +84,8 @@ struct rt_context {
     uint64_t cone_tab_frames = 0, cone_notab_frames = 0;
     // ... and with / without a shadow-cull table (rt_debug_shadow_table)
     uint64_t shadow_tab_frames = 0, shadow_notab_frames = 0;
+    // ... and with / without tile class words (rt_debug_tile_class)
+    uint64_t tile_class_frames = 0, tile_noclass_frames = 0;
     // rt_render_multi: RCCL communicators over the devices of the last context list this
     // context led (rt_multi.cpp); destroyed with the context
     std::vector<rt_context*> group_ctxs;
@@ -140,7 +142,8 @@ struct rt_scene {
         // packet_cone_table_kernel on the stream of the render that created it, never rewritten;
         // renders on other streams wait for `ready` until it has completed.  Dropped with the
         // image entry.  The buffer also holds the shadow-cull words formed from the cone masks
-        // (rt_shadow_table.hpp), after them: nl per tile when the scene gets any.
+        // (rt_shadow_table.hpp), after them: nl per tile when the scene gets any, and then the
+        // tile class words, one per tile, when the key says so.
         struct ConeTab {
             static constexpr size_t kKeyWords = 20;
             uint32_t key[kKeyWords] = {};

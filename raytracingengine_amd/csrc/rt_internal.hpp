@@ -142,6 +142,13 @@ struct TraceParams {
     // pointer: the wave forms its own mask (origin_ball + cull_capsule).  fr_stab[f]: frame f's
     const unsigned long long* shadow_tab;
     const unsigned long long* fr_stab[kPkMaxBatch];
+    // the fix-up variant of those: the class word of every wave tile (tile_class_word,
+    // rt_shadow_table.hpp), one per tile at (tby · gx + tbx) · waves + wave in the same buffer
+    // after the shadow words — 0: the general path, else the tile sees only sky or only one
+    // plane and casts no shadow ray a sphere can meet (pk_uniform_tile).  Null: no tile is
+    // classified.  fr_ctab[f]: frame f's
+    const unsigned long long* class_tab;
+    const unsigned long long* fr_ctab[kPkMaxBatch];
 };
 // the runtime passes at most 4 KiB of kernel arguments (packet_image_batch_kernel and
 // packet_cone_table_kernel take a job list of kPkMaxBatch pointers and ints next to it)
@@ -216,6 +223,9 @@ struct PkConeJobs {
     // > 0: the shadow-cull words too (rt_shadow_table.hpp), shadow_nl per tile, written after
     // the job's cone words: dst[j] + tiles
     int32_t shadow_nl;
+    // != 0 (with shadow_nl > 0 only): the tile class words too, one per tile after the shadow
+    // words: dst[j] + tiles · (1 + shadow_nl)
+    int32_t class_words;
 };
 hipError_t launch_packet_cone_tables(const TraceParams& p, const PkConeJobs& jobs,
                                      hipStream_t stream);

@@ -54,8 +54,10 @@ hipError_t launch_packet_image_batch(const TraceParams& p, const PkImageJobs& jo
 // With J.shadow_nl > 0 the same lane goes on to the tile's shadow-cull words
 // (rt_shadow_table.hpp), which depend on the cone mask it just formed: nl words per tile after
 // the job's cone words, so a batch of new cameras pays no launch of its own for them.
+// With J.class_words the lane closes with the tile's class word (tile_class_word), one per tile
+// after the shadow words: which tiles the fix-up variant renders on its uniform path.
 // The kernel waits more than it issues (dependent FP64 chains, one lane per tile), so it is
-// built for 5 waves per SIMD (96 VGPRs, 88 B of scratch; by itself it compiles to 3): the
+// built for 5 waves per SIMD (96 VGPRs, 104 B of scratch; by itself it compiles to 3): the
 // measured times are in DESIGN §4 and profiles/shadow_table_pmc.txt.
 constexpr int kConeThreads = 256;
 __global__ __launch_bounds__(kConeThreads, 5) void packet_cone_table_kernel(TraceParams P,
@@ -96,8 +98,18 @@ __global__ __launch_bounds__(kConeThreads, 5) void packet_cone_table_kernel(Trac
     SB.ok = false;
     if (cone == 0)
         SB = shadow_tile_bound<2>(q, P.half_w, P.half_h, camp, dz, img + kPkSph * ns, P.np, P.bias);
-    for (int l = 0; l < J.shadow_nl; ++l)
+    unsigned long long any = 0;
+    for (int l = 0; l < J.shadow_nl; ++l) {
         sw[l] = shadow_tile_word(SB, P.lt + kLtStride * l, P.bias, s_ctr, 3, s_terms + 7, 8, ns);
+        any |= sw[l];
+    }
+    if (J.class_words == 0) return;
+    // the tile's class word (tile_class_word), after every tile's shadow words; s_pln of the
+    // image follows its planes and lights (pk_build_image).  The OR of the tile's shadow words
+    // stands for them (zero iff every one is; the launcher checked shadow_nl <= kShadowTabLights)
+    const double* pln = img + kPkSph * ns + kPlStride * P.np + kLtStride * P.nl;
+    J.dst[blockIdx.y][static_cast<size_t>(gx) * gy * waves * (1 + J.shadow_nl) + t] =
+        tile_class_word(cone, SB, &any, 1, pln, P.np);
 }
 
 hipError_t launch_packet_cone_tables(const TraceParams& p, const PkConeJobs& jobs,
@@ -107,6 +119,7 @@ hipError_t launch_packet_cone_tables(const TraceParams& p, const PkConeJobs& job
         return hipErrorInvalidValue;
     if (jobs.shadow_nl != 0 && jobs.shadow_nl != packet_shadow_table_lights(p))
         return hipErrorInvalidValue;
+    if (jobs.class_words != 0 && jobs.shadow_nl <= 0) return hipErrorInvalidValue;
     for (int j = 0; j < jobs.n; ++j) {
         const int f = jobs.frame[j];
         if (!jobs.dst[j] || f < -1 || f >= static_cast<int>(p.nframes) ||

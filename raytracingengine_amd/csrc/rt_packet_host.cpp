@@ -226,25 +226,35 @@ rt_status packet_image_entry(rt_context* ctx, const rt_scene* sc, const double* 
 // work only, and a cached table formed that way is one of its own, whatever the bias).  With
 // RTAMD_PK_CONE_TAB=0 alone the cone words are still formed — the shadow words depend on them —
 // but only the shadow pointers reach the kernel.
+// The tile class words (tile_class_word, rt_shadow_table.hpp; TraceParams.class_tab / fr_ctab)
+// follow the shadow words in the same buffer, one per tile: formed by the same launch only when
+// both the cone and the shadow words are formed and passed, under the same key (one more word
+// says whether the buffer holds them), cache entry, ring entry and caps, and counted in the
+// ring's accounting.  RTAMD_PK_TILE_CLASS=0 (read per launch): none are formed or passed, and a
+// cached table formed that way is one of its own.
 constexpr size_t kMaxConeTabs = 8;
 // The ring's table memory per entry (kPkBatchRing entries), counted in cone words: a 32-frame
 // 1080p batch takes 8.3 MB (259 KB a frame), a 4K frame 1 MB; frames past the cap go without a
-// table.  The shadow words come on top (nl times as much, 16.6 MB for a 32-frame C2 batch).
+// table.  The class words count too (as much again: 16.6 MB for the 32-frame batch, still under
+// the cap).  The shadow words come on top (nl times as much, 8.3 MB for a 32-frame C2 batch).
 constexpr size_t kConeRingBytes = size_t(16) << 20;
 
 struct TabsWanted {
     bool cone, shadow;
     int shadow_nl;  // shadow words per tile this launch's tables hold (0: cone masks only)
+    bool cls;       // the tile class words too, one per tile after the shadow words
     bool any() const { return cone || shadow; }
 };
 TabsWanted tables_wanted(const rt_scene* sc, const TraceParams& p) {
-    TabsWanted w{false, false, 0};
+    TabsWanted w{false, false, 0, false};
     if (!packet_reads_cone_table(p, sc->max_specular > 0.0)) return w;
     const char* e = std::getenv("RTAMD_PK_CONE_TAB");
     w.cone = !(e && std::atoi(e) == 0);
     e = std::getenv("RTAMD_PK_SHADOW_TAB");
     w.shadow = packet_shadow_table_lights(p) > 0 && !(e && std::atoi(e) == 0);
     w.shadow_nl = w.shadow ? packet_shadow_table_lights(p) : 0;
+    e = std::getenv("RTAMD_PK_TILE_CLASS");
+    w.cls = w.cone && w.shadow && !(e && std::atoi(e) == 0);
     return w;
 }
 
@@ -257,7 +267,7 @@ TabsWanted tables_wanted(const rt_scene* sc, const TraceParams& p) {
 // bias bit for bit: the words formed at one bias are wrong masks at a larger one.  Returns the
 // table's size.
 constexpr size_t kConeKeyWords = rt_scene::PkImage::ConeTab::kKeyWords;
-size_t cone_table_key(const TraceParams& p, double dz, int shadow_nl,
+size_t cone_table_key(const TraceParams& p, double dz, int shadow_nl, bool cls,
                       uint32_t (&key)[kConeKeyWords], size_t* tiles = nullptr) {
     uint32_t gx, gy, waves;
     packet_grid(p, gx, gy, waves);
@@ -267,28 +277,30 @@ size_t cone_table_key(const TraceParams& p, double dz, int shadow_nl,
     std::memset(key, 0, sizeof key);
     std::memcpy(key, k, sizeof k);
     std::memcpy(key + 9, c, sizeof c);
-    static_assert(sizeof k + sizeof c + sizeof(uint32_t) + sizeof(double) <=
+    static_assert(sizeof k + sizeof c + 2 * sizeof(uint32_t) + sizeof(double) <=
                       sizeof(uint32_t) * kConeKeyWords, "cone table key");
     // (lights and planes are the scene's, like the spheres: not part of the key)
     if (shadow_nl > 0) {
         key[15] = static_cast<uint32_t>(shadow_nl);
         std::memcpy(key + 16, &p.bias, sizeof p.bias);
+        key[18] = cls ? 1u : 0u;  // the class words follow the shadow words
     }
     const size_t n = static_cast<size_t>(gx) * gy * waves;
     if (tiles) *tiles = n;
-    return sizeof(unsigned long long) * n * (1 + static_cast<size_t>(shadow_nl > 0 ? shadow_nl : 0));
+    return sizeof(unsigned long long) * n *
+           (1 + static_cast<size_t>(shadow_nl > 0 ? shadow_nl + (cls ? 1 : 0) : 0));
 }
 
 // The cached camera's table for p's launch shape: *tab = the existing one (this stream ordered
 // after the launch that formed it), or a new entry whose table the caller forms (*fresh) and
 // whose event it records; null when the camera's table list is full.
 rt_status cone_table_entry(rt_context* ctx, rt_scene::PkImage& im, const TraceParams& p,
-                           double dz, int shadow_nl, rt_scene::PkImage::ConeTab** tab,
-                           bool* fresh) {
+                           double dz, int shadow_nl, bool cls,
+                           rt_scene::PkImage::ConeTab** tab, bool* fresh) {
     *tab = nullptr;
     *fresh = false;
     uint32_t key[kConeKeyWords];
-    const size_t bytes = cone_table_key(p, dz, shadow_nl, key);
+    const size_t bytes = cone_table_key(p, dz, shadow_nl, cls, key);
     for (auto& t : im.tabs) {
         if (std::memcmp(t.key, key, sizeof key) != 0) continue;
         if (!t.done && t.stream != ctx->stream) {
@@ -333,7 +345,8 @@ rt_status cone_table_single(rt_context* ctx, const rt_scene* sc, rt_scene::PkIma
     if (!want.any()) return RT_OK;
     rt_scene::PkImage::ConeTab* t = nullptr;
     bool fresh = false;
-    const rt_status st = cone_table_entry(ctx, im, p, p.cam_dz, want.shadow_nl, &t, &fresh);
+    const rt_status st =
+        cone_table_entry(ctx, im, p, p.cam_dz, want.shadow_nl, want.cls, &t, &fresh);
     if (st != RT_OK || !t) return st;
     if (fresh) {
         PkConeJobs jobs;
@@ -342,6 +355,7 @@ rt_status cone_table_single(rt_context* ctx, const rt_scene* sc, rt_scene::PkIma
         jobs.frame[0] = -1;
         jobs.n = 1;
         jobs.shadow_nl = want.shadow_nl;
+        jobs.class_words = want.cls ? 1 : 0;
         hipError_t e = launch_packet_cone_tables(p, jobs, ctx->stream);
         if (e == hipSuccess) e = hipEventRecord(t->ready, ctx->stream);
         if (e != hipSuccess) {
@@ -351,10 +365,11 @@ rt_status cone_table_single(rt_context* ctx, const rt_scene* sc, rt_scene::PkIma
     }
     uint32_t key[kConeKeyWords];
     size_t tiles = 0;
-    (void)cone_table_key(p, p.cam_dz, want.shadow_nl, key, &tiles);
+    (void)cone_table_key(p, p.cam_dz, want.shadow_nl, want.cls, key, &tiles);
     const unsigned long long* words = static_cast<const unsigned long long*>(t->buf.ptr);
     if (want.cone) p.cone_tab = words;
     if (want.shadow) p.shadow_tab = words + tiles;
+    if (want.cls) p.class_tab = words + tiles * (1 + static_cast<size_t>(want.shadow_nl));
     return RT_OK;
 }
 
@@ -508,8 +523,10 @@ rt_status packet_batch_images(rt_context* ctx, const rt_scene* sc, const rt_came
     uint32_t key[kConeKeyWords];
     size_t tiles = 0;
     const size_t tab_bytes =  // (the sizes only)
-        (cone_table_key(p, 0.0, want.shadow_nl, key, &tiles) + 255) & ~size_t(255);
-    const size_t cone_bytes = (sizeof(unsigned long long) * tiles + 255) & ~size_t(255);
+        (cone_table_key(p, 0.0, want.shadow_nl, want.cls, key, &tiles) + 255) & ~size_t(255);
+    // (the cap counts the cone words and the class words; the shadow words come on top)
+    const size_t cone_bytes =
+        (sizeof(unsigned long long) * tiles * (want.cls ? 2 : 1) + 255) & ~size_t(255);
     char* ring_tab = nullptr;
     size_t ring_room = 0;
     if (any_ring) {
@@ -530,10 +547,13 @@ rt_status packet_batch_images(rt_context* ctx, const rt_scene* sc, const rt_came
     PkConeJobs cj;
     std::memset(&cj, 0, sizeof cj);
     cj.shadow_nl = want.shadow_nl;
+    cj.class_words = want.cls ? 1 : 0;
     // the kernel's pointers of a frame whose table is (or will be) at `words`
     auto hand = [&](int f, const unsigned long long* words) {
         p.fr_tab[f] = want.cone ? words : nullptr;
         p.fr_stab[f] = want.shadow ? words + tiles : nullptr;
+        p.fr_ctab[f] =
+            want.cls ? words + tiles * (1 + static_cast<size_t>(want.shadow_nl)) : nullptr;
     };
     rt_scene::PkImage* made[kPkMaxBatch];  // entries that got a fresh table (newest last)
     rt_scene::PkImage::ConeTab* made_tab[kPkMaxBatch];
@@ -542,10 +562,12 @@ rt_status packet_batch_images(rt_context* ctx, const rt_scene* sc, const rt_came
     for (int f = 0; f < nframes && st == RT_OK; ++f) {
         p.fr_tab[f] = nullptr;
         p.fr_stab[f] = nullptr;
+        p.fr_ctab[f] = nullptr;
         unsigned long long* dst = nullptr;
         if (kind[f] == kDup) {
             p.fr_tab[f] = p.fr_tab[dup_of[f]];
             p.fr_stab[f] = p.fr_stab[dup_of[f]];
+            p.fr_ctab[f] = p.fr_ctab[dup_of[f]];
             continue;
         }
         if (kind[f] == kRing) {
@@ -556,7 +578,8 @@ rt_status packet_batch_images(rt_context* ctx, const rt_scene* sc, const rt_came
         } else {
             rt_scene::PkImage::ConeTab* t = nullptr;
             bool fresh = false;
-            st = cone_table_entry(ctx, *ent[f], p, p.fr_dz[f][0], want.shadow_nl, &t, &fresh);
+            st = cone_table_entry(ctx, *ent[f], p, p.fr_dz[f][0], want.shadow_nl, want.cls, &t,
+                                  &fresh);
             if (st != RT_OK || !t) continue;
             hand(f, static_cast<const unsigned long long*>(t->buf.ptr));
             if (!fresh) continue;

@@ -6,6 +6,7 @@
 #pragma once
 
 #include "rt_packet_device.hpp"
+#include "rt_shadow_table.hpp"
 
 #pragma clang fp contract(off)
 
@@ -335,6 +336,93 @@ __device__ __forceinline__ void pk_light_record(const PacketScene& S, const Trac
     }
 }
 
+// A uniform tile of the fix-up variant (class word `cls` ≠ 0: tile_class_word,
+// rt_shadow_table.hpp): every camera ray of the wave misses everything (kTileSky) or ends on the
+// one plane k = cls − kTilePlane0, and no shadow ray of the tile can meet a sphere.  The wave's
+// scene is then that plane's record, oriented normal and material row, the np ≤ 2 plane records
+// of the shadow classification and the light records: wave-uniform, read from the global packet
+// image `img` (pk_build_image's layout, no chunk bounds: ns ≤ 63) and the scene through the
+// scalar cache — no LDS image, no sphere, no mask, no divergence bookkeeping.  Every lane is
+// active, the lanes past the image edge included (clamped rays of the tile's rectangle: the
+// class holds for them; the epilogue stores and queues nothing for them).  Returns the pixel's
+// colour with the bits of the general path, whose operations these are, in its order:
+// closest_camera's plane loop ends on plane k with t = num / n·d formed with found = false
+// (the class's ordering argument), the normal is s_pln's, pk_light runs with active = true and a
+// table word of 0 (pk_occlusion_t<1, FEAT, false>: the plane loop over every plane, M.pm all
+// ones), and the shading is the kernel's own.
+template <int MAXC, int FEAT>
+__device__ __forceinline__ d3 pk_uniform_tile(const PacketScene& S, const TraceParams& P,
+                                              const double* img, unsigned long long cls, d3 cam,
+                                              d3 d, int ns, int np, int nl, double bias,
+                                              bool& fix) {
+    if (cls == kTileSky) return sky(d);
+    const int k = static_cast<int>(cls - kTilePlane0);
+    const pk_cdp pl = (pk_cdp)img + kPkSph * ns;
+    const pk_cdp rec = pl + kPlStride * k;
+    const pk_cdp on = pl + kPlStride * np + kLtStride * nl + 4 * k;
+    const pk_cdp m = (pk_cdp)P.sph_mat + kMatStride * (ns + k);
+    // The shadow classification's planes: the kept one and, with two planes, the other (np ≤ 2
+    // where a class word exists: packet_shadow_table_lights).  Each plane sets `blocked` or
+    // `undecided` by itself, so their order does not matter.
+    const pk_cdp oth = pl + kPlStride * (np > 1 ? 1 - k : k);
+    const d3 pp = mk(rec[0], rec[1], rec[2]), pn = mk(rec[3], rec[4], rec[5]);
+    const double num = rec[6], core = rec[7];
+    const d3 n = mk(on[0], on[1], on[2]);
+    bool found = false;
+    double t = 0.0;
+    int prim = -1;
+    const double denom = dot(pn, d);
+    if (core != 0.0) plane_t_core(num, denom, ns + k, found, t, prim);  // uniform
+    else plane_t(num, denom, ns + k, found, t, prim);
+    const d3 hp = cam + d * t;
+    d3 diff = mk(0.0, 0.0, 0.0);
+    const d3 spec = mk(0.0, 0.0, 0.0);  // (no Blinn-Phong in this variant)
+    for (int l = 0; l < nl; ++l) {
+        d3 lpos, E;
+        pk_light_record<MAXC>(S, P, l, lpos, E);
+        // pk_light, active
+        double dist = 0.0, inv_d2 = 0.0;
+        d3 L = mk(0.0, 0.0, 0.0);
+        light_dir(lpos - hp, dist, L, inv_d2);
+        const bool reach = !(dist <= 0.0);
+        if (!reach) L = mk(0.0, 0.0, 0.0);
+        const double ndl = smax(0.0, dot(n, L));
+        const bool need = reach && !(ndl <= 0.0) && !(dist <= bias);
+        const d3 so = hp + n * bias;
+        if (!__ballot(need)) continue;  // no lane casts this shadow ray (uniform)
+        // pk_occlusion_t<1, FEAT, false>'s plane classification, every plane
+        bool blocked = false, undecided = false;
+        if (need) {
+            const double max_dist = dist - bias;
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                if (i >= np) break;
+                const d3 qp = i == 0 ? pp : mk(oth[0], oth[1], oth[2]);
+                const d3 qn = i == 0 ? pn : mk(oth[3], oth[4], oth[5]);
+                const double dn = dot(qn, L);
+                if (!(fabs(dn) > 1e-6)) continue;
+                const double nm = dot(qp - so, qn);
+                const double A = dn > 0.0 ? nm : -nm, B = fabs(dn);
+                if (A < -1e-300 * B) continue;
+                if (A >= max_dist * B * (1.0 + 1e-9)) continue;
+                if (A > bias * B * (1.0 + 1e-9) && A < max_dist * B * (1.0 - 1e-9)) blocked = true;
+                else undecided = true;
+            }
+        }
+        const double T = (!undecided && blocked) ? 0.0 : 1.0;
+        // no march here: the pixel is queued for packet_fixup_kernel (its output is rewritten)
+        if (undecided) fix = true;
+        if (!need) continue;
+        if (T <= bias) continue;
+        diff = diff + ((E * inv_d2) * ndl) * T;
+    }
+    const d3 local = hmul(mk(m[0], m[1], m[2]), diff) + spec * m[4];
+    const double tr = sclamp(m[5], 0.0, 1.0);
+    d3 fin = mk(0.0, 0.0, 0.0);
+    if (tr < 1.0) fin = fin + local * (1.0 - tr);
+    return fin;
+}
+
 // Waves per SIMD of a variant (its register budget).
 constexpr int pk_waves(int MAXC, int FEAT, bool COUNT, bool MULTI) {
     return (FEAT == kFeatFix && MAXC == 1 && !MULTI && !COUNT) ? RT_PACKET_FIX_WAVES
@@ -394,6 +482,11 @@ __global__ __launch_bounds__(64 * kWgWavesX * WGY, pk_waves(MAXC, FEAT, COUNT, M
     constexpr bool kTab = kLean && !MULTI && !COUNT && (FEAT == 0 || FEAT == kFeatFix);
     const unsigned long long* cone_tab = kTab ? P.cone_tab : nullptr;
     const unsigned long long* shadow_tab = kTab ? P.shadow_tab : nullptr;
+    // The fix-up variant of those also reads the tiles' class words (pk_uniform_tile).  The
+    // marching variant does not: its undecided lanes march over the LDS image, so it would have
+    // to keep the staging, and it stays on the general path as it is.
+    constexpr bool kUni = kTab && FEAT == kFeatFix;
+    const unsigned long long* class_tab = kUni ? P.class_tab : nullptr;
     double cam_dz = P.cam_dz, cam_dz2 = P.cam_dz2;
     if (P.nframes) {
         const PkFrame& F = P.fr[blockIdx.z];
@@ -408,15 +501,39 @@ __global__ __launch_bounds__(64 * kWgWavesX * WGY, pk_waves(MAXC, FEAT, COUNT, M
             cone_tab = P.fr_tab[blockIdx.z];
             shadow_tab = P.fr_stab[blockIdx.z];
         }
+        if constexpr (kUni) class_tab = P.fr_ctab[blockIdx.z];
     }
     const d3 cam = mk(camp[0], camp[1], camp[2]);
     constexpr int kThreads = 64 * kWgWavesX * WGY;
-    if (pk_img) {  // the image of this scene and camera, formed once (packet_image_kernel)
+    // This wave's class word (0: the general path) and whether the workgroup stages the image:
+    // every wave reads the adjacent words of all the workgroup's waves (one scalar load) and
+    // forms the same test, so the barrier count stays uniform; a workgroup of uniform waves
+    // reads no LDS afterwards (pk_uniform_tile, the epilogue) and skips the copy and its barrier.
+    unsigned long long cls = kTileGeneral;
+    bool staged = true;
+    if constexpr (kUni) {
+        if (class_tab && pk_img && P.max_rec > 0) {
+            const pk_culp cw =
+                (pk_culp)class_tab + (tby * gridDim.x + tbx) * (kWgWavesX * WGY);
+            const uint32_t w = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(tid >> 6));
+            bool all = true;
+#pragma unroll
+            for (uint32_t i = 0; i < kWgWavesX * WGY; ++i) {
+                const unsigned long long c = cw[i];
+                all = all && c != kTileGeneral;
+                if (i == w) cls = c;
+            }
+            staged = !all;
+        }
+    }
+    if (pk_img && staged) {  // the image of this scene and camera, formed once (packet_image_kernel)
         const float4* src = reinterpret_cast<const float4*>(pk_img);
         float4* dst = reinterpret_cast<float4*>(smem);
         const int nv = static_cast<int>(pk_image_bytes(ns, np, nl) / 16);
         for (int i = tid; i < nv; i += kThreads) dst[i] = src[i];
         __syncthreads();
+    } else if (pk_img) {
+        // (a workgroup of uniform tiles: no image in LDS)
     } else if (pk_pub) {
         // A camera without a cached image: the launch's first workgroup forms the image and
         // publishes it as {epoch, word} granules (8-byte agent-scope atomic stores, written
@@ -534,6 +651,9 @@ __global__ __launch_bounds__(64 * kWgWavesX * WGY, pk_waves(MAXC, FEAT, COUNT, M
         d3 col;
         if (P.max_rec <= 0) {
             col = sky(d);  // TraceRay at depth >= maxRecursion (Scene.h:132-134)
+        } else if (kUni && cls != kTileGeneral) {  // uniform (cls is only set with max_rec > 0)
+            if constexpr (kUni)
+                col = pk_uniform_tile<MAXC, FEAT>(S, P, pk_img, cls, cam, d, ns, np, nl, bias, fix);
         } else {
             if (COUNT && valid) cnt.trace++;
             // (a lambda: the variants without a table compile to the code they had)

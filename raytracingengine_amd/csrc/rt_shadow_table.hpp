@@ -71,6 +71,11 @@ namespace rtamd {
 constexpr int kShadowTabLights = 4;
 constexpr int kShadowTabPlanes = 8;
 constexpr unsigned long long kShadowNoWord = ~0ull;
+// The tile class (tile_class_word, below): the relative margin of its plane ordering, and its
+// words — 0: the general path; 1: every ray of the tile misses everything; 2 + i: every ray's
+// closest hit is plane i, and no shadow ray of the tile can meet a sphere.
+constexpr double kClassMargin = 1e-6;
+constexpr unsigned long long kTileGeneral = 0ull, kTileSky = 1ull, kTilePlane0 = 2ull;
 
 // Lights per tile a scene's table holds (0: no shadow table for this scene).
 RT_CT_HD inline int shadow_table_lights(int ns, int np, int nl, bool area_light) {
@@ -82,7 +87,9 @@ RT_CT_HD inline int shadow_table_lights(int ns, int np, int nl, bool area_light)
 
 struct ShadowBall {
     double c[3];
-    float R;  // holds every shadow origin of the tile on its plane (bias included)
+    float R;     // holds every shadow origin of the tile on its plane (bias included)
+    int plane;   // the kept plane's index in `planes`
+    bool lead;   // ahead of every other always-hit plane by kClassMargin (tile_class_word)
 };
 template <int kMaxPlanes = kShadowTabPlanes>
 struct ShadowBound {
@@ -175,6 +182,21 @@ RT_CT_HD inline ShadowBound<kMaxPlanes> shadow_tile_bound(const ConeRect& q, dou
         }
         if (hidden) continue;
         ShadowBall& S = B.ball[B.n];
+        S.plane = j;
+        // the tile class's own ordering test (tile_class_word): g_j ≥ g_i·(1 + kClassMargin) at
+        // every corner, for every other always-hit plane i, decided by j itself
+        S.lead = true;
+    RT_ST_UNROLL
+        for (int i = 0; i < kMaxPlanes; ++i) {
+            if (i >= np) break;
+            if (i == j || !hit[i]) continue;
+            int ahead = 0;
+            for (int k = 0; k < kHideCorners; ++k) {
+                const double lhs = e[j][k] * an[i], rhs = e[i][k] * an[j];
+                ahead += lhs >= rhs * (1.0 + kClassMargin) && rhs >= 0x1p-900;
+            }
+            S.lead = S.lead && ahead == kHideCorners;
+        }
         double h[4][3];
         S.c[0] = S.c[1] = S.c[2] = 0.0;
         // t_k = num / n·v_k through ONE division: an · Π_{m≠k} e_m / Π e_m (each factor in
@@ -274,6 +296,46 @@ RT_CT_HD inline unsigned long long shadow_tile_word(const ShadowBound<kMaxPlanes
                 m |= 1ull << i;
     }
     return m;
+}
+
+// The tile's class word (packet_direct_kernel's uniform path, rt_packet_kernel.hpp).  A tile is
+// *uniform* when its cone mask is empty (no camera ray meets a sphere), shadow_tile_bound decided
+// every plane (ok) and kept at most one, every light's shadow word is 0 (no shadow ray of the tile
+// can meet a sphere: a word is a superset of the spheres any of them meets), nl ≤
+// kShadowTabLights, and — with a kept plane — the packet image holds that plane's oriented unit
+// normal (pln[4i + 3] ≠ 0: s_pln of pk_build_image) and the plane leads.
+//
+// What the class claims.  Sky (no kept plane): every plane is "never hit", so plane_t /
+// plane_t_core reject each for every ray of the tile and IntersectClosest misses.  Plane i: it is
+// "always hit" (t > 0, |n·d| > 1e-6 as the kernel computes it), every other plane is never hit
+// or an always-hit plane j with g_i ≥ g_j·(1 + kClassMargin) at the four corners.  g_i − (1 + m)·g_j
+// is linear in v, so the inequality holds exactly over the rectangle up to the corners' rounding:
+// each e[·][k] = n·v_k carries ≤ 3ε·Σ|n_a v_a| ≤ 3ε·2√3·|v| of error against |n·v| ≥ 2e-6·|v|,
+// 6e-10 relative, twice (i and j); the kernel's t = num / (n·d) has the image's own num (the one
+// read here) and a denominator within 5ε·|n|₁ ≤ 1.1e-15 of the exact n·v/|v| (three products,
+// two sums, d's components within 2ε), 5.5e-10 relative at |n·d| ≥ 2e-6, twice; the products and
+// the quotients add 4ε.  Together < 2.4e-9, so with m = 1e-6 (430× that; the shadow words' 1e-9
+// rule is left as it is — a plane it hides wrongly costs candidates there, a wrong t here) the
+// kernel's computed t_i < t_j for every ray, and its in-order loop with strict '<' (plane_t's
+// no-win skip needs t ≥ best·(1 − 2^-40)) ends on plane i with the bits of num_i / (n_i·d).
+// The margin only costs tiles within 1e-6 of two planes' line of intersection, which straddle it.
+//
+// kClassPlanes and kIndexOff exist for the host test's mutants only (the class taken on two kept
+// planes, without the ordering; the kept plane's index off by one).
+template <int kMaxPlanes, int kClassPlanes = 1, int kIndexOff = 0>
+RT_CT_HD inline unsigned long long tile_class_word(unsigned long long cone,
+                                                   const ShadowBound<kMaxPlanes>& B,
+                                                   const unsigned long long* words, int nl,
+                                                   const double* pln, int np) {
+    if (cone != 0 || !B.ok || B.n > kClassPlanes || nl < 1 || nl > kShadowTabLights)
+        return kTileGeneral;
+    for (int l = 0; l < nl; ++l)
+        if (words[l] != 0) return kTileGeneral;
+    if (B.n == 0) return kTileSky;
+    const int i = B.ball[0].plane;
+    if (kClassPlanes == 1 && !B.ball[0].lead) return kTileGeneral;
+    if (i < 0 || i >= np || !(pln[4 * i + 3] != 0.0)) return kTileGeneral;
+    return kTilePlane0 + static_cast<unsigned long long>((i + kIndexOff) % np);
 }
 
 }  // namespace rtamd
