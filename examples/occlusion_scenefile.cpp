@@ -1,0 +1,60 @@
+// examples/occlusion_scenefile.cpp — occlusion queries on a scene file (raytracingengine_amd/
+// scene.py format) through the drop-in C++ API, dumped raw for the parity tests
+// (tests/test_gpu_occlusion.py):
+//   rays.f64   n rays, six doubles each {ox, oy, oz, dx, dy, dz}
+//   dist.f64   n distances
+//   -> batch.u8    Scene::IntersectAnyBefore(rays, maxDist): one launch on the GPU
+//   -> single.u8   Scene::IntersectAnyBefore(ray, maxDist) per ray: the host utility
+// one byte per ray, 1 = something lies at 0 < t < maxDist.
+#include <fstream>
+#include <iostream>
+#include <iterator>
+#include <string>
+#include <vector>
+
+#include "Scene.h"
+#include "rtamd/scenefile.hpp"
+
+static std::vector<double> load(const std::string& path) {
+    std::ifstream f(path, std::ios::binary);
+    if (!f) throw std::runtime_error("cannot open " + path);
+    const std::vector<char> raw((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
+    if (raw.size() % sizeof(double)) throw std::runtime_error(path + ": not a file of doubles");
+    std::vector<double> v(raw.size() / sizeof(double));
+    std::copy(raw.begin(), raw.end(), reinterpret_cast<char*>(v.data()));
+    return v;
+}
+
+static void dump(const std::string& path, const std::vector<uint8_t>& v) {
+    std::ofstream f(path, std::ios::binary);
+    f.write(reinterpret_cast<const char*>(v.data()), static_cast<std::streamsize>(v.size()));
+}
+
+int main(int argc, char** argv) {
+    if (argc < 5) {
+        std::cerr << "usage: occlusion_scenefile <scene.txt> <rays.f64> <dist.f64> <outdir>\n";
+        return 2;
+    }
+    const std::string out = argv[4];
+    try {
+        const rtamd::LoadedScene L = rtamd::load_scene_file(argv[1]);
+        const Scene scene = L.build();
+        const std::vector<double> r = load(argv[2]), dist = load(argv[3]);
+        if (r.size() != 6 * dist.size())
+            throw std::runtime_error("six doubles per ray and one distance per ray expected");
+        std::vector<Rayon> rays;
+        rays.reserve(dist.size());
+        for (size_t i = 0; i < dist.size(); ++i)
+            rays.emplace_back(Vec3(r[6 * i], r[6 * i + 1], r[6 * i + 2]),
+                              Vec3(r[6 * i + 3], r[6 * i + 4], r[6 * i + 5]));
+        dump(out + "/batch.u8", scene.IntersectAnyBefore(rays, dist));
+        std::vector<uint8_t> single(rays.size());
+        for (size_t i = 0; i < rays.size(); ++i)
+            single[i] = scene.IntersectAnyBefore(rays[i], dist[i]) ? 1 : 0;
+        dump(out + "/single.u8", single);
+    } catch (const std::exception& e) {
+        std::cerr << "error: " << e.what() << "\n";
+        return 1;
+    }
+    return 0;
+}

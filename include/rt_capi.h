@@ -10,6 +10,9 @@
  *                                  (per pixel: GeneratePixelAt Scene.h:283-304 → TraceRay Scene.h:131-198
  *                                   → IntersectClosest Scene.h:218-257, directLightning Scene.h:79-129,
  *                                   computeTransmittance Scene.h:35-77, backgroundColor Scene.h:30-33)
+ *   rt_occluded_rays[_device]      bool Scene::IntersectAnyBefore(ray, maxDist) const   Scene.h:259-276
+ *                                  (per shape: Sphere::Intersect Shape.h:72-98, Plane::Intersect
+ *                                   Shape.h:149-159, Triangle::Intersect Shape.h:202-220)
  *   rt_tonemap                     tonemap() RaytracingEngine.cpp:165-174 and the operators of
  *                                  tonemapAll() RaytracingEngine.cpp:176-214, each followed by
  *                                  toColor() RaytracingEngine.cpp:113-121
@@ -437,6 +440,24 @@ rt_status rt_trace_rays(rt_context* ctx, const rt_scene* scene, const rt_render_
  * 2 plane, 3 triangle (index into rt_scene_desc.triangles). */
 rt_status rt_intersect_rays(rt_context* ctx, const rt_scene* scene, const double* rays,
                             size_t n, double* hits_out);
+
+/* Batch Scene::IntersectAnyBefore (Scene.h:259-276) for n host rays {ox,oy,oz,dx,dy,dz} and n
+ * distances: occluded_out[i] is 1 when some primitive's Intersect(ray i) returns a t with
+ * t > 0.0 && t < max_dist[i], else 0 — the reference's `within`, each t in binary64 in the
+ * reference's operation order, so there is no tolerance.  A Model counts through its flattened
+ * triangles (its Intersect reports their smallest t).  max_dist NaN or <= 0 gives 0, +inf means
+ * any hit with t > 0; a plane met at exactly t == 0 does not count (and does not hide an
+ * occluder further along, as a closest hit compared with max_dist would); an empty scene gives
+ * 0.  Lights, materials and the area light are not read.  opts may be NULL; only
+ * RT_FLAG_NO_BVH is read.  n == 0 returns RT_OK. */
+rt_status rt_occluded_rays(rt_context* ctx, const rt_scene* scene, const rt_render_opts* opts,
+                           const double* rays, const double* max_dist, size_t n,
+                           uint8_t* occluded_out);
+/* The same on device pointers (d_rays: n*6 doubles, d_max_dist: n doubles, d_occluded: n
+ * bytes), asynchronous on the context's stream. */
+rt_status rt_occluded_rays_device(rt_context* ctx, const rt_scene* scene,
+                                  const rt_render_opts* opts, const void* d_rays,
+                                  const void* d_max_dist, size_t n, void* d_occluded);
 
 /* Device tonemap of host FP64 radiance: op in [0, RT_TONEMAP_COUNT) writes n*3 bytes;
  * op == RT_TONEMAP_COUNT writes all seven operators, tonemapAll() order, 7*n*3 bytes. */

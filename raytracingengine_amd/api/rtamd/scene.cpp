@@ -300,6 +300,27 @@ bool Scene::IntersectAnyBefore(const Rayon& ray, double maxDist) const {
     return false;
 }
 
+std::vector<uint8_t> Scene::IntersectAnyBefore(const std::vector<Rayon>& rays,
+                                               const std::vector<double>& maxDist) const {
+    if (maxDist.size() != rays.size())
+        throw std::invalid_argument("IntersectAnyBefore: one maxDist per ray");
+    std::vector<uint8_t> out(rays.size());
+    if (rays.empty()) return out;
+    rt_scene* sc = upload();
+    // Rayon is two Vec3 of three packed doubles: the {ox,oy,oz,dx,dy,dz} records of the C-ABI
+    static_assert(sizeof(Rayon) == 6 * sizeof(double), "Rayon is not six packed doubles");
+    rtamd::check(rt_occluded_rays(dev_->ctx, sc, nullptr,
+                                  reinterpret_cast<const double*>(rays.data()), maxDist.data(),
+                                  rays.size(), out.data()),
+                 "rt_occluded_rays");
+    return out;
+}
+
+std::vector<uint8_t> Scene::IntersectAnyBefore(const std::vector<Rayon>& rays,
+                                               double maxDist) const {
+    return IntersectAnyBefore(rays, std::vector<double>(rays.size(), maxDist));
+}
+
 std::optional<HitInfo> Scene::CalculatePixelDepth(size_t x, size_t y, bool aa) const {
     return IntersectClosest(camera.getRay(x, y, aa));
 }

@@ -8,8 +8,11 @@
 //   IntersectClosest(ray)    → rt_intersect_rays         (Scene.h:218-257)
 //   CalculatePixelDepth(..)  → rt_intersect_rays         (Scene.h:278-281)
 //   RenderGBuffer()          → rt_gbuffer (extension: CalculatePixelDepth of every pixel)
-// IntersectAnyBefore (Scene.h:259-276, unused by the reference) is a host utility over the
-// shapes' Intersect members.  Failures throw std::runtime_error(rt_last_error()).
+//   IntersectAnyBefore(rays, maxDist) → rt_occluded_rays  (Scene.h:259-276, for n rays at once)
+// The single-ray IntersectAnyBefore(ray, maxDist) of the reference's signature stays a host
+// utility over the shapes' Intersect members: one ray per launch would pay an upload, a launch
+// and a download to learn one bit; the batch overloads give the same answers for many rays.
+// Failures throw std::runtime_error(rt_last_error()).
 //
 // The Add* methods take `const T&` — a compatible superset of the reference's `T&`.
 #pragma once
@@ -102,6 +105,13 @@ public:
     // CalculatePixelDepth(x, y, false) for every pixel in one launch (rt_gbuffer): depth,
     // normalised depth, normal, primitive and base colour maps; `outputs` is a set of RT_GB_* bits.
     rtamd::GBuffer RenderGBuffer(int outputs = RT_GB_ALL) const;
+    // IntersectAnyBefore(rays[i], maxDist[i]) for every ray in one launch (rt_occluded_rays):
+    // 1 or 0 per ray, the answers of the single-ray method above.  maxDist must hold one
+    // distance per ray (std::invalid_argument otherwise); the second overload uses one distance
+    // for all rays.
+    std::vector<uint8_t> IntersectAnyBefore(const std::vector<Rayon>& rays,
+                                            const std::vector<double>& maxDist) const;
+    std::vector<uint8_t> IntersectAnyBefore(const std::vector<Rayon>& rays, double maxDist) const;
     void SetDevice(int device) { device_ = device; dev_.reset(); devices_.clear(); }
     // RenderImage / RenderImageTonemapped / RenderImageF32 over several GPUs of the node from
     // this process: one scene copy per GPU, block-cyclic rows, assembled on the host (distinct

@@ -63,6 +63,7 @@ EXPORTED = [
     "rt_debug_cone_table",
     "rt_debug_shadow_table",
     "rt_debug_tile_class",
+    "rt_occluded_rays", "rt_occluded_rays_device",
 ]
 
 
@@ -165,6 +166,8 @@ def load_library(path: str = LIB_PATH):
         "rt_stats_reset": [vp],
         "rt_trace_rays": [vp, vp, vp, vp, ctypes.c_size_t, vp, vp],
         "rt_intersect_rays": [vp, vp, vp, ctypes.c_size_t, vp],
+        "rt_occluded_rays": [vp, vp, vp, vp, vp, ctypes.c_size_t, vp],
+        "rt_occluded_rays_device": [vp, vp, vp, vp, vp, ctypes.c_size_t, vp],
         "rt_tonemap": [vp, vp, ctypes.c_size_t, i32, vp],
         "rt_debug_f64_ops": [vp, vp, vp, ctypes.c_size_t, vp],
         "rt_debug_vec_ops": [vp, vp, ctypes.c_size_t, vp],
@@ -429,6 +432,49 @@ class DeviceScene:
         out = np.empty((rays.shape[0], 9), np.float64)
         _check(_lib.rt_intersect_rays(self.ctx.handle, self._h, rays.ctypes.data, rays.shape[0],
                                       out.ctypes.data))
+        return out
+
+    def occluded(self, rays: np.ndarray, max_dist, no_bvh: bool = False) -> np.ndarray:
+        """Batch IntersectAnyBefore (rt_occluded_rays): rays [n,6] and max_dist (a scalar, or
+        one distance per ray) -> bool [n], True where a primitive lies at 0 < t < max_dist."""
+        rays = np.ascontiguousarray(rays, np.float64).reshape(-1, 6)
+        n = rays.shape[0]
+        dist = np.ascontiguousarray(np.broadcast_to(np.asarray(max_dist, np.float64), (n,)))
+        out = np.empty(n, np.uint8)
+        o = default_opts(flags=RT_FLAG_NO_BVH if no_bvh else 0)
+        _check(_lib.rt_occluded_rays(self.ctx.handle, self._h, ctypes.byref(o), rays.ctypes.data,
+                                     dist.ctypes.data, n, out.ctypes.data))
+        return out.view(np.bool_)
+
+    def occluded_device(self, rays, max_dist, out=None, no_bvh: bool = False):
+        """Asynchronous IntersectAnyBefore on torch device tensors (rt_occluded_rays_device), on
+        the context's stream: rays float64 [n,6] and max_dist float64 [n] (or a scalar, expanded
+        on the device), contiguous, on this context's device.  Returns `out`, a uint8 [n] tensor
+        of 0 / 1 (made when None); it is written when the context's stream reaches the launch."""
+        import torch
+        dev = torch.device(f"cuda:{self.ctx.device}")
+        if rays.dtype != torch.float64 or rays.device != dev or not rays.is_contiguous():
+            raise ValueError("rays: a contiguous float64 tensor on the context's device")
+        n = rays.numel() // 6
+        if rays.numel() != 6 * n:
+            raise ValueError("rays: n*6 elements")
+        if not torch.is_tensor(max_dist):
+            max_dist = torch.full((n,), float(max_dist), dtype=torch.float64, device=dev)
+            # filled on torch's current stream, read on the context's
+            torch.cuda.current_stream(dev).synchronize()
+        if (max_dist.dtype != torch.float64 or max_dist.device != dev or max_dist.numel() != n
+                or not max_dist.is_contiguous()):
+            raise ValueError("max_dist: a scalar or a contiguous float64 [n] tensor on the device")
+        if out is None:
+            out = torch.empty(n, dtype=torch.uint8, device=dev)
+        elif (out.dtype != torch.uint8 or out.device != dev or out.numel() < n
+              or not out.is_contiguous()):
+            raise ValueError("out: a contiguous uint8 tensor of at least n elements on the device")
+        o = default_opts(flags=RT_FLAG_NO_BVH if no_bvh else 0)
+        _check(_lib.rt_occluded_rays_device(self.ctx.handle, self._h, ctypes.byref(o),
+                                            rays.data_ptr() if n else None,
+                                            max_dist.data_ptr() if n else None, n,
+                                            out.data_ptr() if n else None))
         return out
 
     def debug_tile_order(self):

@@ -1062,6 +1062,60 @@ rt_status rt_intersect_rays(rt_context* ctx, const rt_scene* sc, const double* r
     return RT_OK;
 }
 
+// The launch parameters of the any-hit query: the scene part of build_params; of opts only
+// RT_FLAG_NO_BVH is read (whatever else the caller left there must neither fail nor steer it).
+static rt_status occluded_params(rt_context* ctx, const rt_scene* sc, const rt_render_opts* opts,
+                                 TraceParams& p) {
+    const rt_camera cam = batch_camera();
+    rt_render_opts o;
+    rt_render_opts_default(&o);
+    if (opts) o.flags = opts->flags & RT_FLAG_NO_BVH;
+    int path;
+    bool lds;
+    size_t lds_bytes;
+    uint32_t rows;
+    return build_params(ctx, sc, &cam, &o, p, path, lds, lds_bytes, rows);
+}
+
+rt_status rt_occluded_rays_device(rt_context* ctx, const rt_scene* sc, const rt_render_opts* opts,
+                                  const void* d_rays, const void* d_max_dist, size_t n,
+                                  void* d_occluded) {
+    if (!ctx || (n && (!d_rays || !d_max_dist || !d_occluded)))
+        return fail(RT_ERR_INVALID_ARG, "NULL argument to rt_occluded_rays_device");
+    DeviceGuard g(ctx->device);
+    TraceParams p;
+    rt_status st = occluded_params(ctx, sc, opts, p);
+    if (st != RT_OK) return st;
+    if (n == 0) return RT_OK;
+    RT_HIP(launch_occluded_rays(p, static_cast<const double*>(d_rays),
+                                static_cast<const double*>(d_max_dist), n,
+                                static_cast<uint8_t*>(d_occluded), ctx->stream));
+    return RT_OK;
+}
+
+rt_status rt_occluded_rays(rt_context* ctx, const rt_scene* sc, const rt_render_opts* opts,
+                           const double* rays, const double* max_dist, size_t n,
+                           uint8_t* occluded_out) {
+    if (!ctx || (n && (!rays || !max_dist || !occluded_out)))
+        return fail(RT_ERR_INVALID_ARG, "NULL argument to rt_occluded_rays");
+    DeviceGuard g(ctx->device);
+    TraceParams p;
+    rt_status st = occluded_params(ctx, sc, opts, p);
+    if (st != RT_OK) return st;
+    if (n == 0) return RT_OK;
+    // ctx->rays: n rays (6 doubles), n distances, n answer bytes
+    RT_HIP(ctx->rays.ensure(n * 7 * sizeof(double) + n));
+    double* d_rays = static_cast<double*>(ctx->rays.ptr);
+    double* d_dist = d_rays + 6 * n;
+    uint8_t* d_out = reinterpret_cast<uint8_t*>(d_dist + n);
+    RT_HIP(hipMemcpyAsync(d_rays, rays, n * 6 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    RT_HIP(hipMemcpyAsync(d_dist, max_dist, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    RT_HIP(launch_occluded_rays(p, d_rays, d_dist, n, d_out, ctx->stream));
+    RT_HIP(hipMemcpyAsync(occluded_out, d_out, n, hipMemcpyDeviceToHost, ctx->stream));
+    RT_HIP(hipStreamSynchronize(ctx->stream));
+    return RT_OK;
+}
+
 rt_status rt_tonemap(rt_context* ctx, const double* hdr, size_t n, int op, uint8_t* out) {
     if (!ctx || (!hdr && n) || (!out && n))
         return fail(RT_ERR_INVALID_ARG, "NULL argument to rt_tonemap");

@@ -261,6 +261,9 @@ hipError_t launch_trace_rays(const TraceParams& p, int path, bool count, const d
                              size_t n, double* out, hipStream_t stream);
 hipError_t launch_intersect_rays(const TraceParams& p, const double* rays, size_t n, double* out,
                                  hipStream_t stream);
+// Any-hit query (rt_anyhit.hip): per ray, 1 iff a primitive lies at 0 < t < max_dist[i].
+hipError_t launch_occluded_rays(const TraceParams& p, const double* rays, const double* max_dist,
+                                size_t n, uint8_t* out, hipStream_t stream);
 hipError_t launch_tonemap(const double* hdr, size_t n, int op, uint8_t* out, hipStream_t stream);
 hipError_t launch_debug_f64(const double* x, const double* y, size_t n, double* out,
                             hipStream_t stream);
