@@ -13,6 +13,9 @@
  *   rt_occluded_rays[_device]      bool Scene::IntersectAnyBefore(ray, maxDist) const   Scene.h:259-276
  *                                  (per shape: Sphere::Intersect Shape.h:72-98, Plane::Intersect
  *                                   Shape.h:149-159, Triangle::Intersect Shape.h:202-220)
+ *   rt_transmittance_rays[_device] double Scene::computeTransmittance(ray, maxDist, bias) const   Scene.h:35-77
+ *                                  (private there; each step an IntersectClosest Scene.h:218-257)
+ *   rt_light_transmittance[_device] the shadow rays of Scene::directLightning   Scene.h:81, 86-104
  *   rt_tonemap                     tonemap() RaytracingEngine.cpp:165-174 and the operators of
  *                                  tonemapAll() RaytracingEngine.cpp:176-214, each followed by
  *                                  toColor() RaytracingEngine.cpp:113-121
@@ -458,6 +461,56 @@ rt_status rt_occluded_rays(rt_context* ctx, const rt_scene* scene, const rt_rend
 rt_status rt_occluded_rays_device(rt_context* ctx, const rt_scene* scene,
                                   const rt_render_opts* opts, const void* d_rays,
                                   const void* d_max_dist, size_t n, void* d_occluded);
+
+/* Batch Scene::computeTransmittance (Scene.h:35-77) for n host rays {ox,oy,oz,dx,dy,dz} and n
+ * distances: T_out[i] in [0,1] is the value computeTransmittance(ray i, max_dist[i], opts->bias)
+ * returns — a closest-hit march of at most 64 steps that multiplies the transparencies of what it
+ * crosses before max_dist, each clamped to [0,1] (Scene.h:68).  Every t is binary64 in the
+ * reference's operation order and ties go to the lowest scene index, as IntersectClosest decides
+ * them, so there is no tolerance.  Materials are read for `transparency` only; lights and the
+ * area light are not read.
+ *   - max_dist NaN or <= 0 gives 1.0 (the loop is never entered); an empty scene gives 1.0.
+ *   - max_dist +inf marches until a miss, until T <= 1e-4, or until the 64-step counter runs out:
+ *     what lies beyond the 64th step is not seen.
+ *   - A hit at t <= 0 moves the origin by bias, one at t <= bias by t + bias; neither is counted.
+ *     A counted hit needs traveled + t < max_dist (not t < max_dist, and glass is not opaque:
+ *     this is not rt_occluded_rays).
+ *   - The direction is not normalised: t, traveled, bias and max_dist are all in units of its
+ *     length, as in the reference.
+ * Of opts only bias and RT_FLAG_NO_BVH are read — whatever else the caller left there neither
+ * fails nor steers the call; opts == NULL gives the defaults (bias 1e-3).  n == 0 returns RT_OK.
+ * Synchronous. */
+rt_status rt_transmittance_rays(rt_context* ctx, const rt_scene* scene, const rt_render_opts* opts,
+                                const double* rays, const double* max_dist, size_t n,
+                                double* T_out);
+/* The same on device pointers (d_rays: n*6 doubles, d_max_dist: n doubles, d_T: n doubles),
+ * asynchronous on the context's stream; no host memory is touched. */
+rt_status rt_transmittance_rays_device(rt_context* ctx, const rt_scene* scene,
+                                       const rt_render_opts* opts, const void* d_rays,
+                                       const void* d_max_dist, size_t n, void* d_T);
+
+/* The shadow rays of Scene::directLightning (Scene.h:86-104) from n surface points to every
+ * point light of the scene.  points: n*6 doubles {p.xyz, normal.xyz}; T_out: n*n_lights doubles,
+ * [i*n_lights + l].  For point i = {p, n_in} and light l, in this order (Scene.h:81, 87-104):
+ *   1. normal = n_in.normalize() (Vec3::normalize: a length <= 1e-12 gives the zero vector);
+ *   2. v = light.position - p;
+ *   3. dist = v.length(); the answer is 0.0 if dist <= 0;
+ *   4. L = v / dist;
+ *   5. the answer is 0.0 if max(0, normal·L) <= 0;
+ *   6. the answer is 0.0 if dist <= bias;
+ *   7. otherwise it is computeTransmittance({p + normal*bias, L}, dist - bias, bias).
+ * The three zeros are the reference's `continue`s: that light adds nothing at that point.  The
+ * raw T is returned; dropping T <= bias (Scene.h:105) is the shader's decision, not the query's.
+ * The caller passes the normal facing the viewer, as TraceRay flips it (Scene.h:146).  Only
+ * point lights are served, not the build-defined area light.  A scene without lights returns
+ * RT_OK and writes nothing.  opts as for rt_transmittance_rays.  Synchronous. */
+rt_status rt_light_transmittance(rt_context* ctx, const rt_scene* scene, const rt_render_opts* opts,
+                                 const double* points, size_t n, double* T_out);
+/* The same on device pointers (d_points: n*6 doubles, d_T: n*n_lights doubles), asynchronous on
+ * the context's stream; no host memory is touched. */
+rt_status rt_light_transmittance_device(rt_context* ctx, const rt_scene* scene,
+                                        const rt_render_opts* opts, const void* d_points, size_t n,
+                                        void* d_T);
 
 /* Device tonemap of host FP64 radiance: op in [0, RT_TONEMAP_COUNT) writes n*3 bytes;
  * op == RT_TONEMAP_COUNT writes all seven operators, tonemapAll() order, 7*n*3 bytes. */

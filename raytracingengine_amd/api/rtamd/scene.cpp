@@ -1,6 +1,7 @@
 // rtamd/scene.cpp — Scene methods over the C-ABI (see scene.hpp for the mapping).
 #include "rtamd/scene.hpp"
 
+#include <algorithm>
 #include <cstring>
 #include <map>
 #include <stdexcept>
@@ -319,6 +320,88 @@ std::vector<uint8_t> Scene::IntersectAnyBefore(const std::vector<Rayon>& rays,
 std::vector<uint8_t> Scene::IntersectAnyBefore(const std::vector<Rayon>& rays,
                                                double maxDist) const {
     return IntersectAnyBefore(rays, std::vector<double>(rays.size(), maxDist));
+}
+
+double Scene::ComputeTransmittance(const Rayon& ray, double maxDist, double bias) const {
+    // the closest hit of IntersectClosest's visiting order (spheres, planes, triangles, models;
+    // a later shape wins only when strictly closer), kept as its distance and transparency
+    auto closest = [&](const Rayon& r, double& t, double& transparency) {
+        bool found = false;
+        auto offer = [&](const std::optional<double>& d, const Material& m) {
+            if (d && (!found || *d < t)) {
+                found = true;
+                t = *d;
+                transparency = m.transparency;
+            }
+        };
+        for (const auto& s : spheres) offer(s.Intersect(r), s.getMaterial());
+        for (const auto& p : planes) offer(p.Intersect(r), p.GetMaterial());
+        for (const auto& tr : triangles) offer(tr.Intersect(r), tr.GetMaterial());
+        for (const auto& m : models) offer(m.Intersect(r), m.GetMaterial());
+        return found;
+    };
+    double T = 1.0, traveled = 0.0;
+    Rayon r = ray;
+    for (int step = 0; step < 64 && T > 1e-4 && traveled < maxDist; ++step) {
+        double t = 0.0, transparency = 0.0;
+        if (!closest(r, t, transparency)) break;
+        if (t <= 0.0) {  // a plane under the origin: step off it, nothing is counted
+            r.origin = r.origin + r.direction * bias;
+            traveled += bias;
+            continue;
+        }
+        if (!(t <= bias)) {  // a hit within the bias is stepped over uncounted too
+            if (traveled + t >= maxDist) break;
+            T *= std::clamp(transparency, 0.0, 1.0);
+        }
+        r.origin = r.pointAtDistance(t) + r.direction * bias;
+        traveled += t + bias;
+    }
+    return std::clamp(T, 0.0, 1.0);
+}
+
+std::vector<double> Scene::ComputeTransmittance(const std::vector<Rayon>& rays,
+                                                const std::vector<double>& maxDist,
+                                                double bias) const {
+    if (maxDist.size() != rays.size())
+        throw std::invalid_argument("ComputeTransmittance: one maxDist per ray");
+    std::vector<double> out(rays.size());
+    if (rays.empty()) return out;
+    rt_scene* sc = upload();
+    static_assert(sizeof(Rayon) == 6 * sizeof(double), "Rayon is not six packed doubles");
+    rt_render_opts o = optsDesc(RT_TONEMAP_NONE);
+    o.bias = bias;
+    rtamd::check(rt_transmittance_rays(dev_->ctx, sc, &o,
+                                       reinterpret_cast<const double*>(rays.data()),
+                                       maxDist.data(), rays.size(), out.data()),
+                 "rt_transmittance_rays");
+    return out;
+}
+
+std::vector<double> Scene::ComputeTransmittance(const std::vector<Rayon>& rays, double maxDist,
+                                                double bias) const {
+    return ComputeTransmittance(rays, std::vector<double>(rays.size(), maxDist), bias);
+}
+
+std::vector<double> Scene::LightTransmittance(const std::vector<Vec3>& points,
+                                              const std::vector<Vec3>& normals,
+                                              double bias) const {
+    if (normals.size() != points.size())
+        throw std::invalid_argument("LightTransmittance: one normal per point");
+    std::vector<double> out(points.size() * lights.size());
+    if (out.empty()) return out;
+    rt_scene* sc = upload();
+    std::vector<double> pn(6 * points.size());
+    for (size_t i = 0; i < points.size(); ++i) {
+        const double rec[6] = {points[i].x, points[i].y, points[i].z,
+                               normals[i].x, normals[i].y, normals[i].z};
+        std::copy(rec, rec + 6, pn.begin() + 6 * i);
+    }
+    rt_render_opts o = optsDesc(RT_TONEMAP_NONE);
+    o.bias = bias;
+    rtamd::check(rt_light_transmittance(dev_->ctx, sc, &o, pn.data(), points.size(), out.data()),
+                 "rt_light_transmittance");
+    return out;
 }
 
 std::optional<HitInfo> Scene::CalculatePixelDepth(size_t x, size_t y, bool aa) const {

@@ -9,9 +9,13 @@
 //   CalculatePixelDepth(..)  → rt_intersect_rays         (Scene.h:278-281)
 //   RenderGBuffer()          → rt_gbuffer (extension: CalculatePixelDepth of every pixel)
 //   IntersectAnyBefore(rays, maxDist) → rt_occluded_rays  (Scene.h:259-276, for n rays at once)
+//   ComputeTransmittance(rays, maxDist, bias) → rt_transmittance_rays (Scene.h:35-77, private
+//                              in the reference, for n rays at once)
+//   LightTransmittance(points, normals, bias) → rt_light_transmittance (Scene.h:86-104)
 // The single-ray IntersectAnyBefore(ray, maxDist) of the reference's signature stays a host
 // utility over the shapes' Intersect members: one ray per launch would pay an upload, a launch
 // and a download to learn one bit; the batch overloads give the same answers for many rays.
+// The single-ray ComputeTransmittance(ray, maxDist, bias) is a host utility for the same reason.
 // Failures throw std::runtime_error(rt_last_error()).
 //
 // The Add* methods take `const T&` — a compatible superset of the reference's `T&`.
@@ -112,6 +116,24 @@ public:
     std::vector<uint8_t> IntersectAnyBefore(const std::vector<Rayon>& rays,
                                             const std::vector<double>& maxDist) const;
     std::vector<uint8_t> IntersectAnyBefore(const std::vector<Rayon>& rays, double maxDist) const;
+    // computeTransmittance(ray, maxDist, bias) (Scene.h:35-77, private in the reference): the
+    // transmittance in [0,1] along the ray up to maxDist — a closest-hit march of at most 64
+    // steps over the shapes' Intersect members on the host, the values of the batch overloads.
+    double ComputeTransmittance(const Rayon& ray, double maxDist, double bias = 1e-3) const;
+    // The same for every ray in one launch (rt_transmittance_rays).  maxDist must hold one
+    // distance per ray (std::invalid_argument otherwise); the second overload uses one distance
+    // for all rays.
+    std::vector<double> ComputeTransmittance(const std::vector<Rayon>& rays,
+                                             const std::vector<double>& maxDist,
+                                             double bias = 1e-3) const;
+    std::vector<double> ComputeTransmittance(const std::vector<Rayon>& rays, double maxDist,
+                                             double bias = 1e-3) const;
+    // directLightning's shadow rays (Scene.h:86-104) from every point to every point light in one
+    // launch (rt_light_transmittance): [i * lights + l], 0.0 where the reference skips the light.
+    // normals[i] faces the viewer; one normal per point (std::invalid_argument otherwise).
+    std::vector<double> LightTransmittance(const std::vector<Vec3>& points,
+                                           const std::vector<Vec3>& normals,
+                                           double bias = 1e-3) const;
     void SetDevice(int device) { device_ = device; dev_.reset(); devices_.clear(); }
     // RenderImage / RenderImageTonemapped / RenderImageF32 over several GPUs of the node from
     // this process: one scene copy per GPU, block-cyclic rows, assembled on the host (distinct

@@ -64,6 +64,8 @@ EXPORTED = [
     "rt_debug_shadow_table",
     "rt_debug_tile_class",
     "rt_occluded_rays", "rt_occluded_rays_device",
+    "rt_transmittance_rays", "rt_transmittance_rays_device",
+    "rt_light_transmittance", "rt_light_transmittance_device",
 ]
 
 
@@ -168,6 +170,10 @@ def load_library(path: str = LIB_PATH):
         "rt_intersect_rays": [vp, vp, vp, ctypes.c_size_t, vp],
         "rt_occluded_rays": [vp, vp, vp, vp, vp, ctypes.c_size_t, vp],
         "rt_occluded_rays_device": [vp, vp, vp, vp, vp, ctypes.c_size_t, vp],
+        "rt_transmittance_rays": [vp, vp, vp, vp, vp, ctypes.c_size_t, vp],
+        "rt_transmittance_rays_device": [vp, vp, vp, vp, vp, ctypes.c_size_t, vp],
+        "rt_light_transmittance": [vp, vp, vp, vp, ctypes.c_size_t, vp],
+        "rt_light_transmittance_device": [vp, vp, vp, vp, ctypes.c_size_t, vp],
         "rt_tonemap": [vp, vp, ctypes.c_size_t, i32, vp],
         "rt_debug_f64_ops": [vp, vp, vp, ctypes.c_size_t, vp],
         "rt_debug_vec_ops": [vp, vp, ctypes.c_size_t, vp],
@@ -475,6 +481,91 @@ class DeviceScene:
                                             rays.data_ptr() if n else None,
                                             max_dist.data_ptr() if n else None, n,
                                             out.data_ptr() if n else None))
+        return out
+
+    def transmittance(self, rays: np.ndarray, max_dist, bias: float = 1e-3,
+                      no_bvh: bool = False) -> np.ndarray:
+        """Batch computeTransmittance (rt_transmittance_rays): rays [n,6] and max_dist (a scalar,
+        or one distance per ray) -> float64 [n], the transmittance in [0,1] up to max_dist."""
+        rays = np.ascontiguousarray(rays, np.float64).reshape(-1, 6)
+        n = rays.shape[0]
+        dist = np.ascontiguousarray(np.broadcast_to(np.asarray(max_dist, np.float64), (n,)))
+        out = np.empty(n, np.float64)
+        o = default_opts(bias=bias, flags=RT_FLAG_NO_BVH if no_bvh else 0)
+        _check(_lib.rt_transmittance_rays(self.ctx.handle, self._h, ctypes.byref(o),
+                                          rays.ctypes.data, dist.ctypes.data, n, out.ctypes.data))
+        return out
+
+    def transmittance_device(self, rays, max_dist, out=None, bias: float = 1e-3,
+                             no_bvh: bool = False):
+        """Asynchronous computeTransmittance on torch device tensors
+        (rt_transmittance_rays_device), on the context's stream: rays float64 [n,6] and max_dist
+        float64 [n] (or a scalar, expanded on the device), contiguous, on this context's device.
+        Returns `out`, a float64 [n] tensor (made when None); it is written when the context's
+        stream reaches the launch."""
+        import torch
+        dev = torch.device(f"cuda:{self.ctx.device}")
+        if rays.dtype != torch.float64 or rays.device != dev or not rays.is_contiguous():
+            raise ValueError("rays: a contiguous float64 tensor on the context's device")
+        n = rays.numel() // 6
+        if rays.numel() != 6 * n:
+            raise ValueError("rays: n*6 elements")
+        if not torch.is_tensor(max_dist):
+            max_dist = torch.full((n,), float(max_dist), dtype=torch.float64, device=dev)
+            # filled on torch's current stream, read on the context's
+            torch.cuda.current_stream(dev).synchronize()
+        if (max_dist.dtype != torch.float64 or max_dist.device != dev or max_dist.numel() != n
+                or not max_dist.is_contiguous()):
+            raise ValueError("max_dist: a scalar or a contiguous float64 [n] tensor on the device")
+        if out is None:
+            out = torch.empty(n, dtype=torch.float64, device=dev)
+        elif (out.dtype != torch.float64 or out.device != dev or out.numel() < n
+              or not out.is_contiguous()):
+            raise ValueError("out: a contiguous float64 tensor of at least n elements on the device")
+        o = default_opts(bias=bias, flags=RT_FLAG_NO_BVH if no_bvh else 0)
+        _check(_lib.rt_transmittance_rays_device(self.ctx.handle, self._h, ctypes.byref(o),
+                                                 rays.data_ptr() if n else None,
+                                                 max_dist.data_ptr() if n else None, n,
+                                                 out.data_ptr() if n else None))
+        return out
+
+    def light_transmittance(self, points: np.ndarray, bias: float = 1e-3,
+                            no_bvh: bool = False) -> np.ndarray:
+        """directLightning's shadow rays (rt_light_transmittance): points [n,6] {p, normal}, the
+        normal facing the viewer -> float64 [n, n_lights], the transmittance from each point to
+        each point light (0.0 where the reference skips the light)."""
+        points = np.ascontiguousarray(points, np.float64).reshape(-1, 6)
+        n, nl = points.shape[0], len(self._arrays[3])
+        out = np.empty((n, nl), np.float64)
+        o = default_opts(bias=bias, flags=RT_FLAG_NO_BVH if no_bvh else 0)
+        _check(_lib.rt_light_transmittance(self.ctx.handle, self._h, ctypes.byref(o),
+                                           points.ctypes.data if n else None, n,
+                                           out.ctypes.data if out.size else None))
+        return out
+
+    def light_transmittance_device(self, points, out=None, bias: float = 1e-3,
+                                   no_bvh: bool = False):
+        """Asynchronous rt_light_transmittance_device on the context's stream: points a
+        contiguous float64 [n,6] tensor on this context's device.  Returns `out`, a float64
+        [n, n_lights] tensor (made when None; a given one needs at least n*n_lights elements)."""
+        import torch
+        dev = torch.device(f"cuda:{self.ctx.device}")
+        if points.dtype != torch.float64 or points.device != dev or not points.is_contiguous():
+            raise ValueError("points: a contiguous float64 tensor on the context's device")
+        n = points.numel() // 6
+        if points.numel() != 6 * n:
+            raise ValueError("points: n*6 elements")
+        nl = len(self._arrays[3])
+        if out is None:
+            out = torch.empty((n, nl), dtype=torch.float64, device=dev)
+        elif (out.dtype != torch.float64 or out.device != dev or out.numel() < n * nl
+              or not out.is_contiguous()):
+            raise ValueError("out: a contiguous float64 tensor of at least n*n_lights elements "
+                             "on the device")
+        o = default_opts(bias=bias, flags=RT_FLAG_NO_BVH if no_bvh else 0)
+        _check(_lib.rt_light_transmittance_device(self.ctx.handle, self._h, ctypes.byref(o),
+                                                  points.data_ptr() if n else None, n,
+                                                  out.data_ptr() if n * nl else None))
         return out
 
     def debug_tile_order(self):

@@ -1116,6 +1116,114 @@ rt_status rt_occluded_rays(rt_context* ctx, const rt_scene* sc, const rt_render_
     return RT_OK;
 }
 
+// The launch parameters of the transmittance queries: the scene part of build_params; of opts
+// only bias and RT_FLAG_NO_BVH are read, as occluded_params reads its flag.  opaque: no material
+// is transparent — what selects the tree path — so the kernels' occlusion_opaque variant serves
+// the scene; RTAMD_TX_OPAQUE=0 (read per launch) sends it through the march alone (A/B, tests).
+static rt_status transmit_params(rt_context* ctx, const rt_scene* sc, const rt_render_opts* opts,
+                                 TraceParams& p, bool& opaque) {
+    const rt_camera cam = batch_camera();
+    rt_render_opts o;
+    rt_render_opts_default(&o);
+    if (opts) {
+        o.flags = opts->flags & RT_FLAG_NO_BVH;
+        o.bias = opts->bias;
+    }
+    int path;
+    bool lds;
+    size_t lds_bytes;
+    uint32_t rows;
+    rt_status st = build_params(ctx, sc, &cam, &o, p, path, lds, lds_bytes, rows);
+    if (st != RT_OK) return st;
+    const char* e = std::getenv("RTAMD_TX_OPAQUE");
+    opaque = !sc->any_transparent && !(e && std::atoi(e) == 0);
+    return RT_OK;
+}
+
+rt_status rt_transmittance_rays_device(rt_context* ctx, const rt_scene* sc,
+                                       const rt_render_opts* opts, const void* d_rays,
+                                       const void* d_max_dist, size_t n, void* d_T) {
+    if (!ctx || (n && (!d_rays || !d_max_dist || !d_T)))
+        return fail(RT_ERR_INVALID_ARG, "NULL argument to rt_transmittance_rays_device");
+    DeviceGuard g(ctx->device);
+    TraceParams p;
+    bool opaque;
+    rt_status st = transmit_params(ctx, sc, opts, p, opaque);
+    if (st != RT_OK) return st;
+    if (n == 0) return RT_OK;
+    RT_HIP(launch_transmittance_rays(p, opaque, static_cast<const double*>(d_rays),
+                                     static_cast<const double*>(d_max_dist), n,
+                                     static_cast<double*>(d_T), ctx->stream));
+    return RT_OK;
+}
+
+rt_status rt_transmittance_rays(rt_context* ctx, const rt_scene* sc, const rt_render_opts* opts,
+                                const double* rays, const double* max_dist, size_t n,
+                                double* T_out) {
+    if (!ctx || (n && (!rays || !max_dist || !T_out)))
+        return fail(RT_ERR_INVALID_ARG, "NULL argument to rt_transmittance_rays");
+    DeviceGuard g(ctx->device);
+    TraceParams p;
+    bool opaque;
+    rt_status st = transmit_params(ctx, sc, opts, p, opaque);
+    if (st != RT_OK) return st;
+    if (n == 0) return RT_OK;
+    // ctx->rays: n rays (6 doubles), n distances, n answers
+    RT_HIP(ctx->rays.ensure(n * 8 * sizeof(double)));
+    double* d_rays = static_cast<double*>(ctx->rays.ptr);
+    double* d_dist = d_rays + 6 * n;
+    double* d_out = d_dist + n;
+    RT_HIP(hipMemcpyAsync(d_rays, rays, n * 6 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    RT_HIP(hipMemcpyAsync(d_dist, max_dist, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    RT_HIP(launch_transmittance_rays(p, opaque, d_rays, d_dist, n, d_out, ctx->stream));
+    RT_HIP(hipMemcpyAsync(T_out, d_out, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    RT_HIP(hipStreamSynchronize(ctx->stream));
+    return RT_OK;
+}
+
+rt_status rt_light_transmittance_device(rt_context* ctx, const rt_scene* sc,
+                                        const rt_render_opts* opts, const void* d_points, size_t n,
+                                        void* d_T) {
+    if (!ctx || (n && !d_points))
+        return fail(RT_ERR_INVALID_ARG, "NULL argument to rt_light_transmittance_device");
+    DeviceGuard g(ctx->device);
+    TraceParams p;
+    bool opaque;
+    rt_status st = transmit_params(ctx, sc, opts, p, opaque);
+    if (st != RT_OK) return st;
+    if (n == 0 || p.nl == 0) return RT_OK;  // no lights: nothing is written
+    if (!d_T)  // with no lights there is no output to point to
+        return fail(RT_ERR_INVALID_ARG, "NULL argument to rt_light_transmittance_device");
+    RT_HIP(launch_light_transmittance(p, opaque, static_cast<const double*>(d_points), n,
+                                      static_cast<double*>(d_T), ctx->stream));
+    return RT_OK;
+}
+
+rt_status rt_light_transmittance(rt_context* ctx, const rt_scene* sc, const rt_render_opts* opts,
+                                 const double* points, size_t n, double* T_out) {
+    if (!ctx || (n && !points))
+        return fail(RT_ERR_INVALID_ARG, "NULL argument to rt_light_transmittance");
+    DeviceGuard g(ctx->device);
+    TraceParams p;
+    bool opaque;
+    rt_status st = transmit_params(ctx, sc, opts, p, opaque);
+    if (st != RT_OK) return st;
+    if (n == 0 || p.nl == 0) return RT_OK;  // no lights: nothing is written
+    if (!T_out)  // with no lights there is no output to point to
+        return fail(RT_ERR_INVALID_ARG, "NULL argument to rt_light_transmittance");
+    // ctx->rays: n points (6 doubles), n * nl answers
+    const size_t nl = static_cast<size_t>(p.nl);
+    RT_HIP(ctx->rays.ensure(n * (6 + nl) * sizeof(double)));
+    double* d_pts = static_cast<double*>(ctx->rays.ptr);
+    double* d_out = d_pts + 6 * n;
+    RT_HIP(hipMemcpyAsync(d_pts, points, n * 6 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    RT_HIP(launch_light_transmittance(p, opaque, d_pts, n, d_out, ctx->stream));
+    RT_HIP(hipMemcpyAsync(T_out, d_out, n * nl * sizeof(double), hipMemcpyDeviceToHost,
+                          ctx->stream));
+    RT_HIP(hipStreamSynchronize(ctx->stream));
+    return RT_OK;
+}
+
 rt_status rt_tonemap(rt_context* ctx, const double* hdr, size_t n, int op, uint8_t* out) {
     if (!ctx || (!hdr && n) || (!out && n))
         return fail(RT_ERR_INVALID_ARG, "NULL argument to rt_tonemap");

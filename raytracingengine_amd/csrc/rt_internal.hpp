@@ -264,6 +264,14 @@ hipError_t launch_intersect_rays(const TraceParams& p, const double* rays, size_
 // Any-hit query (rt_anyhit.hip): per ray, 1 iff a primitive lies at 0 < t < max_dist[i].
 hipError_t launch_occluded_rays(const TraceParams& p, const double* rays, const double* max_dist,
                                 size_t n, uint8_t* out, hipStream_t stream);
+// Transmittance queries (rt_transmit.hip): per ray, computeTransmittance(ray, max_dist[i], p.bias);
+// per point {p, normal} and point light l, directLightning's shadow ray, out[i * p.nl + l].
+// opaque: the scene has no transparent material (the variant that asks occlusion_opaque first).
+hipError_t launch_transmittance_rays(const TraceParams& p, bool opaque, const double* rays,
+                                     const double* max_dist, size_t n, double* out,
+                                     hipStream_t stream);
+hipError_t launch_light_transmittance(const TraceParams& p, bool opaque, const double* points,
+                                      size_t n, double* out, hipStream_t stream);
 hipError_t launch_tonemap(const double* hdr, size_t n, int op, uint8_t* out, hipStream_t stream);
 hipError_t launch_debug_f64(const double* x, const double* y, size_t n, double* out,
                             hipStream_t stream);
