@@ -16,6 +16,10 @@
  *   rt_transmittance_rays[_device] double Scene::computeTransmittance(ray, maxDist, bias) const   Scene.h:35-77
  *                                  (private there; each step an IntersectClosest Scene.h:218-257)
  *   rt_light_transmittance[_device] the shadow rays of Scene::directLightning   Scene.h:81, 86-104
+ *   rt_direct_light[_device]       Vec3 Scene::directLightning(hit, viewDir, normalIn, bias) const   Scene.h:79-129
+ *                                  (private there; over the point lights, for n surface points)
+ *   rt_direct_light_rays[_device]  the localLight of Scene::TraceRay   Scene.h:136-147, 168
+ *                                  (IntersectClosest, the normal flip, then directLightning)
  *   rt_tonemap                     tonemap() RaytracingEngine.cpp:165-174 and the operators of
  *                                  tonemapAll() RaytracingEngine.cpp:176-214, each followed by
  *                                  toColor() RaytracingEngine.cpp:113-121
@@ -511,6 +515,73 @@ rt_status rt_light_transmittance(rt_context* ctx, const rt_scene* scene, const r
 rt_status rt_light_transmittance_device(rt_context* ctx, const rt_scene* scene,
                                         const rt_render_opts* opts, const void* d_points, size_t n,
                                         void* d_T);
+
+/* Batch Scene::directLightning (Scene.h:79-129) for n surface points the caller supplies.
+ * points: n*9 doubles {p.xyz, normal.xyz, view.xyz}.  `normal` faces the viewer, as TraceRay flips
+ * it (Scene.h:146), and is normalised by the query (Scene.h:81, Vec3::normalize: a length <= 1e-12
+ * gives the zero vector); `view` is viewDir (Scene.h:147) and is used as given, not normalised.
+ * materials: n_materials == n gives every point its own rt_material, n_materials == 1 one
+ * material shared by all points; any other count is RT_ERR_INVALID_ARG.
+ * Per point, over the scene's point lights in scene order (Scene.h:86-124):
+ *   1. v = light.position - p; dist = v.length(); the light is skipped if dist <= 0 (Scene.h:89);
+ *   2. L = v / dist; ndl = max(0, normal·L); skipped if ndl <= 0 (Scene.h:93) or dist <= bias
+ *      (Scene.h:98);
+ *   3. T = computeTransmittance({p + normal*bias, L}, dist - bias, bias); dropped if T <= bias
+ *      (Scene.h:105);
+ *   4. contribution = (emitted * (1.0 / (dist*dist))) * ndl with emitted = color * intensity;
+ *      diffuse += contribution * T (Scene.h:110-113);
+ *   5. only if material.transparency <= 0 and material.specular > 0: H = (L + view).normalize(),
+ *      NdotH = max(0, normal·H), and if NdotH > 0
+ *      specular += ((emitted * (1.0 / (dist*dist))) * pow(NdotH, shininess)) * T (Scene.h:115-123).
+ * Outputs, each n*3 doubles, chosen by the bits of `outputs`:
+ *   RT_DL_DIFFUSE / RT_DL_SPECULAR  the two accumulators after the last light;
+ *   RT_DL_RADIANCE                  color * diffuse + specular * material.specular (Scene.h:126-128),
+ *                                   directLightning's return value.
+ * Every operation is binary64 in the reference's order, so diffuse has no tolerance; where pow is
+ * reached, specular and radiance are within 1e-12 * max(1, |value|) of libm's.
+ * Only the scene's point lights are read, not the build-defined area light (the rule of
+ * rt_light_transmittance).  A scene without lights writes zeros: the outputs have a fixed shape.
+ * Of opts only bias and RT_FLAG_NO_BVH are read; opts == NULL gives the defaults (bias 1e-3).
+ * RT_ERR_INVALID_ARG: outputs == 0, an unknown bit in outputs, out NULL or a requested output's
+ * pointer NULL (pointers of outputs not requested are ignored), NULL inputs with n > 0.
+ * n == 0 returns RT_OK.  Synchronous. */
+#define RT_DL_RADIANCE 0x1  /* double [n][3]  directLightning's return value               */
+#define RT_DL_DIFFUSE  0x2  /* double [n][3]  diffuseAccumulation  (Scene.h:83, 113)        */
+#define RT_DL_SPECULAR 0x4  /* double [n][3]  specularAccumlation  (Scene.h:84, 121)        */
+#define RT_DL_ALL      0x7
+struct rt_direct_light_out {
+    void* radiance;
+    void* diffuse;
+    void* specular;
+};
+rt_status rt_direct_light(rt_context* ctx, const rt_scene* scene, const rt_render_opts* opts,
+                          const double* points, const rt_material* materials, size_t n_materials,
+                          size_t n, int outputs, const struct rt_direct_light_out* out);
+/* The same on device pointers (d_points: n*9 doubles, d_materials: n_materials*7 doubles, the
+ * members of d_out: n*3 doubles each), asynchronous on the context's stream.  With
+ * n_materials == n no host memory is touched; with n_materials == 1 d_materials is a HOST
+ * pointer to the one shared material, which travels in the kernel arguments. */
+rt_status rt_direct_light_device(rt_context* ctx, const rt_scene* scene,
+                                 const rt_render_opts* opts, const void* d_points,
+                                 const void* d_materials, size_t n_materials, size_t n,
+                                 int outputs, const struct rt_direct_light_out* d_out);
+
+/* The same shading at the first hit of n rays {ox,oy,oz,dx,dy,dz}: what TraceRay calls localLight
+ * (Scene.h:168) at recursion depth 0.  Per ray: IntersectClosest (Scene.h:218-257), hitPoint =
+ * o + d*t, incoming = d.normalize(), normal = hit.normal flipped against incoming
+ * (Scene.h:145-146), viewDir = -incoming, the hit primitive's material, then directLightning as
+ * above.  Every scene type is served: mirrors and glass too, whose child rays are simply not
+ * traced.  A ray that hits nothing writes +0.0 to every requested output; what was hit is
+ * rt_intersect_rays' or the G-buffer's answer.  outputs, out, opts and the errors as for
+ * rt_direct_light.  Synchronous. */
+rt_status rt_direct_light_rays(rt_context* ctx, const rt_scene* scene, const rt_render_opts* opts,
+                               const double* rays, size_t n, int outputs,
+                               const struct rt_direct_light_out* out);
+/* The same on device pointers (d_rays: n*6 doubles), asynchronous on the context's stream; no
+ * host memory is touched. */
+rt_status rt_direct_light_rays_device(rt_context* ctx, const rt_scene* scene,
+                                      const rt_render_opts* opts, const void* d_rays, size_t n,
+                                      int outputs, const struct rt_direct_light_out* d_out);
 
 /* Device tonemap of host FP64 radiance: op in [0, RT_TONEMAP_COUNT) writes n*3 bytes;
  * op == RT_TONEMAP_COUNT writes all seven operators, tonemapAll() order, 7*n*3 bytes. */

@@ -2,6 +2,7 @@
 #include "rtamd/scene.hpp"
 
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <map>
 #include <stdexcept>
@@ -402,6 +403,101 @@ std::vector<double> Scene::LightTransmittance(const std::vector<Vec3>& points,
     rtamd::check(rt_light_transmittance(dev_->ctx, sc, &o, pn.data(), points.size(), out.data()),
                  "rt_light_transmittance");
     return out;
+}
+
+std::optional<HitInfo> Scene::IntersectClosestHost(const Rayon& ray) const {
+    std::optional<HitInfo> best;
+    auto offer = [&](const std::optional<HitInfo>& h) {
+        if (h && (!best || h->isCloserThan(*best))) best = h;
+    };
+    for (size_t i = 0; i < spheres.size(); ++i) offer(spheres[i].GetHitInfoAt(ray, i));
+    for (size_t i = 0; i < planes.size(); ++i) offer(planes[i].GetHitInfoAt(ray, i));
+    for (size_t i = 0; i < triangles.size(); ++i) offer(triangles[i].GetHitInfoAt(ray, i));
+    for (size_t i = 0; i < models.size(); ++i) offer(models[i].GetHitInfoAt(ray, i));
+    return best;
+}
+
+Vec3 Scene::DirectLightning(const HitInfo& hit, const Vec3& viewDir, const Vec3& normalIn,
+                            double bias) const {
+    const Material& material = hit.material;
+    const Vec3 normal = normalIn.normalize();
+    Vec3 diffuseAccumulation(0, 0, 0), specularAccumulation(0, 0, 0);
+    for (const Light& light : lights) {
+        const Vec3 vecToLight = light.position - hit.hitPoint;
+        const double distanceToLight = vecToLight.length();
+        if (distanceToLight <= 0.0) continue;
+        const Vec3 lightToHit = vecToLight / distanceToLight;
+        const double normalDotLightHit = std::max(0.0, normal.dot(lightToHit));
+        if (normalDotLightHit <= 0.0) continue;
+        if (distanceToLight <= bias) continue;
+        const Rayon shadowRay{hit.hitPoint + normal * bias, lightToHit};
+        const double transmittance = ComputeTransmittance(shadowRay, distanceToLight - bias, bias);
+        if (transmittance <= bias) continue;
+        const Vec3 emitted = light.color * light.intensity;
+        const Vec3 contribution =
+            emitted * (1.0 / (distanceToLight * distanceToLight)) * normalDotLightHit;
+        diffuseAccumulation += contribution * transmittance;
+        if (material.transparency <= 0.0 && material.specular > 0.0) {
+            const Vec3 halfVector = (lightToHit + viewDir).normalize();
+            const double NdotH = std::max(0.0, normal.dot(halfVector));
+            if (NdotH > 0.0) {
+                const double specFactor = std::pow(NdotH, material.shininess);
+                specularAccumulation +=
+                    (emitted * (1.0 / (distanceToLight * distanceToLight))) * specFactor * transmittance;
+            }
+        }
+    }
+    return material.color * diffuseAccumulation + specularAccumulation * material.specular;
+}
+
+static std::vector<Vec3> unpackVec3(const std::vector<double>& v) {
+    std::vector<Vec3> out;
+    out.reserve(v.size() / 3);
+    for (size_t i = 0; i + 2 < v.size(); i += 3) out.emplace_back(v[i], v[i + 1], v[i + 2]);
+    return out;
+}
+
+std::vector<Vec3> Scene::DirectLightning(const std::vector<HitInfo>& hits,
+                                         const std::vector<Vec3>& viewDirs,
+                                         const std::vector<Vec3>& normals, double bias) const {
+    if (viewDirs.size() != hits.size() || normals.size() != hits.size())
+        throw std::invalid_argument("DirectLightning: one viewDir and one normal per hit");
+    const size_t n = hits.size();
+    if (n == 0) return {};
+    rt_scene* sc = upload();
+    std::vector<double> pts(9 * n);
+    std::vector<rt_material> mats(n);
+    for (size_t i = 0; i < n; ++i) {
+        const Vec3 &p = hits[i].hitPoint, &nr = normals[i], &v = viewDirs[i];
+        const double rec[9] = {p.x, p.y, p.z, nr.x, nr.y, nr.z, v.x, v.y, v.z};
+        std::copy(rec, rec + 9, pts.begin() + 9 * i);
+        const Material& m = hits[i].material;
+        mats[i] = rt_material{{m.color.x, m.color.y, m.color.z}, m.shininess, m.specular,
+                              m.transparency, m.refractiveIndex};
+    }
+    std::vector<double> rgb(3 * n);
+    rt_render_opts o = optsDesc(RT_TONEMAP_NONE);
+    o.bias = bias;
+    const rt_direct_light_out out{rgb.data(), nullptr, nullptr};
+    rtamd::check(rt_direct_light(dev_->ctx, sc, &o, pts.data(), mats.data(), n, n, RT_DL_RADIANCE,
+                                 &out),
+                 "rt_direct_light");
+    return unpackVec3(rgb);
+}
+
+std::vector<Vec3> Scene::DirectLightning(const std::vector<Rayon>& rays, double bias) const {
+    if (rays.empty()) return {};
+    rt_scene* sc = upload();
+    static_assert(sizeof(Rayon) == 6 * sizeof(double), "Rayon is not six packed doubles");
+    std::vector<double> rgb(3 * rays.size());
+    rt_render_opts o = optsDesc(RT_TONEMAP_NONE);
+    o.bias = bias;
+    const rt_direct_light_out out{rgb.data(), nullptr, nullptr};
+    rtamd::check(rt_direct_light_rays(dev_->ctx, sc, &o,
+                                      reinterpret_cast<const double*>(rays.data()), rays.size(),
+                                      RT_DL_RADIANCE, &out),
+                 "rt_direct_light_rays");
+    return unpackVec3(rgb);
 }
 
 std::optional<HitInfo> Scene::CalculatePixelDepth(size_t x, size_t y, bool aa) const {

@@ -12,10 +12,15 @@
 //   ComputeTransmittance(rays, maxDist, bias) → rt_transmittance_rays (Scene.h:35-77, private
 //                              in the reference, for n rays at once)
 //   LightTransmittance(points, normals, bias) → rt_light_transmittance (Scene.h:86-104)
+//   DirectLightning(hits, viewDirs, normals, bias) → rt_direct_light (Scene.h:79-129, private
+//                              in the reference, for n surface points at once)
+//   DirectLightning(rays, bias) → rt_direct_light_rays (TraceRay's localLight, Scene.h:136-147, 168)
 // The single-ray IntersectAnyBefore(ray, maxDist) of the reference's signature stays a host
 // utility over the shapes' Intersect members: one ray per launch would pay an upload, a launch
 // and a download to learn one bit; the batch overloads give the same answers for many rays.
-// The single-ray ComputeTransmittance(ray, maxDist, bias) is a host utility for the same reason.
+// The single-ray ComputeTransmittance(ray, maxDist, bias) is a host utility for the same reason,
+// and so are the single-point DirectLightning(hit, viewDir, normalIn, bias) built on it and
+// IntersectClosestHost(ray), the closest hit over the shapes' GetHitInfoAt members.
 // Failures throw std::runtime_error(rt_last_error()).
 //
 // The Add* methods take `const T&` — a compatible superset of the reference's `T&`.
@@ -134,6 +139,26 @@ public:
     std::vector<double> LightTransmittance(const std::vector<Vec3>& points,
                                            const std::vector<Vec3>& normals,
                                            double bias = 1e-3) const;
+    // IntersectClosest (Scene.h:218-257) on the host, over the shapes' GetHitInfoAt members in the
+    // reference's visiting order (spheres, planes, triangles, models; a later shape wins only
+    // when strictly closer): the HitInfo of the device method, without a device.
+    std::optional<HitInfo> IntersectClosestHost(const Rayon& ray) const;
+    // directLightning(hit, viewDir, normalIn, bias) (Scene.h:79-129, private in the reference) on
+    // the host, over the point lights in the reference's operation order, each shadow ray through
+    // the host ComputeTransmittance(ray, maxDist, bias): the values of the batch overloads (where
+    // std::pow is reached, within an ulp or two of them).  Reads hit.hitPoint and hit.material;
+    // normalIn faces the viewer.  The area light of SetAreaLight is not read.
+    Vec3 DirectLightning(const HitInfo& hit, const Vec3& viewDir, const Vec3& normalIn,
+                         double bias = 1e-3) const;
+    // The same for every hit in one launch (rt_direct_light): one viewDir and one normal per hit
+    // (std::invalid_argument otherwise).
+    std::vector<Vec3> DirectLightning(const std::vector<HitInfo>& hits,
+                                      const std::vector<Vec3>& viewDirs,
+                                      const std::vector<Vec3>& normals, double bias = 1e-3) const;
+    // directLightning at the first hit of every ray, as TraceRay calls it (Scene.h:136-147, 168),
+    // in one launch (rt_direct_light_rays): the hit primitive's material, the normal flipped
+    // against the ray, viewDir = -ray.direction.normalize().  (0, 0, 0) where a ray hits nothing.
+    std::vector<Vec3> DirectLightning(const std::vector<Rayon>& rays, double bias = 1e-3) const;
     void SetDevice(int device) { device_ = device; dev_.reset(); devices_.clear(); }
     // RenderImage / RenderImageTonemapped / RenderImageF32 over several GPUs of the node from
     // this process: one scene copy per GPU, block-cyclic rows, assembled on the host (distinct

@@ -41,6 +41,12 @@ GB_NORMAL = 0x04
 GB_PRIM = 0x08
 GB_ALBEDO = 0x10
 GB_ALL = 0x1F
+# direct-lighting outputs (rt_capi.h RT_DL_*), each float64 [n, 3]
+DL_RADIANCE = 0x1
+DL_DIFFUSE = 0x2
+DL_SPECULAR = 0x4
+DL_ALL = 0x7
+DL_OUTPUTS = [("radiance", DL_RADIANCE), ("diffuse", DL_DIFFUSE), ("specular", DL_SPECULAR)]
 # per output, in bit order: name (the key of DeviceScene.gbuffer's dict and the field of
 # rt_gbuffer), bit, element type, elements per pixel
 GB_OUTPUTS = [("depth", GB_DEPTH, np.float64, 1), ("depth_norm", GB_DEPTH_NORM, np.float32, 1),
@@ -66,6 +72,8 @@ EXPORTED = [
     "rt_occluded_rays", "rt_occluded_rays_device",
     "rt_transmittance_rays", "rt_transmittance_rays_device",
     "rt_light_transmittance", "rt_light_transmittance_device",
+    "rt_direct_light", "rt_direct_light_device",
+    "rt_direct_light_rays", "rt_direct_light_rays_device",
 ]
 
 
@@ -113,6 +121,31 @@ def gbuffer_layout(outputs: int, width: int, rows: int, frames: int | None = Non
     lead = () if frames is None else (int(frames),)
     return {name: (lead + (rows, width) + ((k,) if k > 1 else ()), np.dtype(dt))
             for name, bit, dt, k in GB_OUTPUTS if outputs & bit}
+
+
+class DirectLightPtrs(ctypes.Structure):
+    """struct rt_direct_light_out: one pointer per output, in RT_DL_* bit order."""
+    _fields_ = [(name, ctypes.c_void_p) for name, _ in DL_OUTPUTS]
+
+
+def material_rows(materials, n: int) -> np.ndarray:
+    """`materials` of the direct-light queries as float64 [1, 7] or [n, 7] rows of rt_material's
+    layout {r, g, b, shininess, specular, transparency, refractive_index}: a scene.Material, a
+    7-tuple, or an [n, 7] array."""
+    if hasattr(materials, "as_tuple"):
+        c, *rest = materials.as_tuple()
+        materials = (*c, *rest)
+    m = np.ascontiguousarray(materials, np.float64)
+    if m.ndim == 1:
+        m = m.reshape(1, -1)
+    if m.ndim != 2 or m.shape[1] != 7 or m.shape[0] not in (1, n):
+        raise ValueError("materials: a Material, seven values, or an [n, 7] array")
+    return m
+
+
+def _dl_check(outputs: int):
+    if outputs == 0 or outputs & ~DL_ALL:
+        raise ValueError("outputs: a non-empty combination of DL_* bits")
 
 
 class GatherTiming(ctypes.Structure):
@@ -174,6 +207,10 @@ def load_library(path: str = LIB_PATH):
         "rt_transmittance_rays_device": [vp, vp, vp, vp, vp, ctypes.c_size_t, vp],
         "rt_light_transmittance": [vp, vp, vp, vp, ctypes.c_size_t, vp],
         "rt_light_transmittance_device": [vp, vp, vp, vp, ctypes.c_size_t, vp],
+        "rt_direct_light": [vp, vp, vp, vp, vp, ctypes.c_size_t, ctypes.c_size_t, i32, vp],
+        "rt_direct_light_device": [vp, vp, vp, vp, vp, ctypes.c_size_t, ctypes.c_size_t, i32, vp],
+        "rt_direct_light_rays": [vp, vp, vp, vp, ctypes.c_size_t, i32, vp],
+        "rt_direct_light_rays_device": [vp, vp, vp, vp, ctypes.c_size_t, i32, vp],
         "rt_tonemap": [vp, vp, ctypes.c_size_t, i32, vp],
         "rt_debug_f64_ops": [vp, vp, vp, ctypes.c_size_t, vp],
         "rt_debug_vec_ops": [vp, vp, ctypes.c_size_t, vp],
@@ -567,6 +604,111 @@ class DeviceScene:
                                                   points.data_ptr() if n else None, n,
                                                   out.data_ptr() if n * nl else None))
         return out
+
+    def _dl_host(self, n: int, outputs: int):
+        _dl_check(outputs)
+        res = {name: np.empty((n, 3), np.float64) for name, bit in DL_OUTPUTS if outputs & bit}
+        ptrs = DirectLightPtrs(**{k: v.ctypes.data for k, v in res.items()})
+        return res, ptrs
+
+    def _dl_device(self, n: int, outputs: int, out):
+        import torch
+        _dl_check(outputs)
+        dev = torch.device(f"cuda:{self.ctx.device}")
+        res = {}
+        for name, bit in DL_OUTPUTS:
+            if not outputs & bit:
+                continue
+            t = None if out is None else out.get(name)
+            if t is None:
+                t = torch.empty((n, 3), dtype=torch.float64, device=dev)
+            elif (t.dtype != torch.float64 or t.device != dev or t.numel() < 3 * n
+                  or not t.is_contiguous()):
+                raise ValueError(f"out[{name!r}]: a contiguous float64 tensor of at least n*3 "
+                                 "elements on the device")
+            res[name] = t
+        # never a NULL pointer for a requested output, an empty tensor's included
+        ptrs = DirectLightPtrs(**{k: (v.data_ptr() or 8) for k, v in res.items()})
+        return res, ptrs
+
+    def direct_light(self, points: np.ndarray, materials, outputs: int = DL_RADIANCE,
+                     bias: float = 1e-3, no_bvh: bool = False) -> dict:
+        """Batch directLightning (rt_direct_light): points [n,9] {p, normal facing the viewer,
+        view}; materials a scene.Material or seven values (shared by all points) or an [n,7]
+        array -> {"radiance" | "diffuse" | "specular": float64 [n,3]} for the DL_* bits of
+        `outputs`."""
+        points = np.ascontiguousarray(points, np.float64).reshape(-1, 9)
+        n = points.shape[0]
+        m = material_rows(materials, n)
+        res, ptrs = self._dl_host(n, outputs)
+        o = default_opts(bias=bias, flags=RT_FLAG_NO_BVH if no_bvh else 0)
+        _check(_lib.rt_direct_light(self.ctx.handle, self._h, ctypes.byref(o),
+                                    points.ctypes.data if n else None, m.ctypes.data, m.shape[0],
+                                    n, outputs, ctypes.byref(ptrs)))
+        return res
+
+    def direct_light_rays(self, rays: np.ndarray, outputs: int = DL_RADIANCE, bias: float = 1e-3,
+                          no_bvh: bool = False) -> dict:
+        """directLightning at the first hit of every ray (rt_direct_light_rays), with the hit
+        primitive's material: rays [n,6] -> the dict of direct_light; zeros where a ray misses."""
+        rays = np.ascontiguousarray(rays, np.float64).reshape(-1, 6)
+        n = rays.shape[0]
+        res, ptrs = self._dl_host(n, outputs)
+        o = default_opts(bias=bias, flags=RT_FLAG_NO_BVH if no_bvh else 0)
+        _check(_lib.rt_direct_light_rays(self.ctx.handle, self._h, ctypes.byref(o),
+                                         rays.ctypes.data if n else None, n, outputs,
+                                         ctypes.byref(ptrs)))
+        return res
+
+    def direct_light_device(self, points, materials, outputs: int = DL_RADIANCE, out=None,
+                            bias: float = 1e-3, no_bvh: bool = False) -> dict:
+        """Asynchronous rt_direct_light_device on the context's stream: points a contiguous
+        float64 [n,9] tensor on this context's device; materials a contiguous float64 [n,7]
+        tensor there, or a scene.Material / seven values on the host (shared by all points, passed
+        in the kernel arguments).  Returns a dict of float64 [n,3] tensors; `out` may hold a
+        tensor per requested name to write into."""
+        import torch
+        dev = torch.device(f"cuda:{self.ctx.device}")
+        if points.dtype != torch.float64 or points.device != dev or not points.is_contiguous():
+            raise ValueError("points: a contiguous float64 tensor on the context's device")
+        n = points.numel() // 9
+        if points.numel() != 9 * n:
+            raise ValueError("points: n*9 elements")
+        if torch.is_tensor(materials) and materials.numel() != 7:
+            if (materials.dtype != torch.float64 or materials.device != dev
+                    or materials.numel() != 7 * n or not materials.is_contiguous()):
+                raise ValueError("materials: a contiguous float64 [n,7] tensor on the device")
+            m_ptr, n_m = materials.data_ptr(), n
+        else:   # one material: a host record, read by the call before it returns
+            if torch.is_tensor(materials):
+                materials = materials.detach().cpu().numpy().reshape(7)
+            host = material_rows(materials, 1)
+            m_ptr, n_m = host.ctypes.data, 1
+        res, ptrs = self._dl_device(n, outputs, out)
+        o = default_opts(bias=bias, flags=RT_FLAG_NO_BVH if no_bvh else 0)
+        _check(_lib.rt_direct_light_device(self.ctx.handle, self._h, ctypes.byref(o),
+                                           points.data_ptr() if n else None, m_ptr, n_m, n,
+                                           outputs, ctypes.byref(ptrs)))
+        return res
+
+    def direct_light_rays_device(self, rays, outputs: int = DL_RADIANCE, out=None,
+                                 bias: float = 1e-3, no_bvh: bool = False) -> dict:
+        """Asynchronous rt_direct_light_rays_device on the context's stream: rays a contiguous
+        float64 [n,6] tensor on this context's device.  Returns a dict of float64 [n,3] tensors;
+        `out` may hold a tensor per requested name to write into."""
+        import torch
+        dev = torch.device(f"cuda:{self.ctx.device}")
+        if rays.dtype != torch.float64 or rays.device != dev or not rays.is_contiguous():
+            raise ValueError("rays: a contiguous float64 tensor on the context's device")
+        n = rays.numel() // 6
+        if rays.numel() != 6 * n:
+            raise ValueError("rays: n*6 elements")
+        res, ptrs = self._dl_device(n, outputs, out)
+        o = default_opts(bias=bias, flags=RT_FLAG_NO_BVH if no_bvh else 0)
+        _check(_lib.rt_direct_light_rays_device(self.ctx.handle, self._h, ctypes.byref(o),
+                                                rays.data_ptr() if n else None, n, outputs,
+                                                ctypes.byref(ptrs)))
+        return res
 
     def debug_tile_order(self):
         """The packet kernel's tile-order state for this scene's camera (rt_debug_tile_order):

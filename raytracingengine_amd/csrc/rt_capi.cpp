@@ -1224,6 +1224,166 @@ rt_status rt_light_transmittance(rt_context* ctx, const rt_scene* sc, const rt_r
     return RT_OK;
 }
 
+// ---- direct lighting (rt_direct.hip) -------------------------------------------------------
+static_assert(sizeof(rt_material) == 7 * sizeof(double), "rt_material is not seven packed doubles");
+
+// The argument checks the four direct-light entries share, made before anything touches a
+// device; `entry` ends every message.  inputs_ok: no input pointer is NULL, or n == 0.
+static rt_status check_direct_light_args(const rt_context* ctx, int outputs,
+                                         const rt_direct_light_out* out, bool inputs_ok,
+                                         size_t n_materials, size_t n, const char* entry) {
+    const std::string name(entry);
+    if (outputs == 0) return fail(RT_ERR_INVALID_ARG, "no output requested from " + name);
+    if (outputs & ~RT_DL_ALL) return fail(RT_ERR_INVALID_ARG, "unknown output bit passed to " + name);
+    if (!out) return fail(RT_ERR_INVALID_ARG, "NULL output record passed to " + name);
+    const void* ptr[3] = {out->radiance, out->diffuse, out->specular};
+    for (int k = 0; k < 3; ++k)
+        if ((outputs & (1 << k)) && !ptr[k])
+            return fail(RT_ERR_INVALID_ARG, "NULL pointer of a requested output passed to " + name);
+    if (!inputs_ok) return fail(RT_ERR_INVALID_ARG, "NULL argument to " + name);
+    if (n && n_materials != n && n_materials != 1)
+        return fail(RT_ERR_INVALID_ARG, "n_materials must be n or 1 in " + name);
+    if (!ctx) return fail(RT_ERR_INVALID_ARG, "NULL context passed to " + name);
+    return RT_OK;
+}
+
+// The requested outputs of `o` as the kernels take them (a pointer that was not requested is
+// not passed on).
+static DlOut direct_light_outputs(int outputs, const rt_direct_light_out& o) {
+    return DlOut{(outputs & RT_DL_RADIANCE) ? static_cast<double*>(o.radiance) : nullptr,
+                 (outputs & RT_DL_DIFFUSE) ? static_cast<double*>(o.diffuse) : nullptr,
+                 (outputs & RT_DL_SPECULAR) ? static_cast<double*>(o.specular) : nullptr};
+}
+
+static DlMaterial shared_material(const void* m) {
+    DlMaterial s;
+    std::memcpy(s.v, m, 7 * sizeof(double));
+    s.v[7] = 0.0;
+    return s;
+}
+
+// n*3 doubles per requested output after `used` doubles of ctx->rays (already ensured).
+static rt_direct_light_out direct_light_staging(rt_context* ctx, size_t used, size_t n,
+                                                int outputs) {
+    double* at = static_cast<double*>(ctx->rays.ptr) + used;
+    rt_direct_light_out d{nullptr, nullptr, nullptr};
+    void** slot[3] = {&d.radiance, &d.diffuse, &d.specular};
+    for (int k = 0; k < 3; ++k)
+        if (outputs & (1 << k)) {
+            *slot[k] = at;
+            at += 3 * n;
+        }
+    return d;
+}
+
+static rt_status direct_light_download(rt_context* ctx, const rt_direct_light_out& d,
+                                       const rt_direct_light_out& h, size_t n, int outputs) {
+    void* const dev[3] = {d.radiance, d.diffuse, d.specular};
+    void* const host[3] = {h.radiance, h.diffuse, h.specular};
+    for (int k = 0; k < 3; ++k)
+        if (outputs & (1 << k))
+            RT_HIP(hipMemcpyAsync(host[k], dev[k], n * 3 * sizeof(double), hipMemcpyDeviceToHost,
+                                  ctx->stream));
+    RT_HIP(hipStreamSynchronize(ctx->stream));
+    return RT_OK;
+}
+
+static size_t popcount3(int outputs) {
+    return static_cast<size_t>((outputs & 1) + ((outputs >> 1) & 1) + ((outputs >> 2) & 1));
+}
+
+rt_status rt_direct_light_device(rt_context* ctx, const rt_scene* sc, const rt_render_opts* opts,
+                                 const void* d_points, const void* d_materials, size_t n_materials,
+                                 size_t n, int outputs, const struct rt_direct_light_out* d_out) {
+    const char* entry = "rt_direct_light_device";
+    rt_status st = check_direct_light_args(ctx, outputs, d_out, !n || (d_points && d_materials),
+                                           n_materials, n, entry);
+    if (st != RT_OK) return st;
+    if (n == 0) return RT_OK;
+    DeviceGuard g(ctx->device);
+    TraceParams p;
+    bool opaque;
+    st = transmit_params(ctx, sc, opts, p, opaque);
+    if (st != RT_OK) return st;
+    // one material for all points: d_materials is a host pointer, read now (rt_capi.h)
+    const bool shared = n_materials == 1;
+    RT_HIP(launch_direct_light_points(p, opaque, static_cast<const double*>(d_points),
+                                      shared ? nullptr : static_cast<const double*>(d_materials),
+                                      shared ? shared_material(d_materials) : DlMaterial{}, n,
+                                      direct_light_outputs(outputs, *d_out), ctx->stream));
+    return RT_OK;
+}
+
+rt_status rt_direct_light(rt_context* ctx, const rt_scene* sc, const rt_render_opts* opts,
+                          const double* points, const rt_material* materials, size_t n_materials,
+                          size_t n, int outputs, const struct rt_direct_light_out* out) {
+    const char* entry = "rt_direct_light";
+    rt_status st = check_direct_light_args(ctx, outputs, out, !n || (points && materials),
+                                           n_materials, n, entry);
+    if (st != RT_OK) return st;
+    if (n == 0) return RT_OK;
+    DeviceGuard g(ctx->device);
+    TraceParams p;
+    bool opaque;
+    st = transmit_params(ctx, sc, opts, p, opaque);
+    if (st != RT_OK) return st;
+    // ctx->rays: n points (9 doubles), n materials (7 doubles) unless one is shared, and n * 3
+    // doubles per requested output
+    const bool shared = n_materials == 1;
+    const size_t in = n * (shared ? 9 : 16);
+    RT_HIP(ctx->rays.ensure((in + 3 * n * popcount3(outputs)) * sizeof(double)));
+    double* d_pts = static_cast<double*>(ctx->rays.ptr);
+    double* d_mat = d_pts + 9 * n;
+    RT_HIP(hipMemcpyAsync(d_pts, points, n * 9 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    if (!shared)
+        RT_HIP(hipMemcpyAsync(d_mat, materials, n * 7 * sizeof(double), hipMemcpyHostToDevice,
+                              ctx->stream));
+    const rt_direct_light_out d = direct_light_staging(ctx, in, n, outputs);
+    RT_HIP(launch_direct_light_points(p, opaque, d_pts, shared ? nullptr : d_mat,
+                                      shared ? shared_material(materials) : DlMaterial{}, n,
+                                      direct_light_outputs(outputs, d), ctx->stream));
+    return direct_light_download(ctx, d, *out, n, outputs);
+}
+
+rt_status rt_direct_light_rays_device(rt_context* ctx, const rt_scene* sc,
+                                      const rt_render_opts* opts, const void* d_rays, size_t n,
+                                      int outputs, const struct rt_direct_light_out* d_out) {
+    const char* entry = "rt_direct_light_rays_device";
+    rt_status st = check_direct_light_args(ctx, outputs, d_out, !n || d_rays, 1, n, entry);
+    if (st != RT_OK) return st;
+    if (n == 0) return RT_OK;
+    DeviceGuard g(ctx->device);
+    TraceParams p;
+    bool opaque;
+    st = transmit_params(ctx, sc, opts, p, opaque);
+    if (st != RT_OK) return st;
+    RT_HIP(launch_direct_light_rays(p, opaque, static_cast<const double*>(d_rays), n,
+                                    direct_light_outputs(outputs, *d_out), ctx->stream));
+    return RT_OK;
+}
+
+rt_status rt_direct_light_rays(rt_context* ctx, const rt_scene* sc, const rt_render_opts* opts,
+                               const double* rays, size_t n, int outputs,
+                               const struct rt_direct_light_out* out) {
+    const char* entry = "rt_direct_light_rays";
+    rt_status st = check_direct_light_args(ctx, outputs, out, !n || rays, 1, n, entry);
+    if (st != RT_OK) return st;
+    if (n == 0) return RT_OK;
+    DeviceGuard g(ctx->device);
+    TraceParams p;
+    bool opaque;
+    st = transmit_params(ctx, sc, opts, p, opaque);
+    if (st != RT_OK) return st;
+    // ctx->rays: n rays (6 doubles) and n * 3 doubles per requested output
+    RT_HIP(ctx->rays.ensure(n * (6 + 3 * popcount3(outputs)) * sizeof(double)));
+    double* d_rays = static_cast<double*>(ctx->rays.ptr);
+    RT_HIP(hipMemcpyAsync(d_rays, rays, n * 6 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    const rt_direct_light_out d = direct_light_staging(ctx, 6 * n, n, outputs);
+    RT_HIP(launch_direct_light_rays(p, opaque, d_rays, n, direct_light_outputs(outputs, d),
+                                    ctx->stream));
+    return direct_light_download(ctx, d, *out, n, outputs);
+}
+
 rt_status rt_tonemap(rt_context* ctx, const double* hdr, size_t n, int op, uint8_t* out) {
     if (!ctx || (!hdr && n) || (!out && n))
         return fail(RT_ERR_INVALID_ARG, "NULL argument to rt_tonemap");

@@ -272,6 +272,23 @@ hipError_t launch_transmittance_rays(const TraceParams& p, bool opaque, const do
                                      hipStream_t stream);
 hipError_t launch_light_transmittance(const TraceParams& p, bool opaque, const double* points,
                                       size_t n, double* out, hipStream_t stream);
+// Direct-lighting queries (rt_direct.hip): directLightning (Scene.h:79-129) over the scene's point
+// lights, per point {p, normal, view} with a material of rt_material's layout (materials: one per
+// point, or null: `shared` for all of them), and per ray at its closest hit with the hit
+// primitive's material (a miss writes zeros).  Each output is [n][3] doubles, or null: not written.
+struct DlOut {
+    double* radiance;  // color * diffuse + specular * material.specular (Scene.h:126-128)
+    double* diffuse;   // diffuseAccumulation
+    double* specular;  // specularAccumlation
+};
+struct DlMaterial {
+    double v[8];  // r g b shininess specular transparency ior -
+};
+hipError_t launch_direct_light_points(const TraceParams& p, bool opaque, const double* points,
+                                      const double* materials, const DlMaterial& shared, size_t n,
+                                      const DlOut& out, hipStream_t stream);
+hipError_t launch_direct_light_rays(const TraceParams& p, bool opaque, const double* rays, size_t n,
+                                    const DlOut& out, hipStream_t stream);
 hipError_t launch_tonemap(const double* hdr, size_t n, int op, uint8_t* out, hipStream_t stream);
 hipError_t launch_debug_f64(const double* x, const double* y, size_t n, double* out,
                             hipStream_t stream);
