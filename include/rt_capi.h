@@ -20,6 +20,9 @@
  *                                  (private there; over the point lights, for n surface points)
  *   rt_direct_light_rays[_device]  the localLight of Scene::TraceRay   Scene.h:136-147, 168
  *                                  (IntersectClosest, the normal flip, then directLightning)
+ *   rt_scatter_rays[_device]       one level of Scene::TraceRay   Scene.h:131-198
+ *                                  (what the level adds, and the child rays of Scene.h:178-180 and
+ *                                   190-191 with their weights, before they are traced)
  *   rt_tonemap                     tonemap() RaytracingEngine.cpp:165-174 and the operators of
  *                                  tonemapAll() RaytracingEngine.cpp:176-214, each followed by
  *                                  toColor() RaytracingEngine.cpp:113-121
@@ -582,6 +585,70 @@ rt_status rt_direct_light_rays(rt_context* ctx, const rt_scene* scene, const rt_
 rt_status rt_direct_light_rays_device(rt_context* ctx, const rt_scene* scene,
                                       const rt_render_opts* opts, const void* d_rays, size_t n,
                                       int outputs, const struct rt_direct_light_out* d_out);
+
+/* Batch scatter: one level of Scene::TraceRay (Scene.h:131-198) for n rays {ox,oy,oz,dx,dy,dz},
+ * before its children are traced.  With it TraceRay is composable from this interface:
+ *   TraceRay(ray, 0) == value(ray) + TraceRay(refraction child, 1) * fw
+ *                                  + TraceRay(reflection child, 1) * rw
+ * summed in that order (Scene.h:172, 182, 193); an absent child adds nothing.  The query never
+ * recurses.  Per ray:
+ *   Miss (IntersectClosest, Scene.h:218-257, finds nothing): value = backgroundColor(ray)
+ *     (Scene.h:30-33, 137-139), the flags byte is 0, both child rays and both weights are +0.0.
+ *   Hit: hitPoint = o + d*t; incoming, frontFace, the flipped normal, viewDir and cosTheta as in
+ *     Scene.h:144-148; transparency = clamp(material.transparency, 0, 1) (Scene.h:166);
+ *     localLight = directLightning(hit, viewDir, normal, bias) as rt_direct_light_rays forms it,
+ *     over the scene's point lights only; value = (0,0,0) + localLight * (1 - transparency) if
+ *     transparency < 1, else (0,0,0) (Scene.h:169-173).
+ *   Refraction, only if transparency > 0: eta = frontFace ? 1/etaT : etaT/1, refractDir =
+ *     incoming.refract(normal, eta); if refractDir.length() > bias the ray is
+ *     {hitPoint + dir * (bias * 1e2), dir} with dir = refractDir.normalize(), and
+ *     fw = transparency * (1 - fresnel), fresnel = f0 + (1 - f0) * pow(1 - cosTheta, 5),
+ *     f0 = pow((etaT - 1) / (etaT + 1), 2) (Scene.h:26-28, 161-164, 175-183).  Otherwise (total
+ *     internal reflection, or a refraction direction no longer than bias) there is no refraction
+ *     ray and fresnel becomes exactly 1.0 (Scene.h:185).
+ *   Reflection: rw = transparency > 0 ? fresnel : material.specular; the ray is present if
+ *     rw > bias: {hitPoint + dir * bias, dir} with dir = incoming.reflect(normal).normalize()
+ *     (Scene.h:189-191).
+ *   An absent child: its six doubles and its weight are +0.0, so the outputs have a fixed shape
+ *     and repeated calls return the same bytes.  Callers select live children by the flags; an
+ *     absent child is not to be traced (0 * NaN is NaN).
+ * Recursion limit: opts->max_recursion <= 0 treats every ray as one at the limit
+ * (Scene.h:132-134): value = backgroundColor(ray), nothing is intersected, flags 0, no children —
+ * how a caller ends a composition.  Any max_recursion > 0, the default included, gives the level
+ * above.
+ * Of opts only max_recursion (its sign), bias and RT_FLAG_NO_BVH are read; opts == NULL gives the
+ * defaults.  The build-defined area light is not read, even when attached to the scene (the rule
+ * of rt_direct_light and rt_light_transmittance): callers do not supply the pixel and sample keys
+ * its random numbers need.
+ * Numerics: child rays, flags and a miss's value carry no tolerance.  A hit's value carries none
+ * where directLightning does not reach pow, else it is within 1e-12 * max(1, |value|) of libm's.
+ * rw of an opaque material is material.specular bit for bit; fw and rw of a transparent material
+ * pass through the Fresnel pow and are held to the same 1e-12 bar; under total internal
+ * reflection rw is exactly 1.0.
+ * RT_ERR_INVALID_ARG: outputs == 0, an unknown bit in outputs, out NULL or a requested output's
+ * pointer NULL (pointers of outputs not requested are ignored), NULL rays with n > 0, a NULL
+ * context or scene.  n == 0 returns RT_OK.  Host pointers, synchronous. */
+#define RT_SC_VALUE    0x01  /* double  [n][3]  what this level adds before its children        */
+#define RT_SC_REFRACT  0x02  /* double  [n][6]  refraction ray {o, d}      (Scene.h:178-180)     */
+#define RT_SC_REFLECT  0x04  /* double  [n][6]  reflection ray {o, d}      (Scene.h:190-191)     */
+#define RT_SC_WEIGHTS  0x08  /* double  [n][2]  {fw, rw}: transparency*(1-fresnel), reflectiveness */
+#define RT_SC_FLAGS    0x10  /* uint8_t [n]     bit 0 hit, bit 1 refraction ray, bit 2 reflection ray */
+#define RT_SC_ALL      0x1f
+struct rt_scatter_out {
+    void* value;
+    void* refract_rays;
+    void* reflect_rays;
+    void* weights;
+    void* flags;
+};
+rt_status rt_scatter_rays(rt_context* ctx, const rt_scene* scene, const rt_render_opts* opts,
+                          const double* rays, size_t n, int outputs,
+                          const struct rt_scatter_out* out);
+/* The same on device pointers (d_rays: n*6 doubles; the members of d_out sized as above),
+ * asynchronous on the context's stream; no host memory is touched. */
+rt_status rt_scatter_rays_device(rt_context* ctx, const rt_scene* scene,
+                                 const rt_render_opts* opts, const void* d_rays, size_t n,
+                                 int outputs, const struct rt_scatter_out* d_out);
 
 /* Device tonemap of host FP64 radiance: op in [0, RT_TONEMAP_COUNT) writes n*3 bytes;
  * op == RT_TONEMAP_COUNT writes all seven operators, tonemapAll() order, 7*n*3 bytes. */

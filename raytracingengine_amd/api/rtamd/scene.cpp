@@ -500,6 +500,45 @@ std::vector<Vec3> Scene::DirectLightning(const std::vector<Rayon>& rays, double 
     return unpackVec3(rgb);
 }
 
+rtamd::Scatter Scene::ScatterRays(const std::vector<Rayon>& rays, bool terminal) const {
+    rtamd::Scatter s;
+    const size_t n = rays.size();
+    if (n == 0) return s;
+    rt_scene* sc = upload();
+    static_assert(sizeof(Rayon) == 6 * sizeof(double), "Rayon is not six packed doubles");
+    s.value.assign(n, Vec3(0, 0, 0));
+    s.refraction.assign(n, Rayon(Vec3(0, 0, 0), Vec3(0, 0, 0)));
+    s.reflection.assign(n, Rayon(Vec3(0, 0, 0), Vec3(0, 0, 0)));
+    s.flags.assign(n, 0);
+    std::vector<double> w(2 * n);
+    rt_render_opts o = optsDesc(RT_TONEMAP_NONE);
+    o.max_recursion = terminal ? 0 : 1;
+    const rt_scatter_out out{s.value.data(), s.refraction.data(), s.reflection.data(), w.data(),
+                             s.flags.data()};
+    rtamd::check(rt_scatter_rays(dev_->ctx, sc, &o, reinterpret_cast<const double*>(rays.data()), n,
+                                 RT_SC_ALL, &out),
+                 "rt_scatter_rays");
+    s.refractionWeight.resize(n);
+    s.reflectionWeight.resize(n);
+    for (size_t i = 0; i < n; ++i) {
+        s.refractionWeight[i] = w[2 * i];
+        s.reflectionWeight[i] = w[2 * i + 1];
+    }
+    return s;
+}
+
+std::vector<Vec3> Scene::TraceRays(const std::vector<Rayon>& rays, double bias) const {
+    if (rays.empty()) return {};
+    rt_scene* sc = upload();
+    std::vector<Vec3> rgb(rays.size(), Vec3(0, 0, 0));
+    rt_render_opts o = optsDesc(RT_TONEMAP_NONE);
+    o.bias = bias;
+    rtamd::check(rt_trace_rays(dev_->ctx, sc, &o, reinterpret_cast<const double*>(rays.data()),
+                               rays.size(), reinterpret_cast<double*>(rgb.data()), nullptr),
+                 "rt_trace_rays");
+    return rgb;
+}
+
 std::optional<HitInfo> Scene::CalculatePixelDepth(size_t x, size_t y, bool aa) const {
     return IntersectClosest(camera.getRay(x, y, aa));
 }

@@ -15,6 +15,9 @@
 //   DirectLightning(hits, viewDirs, normals, bias) → rt_direct_light (Scene.h:79-129, private
 //                              in the reference, for n surface points at once)
 //   DirectLightning(rays, bias) → rt_direct_light_rays (TraceRay's localLight, Scene.h:136-147, 168)
+//   ScatterRays(rays, terminal) → rt_scatter_rays (one TraceRay level, Scene.h:131-198, before
+//                              its children are traced)
+//   TraceRays(rays, bias)      → rt_trace_rays (TraceRay(ray, 0, bias) for n rays at once)
 // The single-ray IntersectAnyBefore(ray, maxDist) of the reference's signature stays a host
 // utility over the shapes' Intersect members: one ray per launch would pay an upload, a launch
 // and a download to learn one bit; the batch overloads give the same answers for many rays.
@@ -57,6 +60,18 @@ struct GBuffer {
     std::vector<Vec3> normal;        // HitInfo::normal (unflipped)
     std::vector<int32_t> prim;       // {type, index} pairs as rt_intersect_rays reports them
     std::vector<float> albedo;       // r g b of HitInfo::material.color
+};
+
+// Scene::ScatterRays' result: per ray one TraceRay level (Scene.h:131-198) before its children
+// are traced (rt_capi.h, rt_scatter_rays).  TraceRay(ray, 0) == value + TraceRay(refraction, 1) *
+// refractionWeight + TraceRay(reflection, 1) * reflectionWeight, the children selected by flags.
+struct Scatter {
+    std::vector<Vec3> value;               // the sky on a miss, else localLight * (1 - transparency)
+    std::vector<Rayon> refraction;         // Scene.h:178-180; zeros where absent
+    std::vector<Rayon> reflection;         // Scene.h:190-191; zeros where absent
+    std::vector<double> refractionWeight;  // transparency * (1 - fresnel); 0 where absent
+    std::vector<double> reflectionWeight;  // fresnel, or material.specular; 0 where absent
+    std::vector<uint8_t> flags;            // bit 0 hit, bit 1 refraction ray, bit 2 reflection ray
 };
 }  // namespace rtamd
 
@@ -159,6 +174,14 @@ public:
     // in one launch (rt_direct_light_rays): the hit primitive's material, the normal flipped
     // against the ray, viewDir = -ray.direction.normalize().  (0, 0, 0) where a ray hits nothing.
     std::vector<Vec3> DirectLightning(const std::vector<Rayon>& rays, double bias = 1e-3) const;
+    // One TraceRay level per ray, before its children are traced, in one launch
+    // (rt_scatter_rays): what the level adds, the two child rays, their weights and which of them
+    // exist.  terminal: every ray is at the recursion limit (Scene.h:132-134): the sky, no
+    // intersection, no children — how a caller ends a composition.  The bias is the renderer's
+    // (1e-3); maxRecursion is not read, the method never recurses.
+    rtamd::Scatter ScatterRays(const std::vector<Rayon>& rays, bool terminal = false) const;
+    // TraceRay(ray, 0, bias) for every ray in one launch (rt_trace_rays), with maxRecursion.
+    std::vector<Vec3> TraceRays(const std::vector<Rayon>& rays, double bias = 1e-3) const;
     void SetDevice(int device) { device_ = device; dev_.reset(); devices_.clear(); }
     // RenderImage / RenderImageTonemapped / RenderImageF32 over several GPUs of the node from
     // this process: one scene copy per GPU, block-cyclic rows, assembled on the host (distinct

@@ -47,6 +47,18 @@ DL_DIFFUSE = 0x2
 DL_SPECULAR = 0x4
 DL_ALL = 0x7
 DL_OUTPUTS = [("radiance", DL_RADIANCE), ("diffuse", DL_DIFFUSE), ("specular", DL_SPECULAR)]
+# scatter outputs (rt_capi.h RT_SC_*)
+SC_VALUE = 0x01
+SC_REFRACT = 0x02
+SC_REFLECT = 0x04
+SC_WEIGHTS = 0x08
+SC_FLAGS = 0x10
+SC_ALL = 0x1F
+# per output, in bit order: name (the key of DeviceScene.scatter's dict and the field of
+# rt_scatter_out), bit, element type, elements per ray (0: a flat [n] array)
+SC_OUTPUTS = [("value", SC_VALUE, np.float64, 3), ("refract_rays", SC_REFRACT, np.float64, 6),
+              ("reflect_rays", SC_REFLECT, np.float64, 6), ("weights", SC_WEIGHTS, np.float64, 2),
+              ("flags", SC_FLAGS, np.uint8, 0)]
 # per output, in bit order: name (the key of DeviceScene.gbuffer's dict and the field of
 # rt_gbuffer), bit, element type, elements per pixel
 GB_OUTPUTS = [("depth", GB_DEPTH, np.float64, 1), ("depth_norm", GB_DEPTH_NORM, np.float32, 1),
@@ -74,6 +86,7 @@ EXPORTED = [
     "rt_light_transmittance", "rt_light_transmittance_device",
     "rt_direct_light", "rt_direct_light_device",
     "rt_direct_light_rays", "rt_direct_light_rays_device",
+    "rt_scatter_rays", "rt_scatter_rays_device",
 ]
 
 
@@ -141,6 +154,16 @@ def material_rows(materials, n: int) -> np.ndarray:
     if m.ndim != 2 or m.shape[1] != 7 or m.shape[0] not in (1, n):
         raise ValueError("materials: a Material, seven values, or an [n, 7] array")
     return m
+
+
+class ScatterPtrs(ctypes.Structure):
+    """struct rt_scatter_out: one pointer per output, in RT_SC_* bit order."""
+    _fields_ = [(name, ctypes.c_void_p) for name, *_ in SC_OUTPUTS]
+
+
+def _sc_check(outputs: int):
+    if outputs == 0 or outputs & ~SC_ALL:
+        raise ValueError("outputs: a non-empty combination of SC_* bits")
 
 
 def _dl_check(outputs: int):
@@ -211,6 +234,8 @@ def load_library(path: str = LIB_PATH):
         "rt_direct_light_device": [vp, vp, vp, vp, vp, ctypes.c_size_t, ctypes.c_size_t, i32, vp],
         "rt_direct_light_rays": [vp, vp, vp, vp, ctypes.c_size_t, i32, vp],
         "rt_direct_light_rays_device": [vp, vp, vp, vp, ctypes.c_size_t, i32, vp],
+        "rt_scatter_rays": [vp, vp, vp, vp, ctypes.c_size_t, i32, vp],
+        "rt_scatter_rays_device": [vp, vp, vp, vp, ctypes.c_size_t, i32, vp],
         "rt_tonemap": [vp, vp, ctypes.c_size_t, i32, vp],
         "rt_debug_f64_ops": [vp, vp, vp, ctypes.c_size_t, vp],
         "rt_debug_vec_ops": [vp, vp, ctypes.c_size_t, vp],
@@ -710,6 +735,61 @@ class DeviceScene:
                                                 ctypes.byref(ptrs)))
         return res
 
+    def scatter(self, rays: np.ndarray, outputs: int = SC_ALL, bias: float = 1e-3,
+                terminal: bool = False, no_bvh: bool = False) -> dict:
+        """One TraceRay level per ray, before its children are traced (rt_scatter_rays): rays
+        [n,6] -> {"value" [n,3], "refract_rays" [n,6], "reflect_rays" [n,6], "weights" [n,2] {fw,
+        rw}: float64; "flags" [n] uint8: bit 0 hit, bit 1 refraction ray, bit 2 reflection ray}
+        for the SC_* bits of `outputs`.  An absent child is zeros.  terminal: every ray is at the
+        recursion limit (max_recursion = 0): sky, no intersection, no children."""
+        rays = np.ascontiguousarray(rays, np.float64).reshape(-1, 6)
+        n = rays.shape[0]
+        _sc_check(outputs)
+        res = {name: np.empty((n, k) if k else (n,), dt)
+               for name, bit, dt, k in SC_OUTPUTS if outputs & bit}
+        ptrs = ScatterPtrs(**{k: v.ctypes.data for k, v in res.items()})
+        o = default_opts(bias=bias, flags=RT_FLAG_NO_BVH if no_bvh else 0,
+                         max_recursion=0 if terminal else 1)
+        _check(_lib.rt_scatter_rays(self.ctx.handle, self._h, ctypes.byref(o),
+                                    rays.ctypes.data if n else None, n, outputs,
+                                    ctypes.byref(ptrs)))
+        return res
+
+    def scatter_device(self, rays, outputs: int = SC_ALL, out=None, bias: float = 1e-3,
+                       terminal: bool = False, no_bvh: bool = False) -> dict:
+        """Asynchronous rt_scatter_rays_device on the context's stream: rays a contiguous float64
+        [n,6] tensor on this context's device.  Returns the dict of scatter() as torch tensors;
+        `out` may hold a tensor per requested name to write into."""
+        import torch
+        dev = torch.device(f"cuda:{self.ctx.device}")
+        if rays.dtype != torch.float64 or rays.device != dev or not rays.is_contiguous():
+            raise ValueError("rays: a contiguous float64 tensor on the context's device")
+        n = rays.numel() // 6
+        if rays.numel() != 6 * n:
+            raise ValueError("rays: n*6 elements")
+        _sc_check(outputs)
+        res = {}
+        for name, bit, dt, k in SC_OUTPUTS:
+            if not outputs & bit:
+                continue
+            tdt = torch.uint8 if dt is np.uint8 else torch.float64
+            t = None if out is None else out.get(name)
+            if t is None:
+                t = torch.empty((n, k) if k else (n,), dtype=tdt, device=dev)
+            elif (t.dtype != tdt or t.device != dev or t.numel() < max(k, 1) * n
+                  or not t.is_contiguous()):
+                raise ValueError(f"out[{name!r}]: a contiguous {tdt} tensor of at least "
+                                 f"n*{max(k, 1)} elements on the device")
+            res[name] = t
+        # never a NULL pointer for a requested output, an empty tensor's included
+        ptrs = ScatterPtrs(**{k: (v.data_ptr() or 8) for k, v in res.items()})
+        o = default_opts(bias=bias, flags=RT_FLAG_NO_BVH if no_bvh else 0,
+                         max_recursion=0 if terminal else 1)
+        _check(_lib.rt_scatter_rays_device(self.ctx.handle, self._h, ctypes.byref(o),
+                                           rays.data_ptr() if n else None, n, outputs,
+                                           ctypes.byref(ptrs)))
+        return res
+
     def debug_tile_order(self):
         """The packet kernel's tile-order state for this scene's camera (rt_debug_tile_order):
         (state, order[tiles] or None, cost[tiles, waves] or None)."""
@@ -995,3 +1075,24 @@ def render_gather_all_batch(comms: list, scenes: list, cams: np.ndarray, opts: R
     _check(load_library().rt_render_gather_all_batch(cs, ss, n, cams.ctypes.data, len(cams),
                                                      ctypes.byref(opts), outputs, d_hdr64,
                                                      d_hdr32, d_ldr))
+
+
+def compose_trace(ds: "DeviceScene", rays: np.ndarray, depth: int, bias: float = 1e-3,
+                  _level: int = 0) -> np.ndarray:
+    """TraceRay(ray, 0) with maxRecursion = depth, composed level by level from scatter():
+        TraceRay(ray, k) = value(ray) + TraceRay(refraction child, k + 1) * fw
+                                      + TraceRay(reflection child, k + 1) * rw
+    in the reference's order of the sum (Scene.h:172, 182, 193).  The children that exist are
+    selected by the flags (an absent child adds nothing, not even a zero), and the level `depth`
+    is asked with terminal=True: every ray there is at the recursion limit.  rays [n,6] -> [n,3]."""
+    rays = np.ascontiguousarray(rays, np.float64).reshape(-1, 6)
+    if _level >= depth:
+        return ds.scatter(rays, outputs=SC_VALUE, bias=bias, terminal=True)["value"]
+    s = ds.scatter(rays, outputs=SC_ALL, bias=bias)
+    total = s["value"].copy()
+    for key, bit, w in (("refract_rays", 2, 0), ("reflect_rays", 4, 1)):
+        live = (s["flags"] & bit) != 0
+        if live.any():
+            child = compose_trace(ds, s[key][live], depth, bias, _level + 1)
+            total[live] = total[live] + child * s["weights"][live, w:w + 1]
+    return total

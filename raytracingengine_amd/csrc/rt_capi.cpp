@@ -1384,6 +1384,98 @@ rt_status rt_direct_light_rays(rt_context* ctx, const rt_scene* sc, const rt_ren
     return direct_light_download(ctx, d, *out, n, outputs);
 }
 
+// ---- scatter (rt_scatter.hip) ---------------------------------------------------------------
+// Bytes per ray of each output, in RT_SC_* bit order.
+static constexpr size_t kScBytes[5] = {24, 48, 48, 16, 1};
+
+// The argument checks of the two scatter entries, in rt_direct_light_rays' order, made before
+// anything touches a device; `entry` ends every message.
+static rt_status check_scatter_args(const rt_context* ctx, int outputs, const rt_scatter_out* out,
+                                    bool inputs_ok, const char* entry) {
+    const std::string name(entry);
+    if (outputs == 0) return fail(RT_ERR_INVALID_ARG, "no output requested from " + name);
+    if (outputs & ~RT_SC_ALL) return fail(RT_ERR_INVALID_ARG, "unknown output bit passed to " + name);
+    if (!out) return fail(RT_ERR_INVALID_ARG, "NULL output record passed to " + name);
+    const void* ptr[5] = {out->value, out->refract_rays, out->reflect_rays, out->weights, out->flags};
+    for (int k = 0; k < 5; ++k)
+        if ((outputs & (1 << k)) && !ptr[k])
+            return fail(RT_ERR_INVALID_ARG, "NULL pointer of a requested output passed to " + name);
+    if (!inputs_ok) return fail(RT_ERR_INVALID_ARG, "NULL argument to " + name);
+    if (!ctx) return fail(RT_ERR_INVALID_ARG, "NULL context passed to " + name);
+    return RT_OK;
+}
+
+static ScOut scatter_outputs(int outputs, const rt_scatter_out& o) {
+    return ScOut{(outputs & RT_SC_VALUE) ? static_cast<double*>(o.value) : nullptr,
+                 (outputs & RT_SC_REFRACT) ? static_cast<double*>(o.refract_rays) : nullptr,
+                 (outputs & RT_SC_REFLECT) ? static_cast<double*>(o.reflect_rays) : nullptr,
+                 (outputs & RT_SC_WEIGHTS) ? static_cast<double*>(o.weights) : nullptr,
+                 (outputs & RT_SC_FLAGS) ? static_cast<uint8_t*>(o.flags) : nullptr};
+}
+
+// transmit_params, and of opts->max_recursion its sign: 0 is "at the recursion limit".
+static rt_status scatter_params(rt_context* ctx, const rt_scene* sc, const rt_render_opts* opts,
+                                TraceParams& p, bool& opaque) {
+    rt_status st = transmit_params(ctx, sc, opts, p, opaque);
+    if (st != RT_OK) return st;
+    p.max_rec = (opts && opts->max_recursion <= 0) ? 0 : 1;
+    return RT_OK;
+}
+
+rt_status rt_scatter_rays_device(rt_context* ctx, const rt_scene* sc, const rt_render_opts* opts,
+                                 const void* d_rays, size_t n, int outputs,
+                                 const struct rt_scatter_out* d_out) {
+    rt_status st = check_scatter_args(ctx, outputs, d_out, !n || d_rays, "rt_scatter_rays_device");
+    if (st != RT_OK) return st;
+    if (n == 0) return RT_OK;
+    DeviceGuard g(ctx->device);
+    TraceParams p;
+    bool opaque;
+    st = scatter_params(ctx, sc, opts, p, opaque);
+    if (st != RT_OK) return st;
+    RT_HIP(launch_scatter_rays(p, opaque, static_cast<const double*>(d_rays), n,
+                               scatter_outputs(outputs, *d_out), ctx->stream));
+    return RT_OK;
+}
+
+rt_status rt_scatter_rays(rt_context* ctx, const rt_scene* sc, const rt_render_opts* opts,
+                          const double* rays, size_t n, int outputs,
+                          const struct rt_scatter_out* out) {
+    rt_status st = check_scatter_args(ctx, outputs, out, !n || rays, "rt_scatter_rays");
+    if (st != RT_OK) return st;
+    if (n == 0) return RT_OK;
+    DeviceGuard g(ctx->device);
+    TraceParams p;
+    bool opaque;
+    st = scatter_params(ctx, sc, opts, p, opaque);
+    if (st != RT_OK) return st;
+    // ctx->rays: n rays (6 doubles), then each requested output in bit order; the doubles first,
+    // so the flag bytes, the last, leave every other output 8-byte aligned
+    size_t bytes = n * 6 * sizeof(double);
+    for (int k = 0; k < 5; ++k)
+        if (outputs & (1 << k)) bytes += n * kScBytes[k];
+    RT_HIP(ctx->rays.ensure(bytes));
+    char* at = static_cast<char*>(ctx->rays.ptr);
+    double* d_rays = reinterpret_cast<double*>(at);
+    at += n * 6 * sizeof(double);
+    rt_scatter_out d{nullptr, nullptr, nullptr, nullptr, nullptr};
+    void** slot[5] = {&d.value, &d.refract_rays, &d.reflect_rays, &d.weights, &d.flags};
+    void* const host[5] = {out->value, out->refract_rays, out->reflect_rays, out->weights, out->flags};
+    for (int k = 0; k < 5; ++k)
+        if (outputs & (1 << k)) {
+            *slot[k] = at;
+            at += n * kScBytes[k];
+        }
+    RT_HIP(hipMemcpyAsync(d_rays, rays, n * 6 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    RT_HIP(launch_scatter_rays(p, opaque, d_rays, n, scatter_outputs(outputs, d), ctx->stream));
+    for (int k = 0; k < 5; ++k)
+        if (outputs & (1 << k))
+            RT_HIP(hipMemcpyAsync(host[k], *slot[k], n * kScBytes[k], hipMemcpyDeviceToHost,
+                                  ctx->stream));
+    RT_HIP(hipStreamSynchronize(ctx->stream));
+    return RT_OK;
+}
+
 rt_status rt_tonemap(rt_context* ctx, const double* hdr, size_t n, int op, uint8_t* out) {
     if (!ctx || (!hdr && n) || (!out && n))
         return fail(RT_ERR_INVALID_ARG, "NULL argument to rt_tonemap");

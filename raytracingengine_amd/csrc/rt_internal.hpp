@@ -289,6 +289,19 @@ hipError_t launch_direct_light_points(const TraceParams& p, bool opaque, const d
                                       const DlOut& out, hipStream_t stream);
 hipError_t launch_direct_light_rays(const TraceParams& p, bool opaque, const double* rays, size_t n,
                                     const DlOut& out, hipStream_t stream);
+// Scatter query (rt_scatter.hip): one TraceRay level (Scene.h:131-198) per ray, before its
+// children are traced — shade_hit's Node written out.  p.max_rec <= 0: every ray is at the
+// recursion limit (sky, no intersection).  The area light is not read.  A null output is not
+// written; at least one is set.
+struct ScOut {
+    double* value;         // [n][3] sky on a miss, else localLight * (1 - transparency)
+    double* refract_rays;  // [n][6] {o, d}, zeros where absent
+    double* reflect_rays;  // [n][6] {o, d}, zeros where absent
+    double* weights;       // [n][2] {fw, rw}, zero where the child is absent
+    uint8_t* flags;        // [n]    bit 0 hit, bit 1 refraction ray, bit 2 reflection ray
+};
+hipError_t launch_scatter_rays(const TraceParams& p, bool opaque, const double* rays, size_t n,
+                               const ScOut& out, hipStream_t stream);
 hipError_t launch_tonemap(const double* hdr, size_t n, int op, uint8_t* out, hipStream_t stream);
 hipError_t launch_debug_f64(const double* x, const double* y, size_t n, double* out,
                             hipStream_t stream);
