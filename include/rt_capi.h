@@ -23,6 +23,11 @@
  *   rt_scatter_rays[_device]       one level of Scene::TraceRay   Scene.h:131-198
  *                                  (what the level adds, and the child rays of Scene.h:178-180 and
  *                                   190-191 with their weights, before they are traced)
+ *   rt_camera_rays[_device]        Rayon Camera::getRay(x, y, AA) const   Math.h:99-121
+ *                                  (for every pixel of a frame, with the jitter of one AA sample)
+ *   rt_closest_rays[_device]       std::optional<HitInfo> Scene::IntersectClosest(ray) const
+ *                                  Scene.h:218-257 (and HitInfo::material, Shape.h:28-38)
+ *   rt_trace_rays[_device]         Vec3 Scene::TraceRay(ray, 0, bias) const   Scene.h:131-198
  *   rt_tonemap                     tonemap() RaytracingEngine.cpp:165-174 and the operators of
  *                                  tonemapAll() RaytracingEngine.cpp:176-214, each followed by
  *                                  toColor() RaytracingEngine.cpp:113-121
@@ -649,6 +654,80 @@ rt_status rt_scatter_rays(rt_context* ctx, const rt_scene* scene, const rt_rende
 rt_status rt_scatter_rays_device(rt_context* ctx, const rt_scene* scene,
                                  const rt_render_opts* opts, const void* d_rays, size_t n,
                                  int outputs, const struct rt_scatter_out* d_out);
+
+/* Camera rays: Camera::getRay(x, y, sample > 0 && aa_samples > 1) (Math.h:99-121) for every
+ * pixel of the row set of opts — the primary rays the render kernels trace for AA sample
+ * `sample` of a frame of this camera, seed and row set.  No scene is involved.
+ * rays_out: rows*W*6 doubles {ox,oy,oz,dx,dy,dz}, row-major and rows-local like rt_render_device's
+ * and rt_gbuffer_device's pixels: ray (x, y) sits at idx = (y_local*W + x); row_begin / row_end
+ * and the block-cyclic row_block / row_cycle of opts are honoured.  o is the camera position, d a
+ * unit vector.
+ * Jitter: sample 0 is never jittered (GeneratePixelAt, Scene.h:289-292: `aa > 0 && aaCount > 1`).
+ * Samples > 0 add the two uniform numbers of the build-defined counter RNG under the key
+ * (opts->seed, y_image*W + x, sample, 0 | 1) to the screen x and y, the render kernels' own
+ * draw.  So RenderImage is expressible from this interface:
+ *   render(x, y) == (TraceRay(ray of sample 0) + ... + TraceRay(ray of sample N-1)) / N
+ * summed in that order (Scene.h:289-300), for scenes without an area light (whose random numbers
+ * are keyed by the pixel, not by a ray's index).
+ * Of opts only the row set and seed are read; opts == NULL gives the defaults.
+ * RT_ERR_INVALID_ARG: a NULL context, camera or output, zero width or height, a row set outside
+ * the image, sample < 0 or sample >= max(1, aa_samples).  RT_ERR_UNSUPPORTED: more than 2^31
+ * pixels.  Host pointer, synchronous. */
+rt_status rt_camera_rays(rt_context* ctx, const rt_camera* cam, const rt_render_opts* opts,
+                         int sample, double* rays_out);
+/* The same into a device pointer (rows*W*6 doubles), asynchronous on the context's stream; no
+ * host memory is touched. */
+rt_status rt_camera_rays_device(rt_context* ctx, const rt_camera* cam, const rt_render_opts* opts,
+                                int sample, void* d_rays);
+
+/* Batch Scene::IntersectClosest (Scene.h:218-257) for n rays {ox,oy,oz,dx,dy,dz} with selectable
+ * structure-of-arrays outputs: what rt_intersect_rays answers in nine interleaved doubles per
+ * ray, plus the hit primitive's material (HitInfo::material), each in a plane of its own, and
+ * only those requested are computed and written.
+ * Bit-exactness: t, normal, point and prim carry the bits rt_intersect_rays returns for the same
+ *   ray (ties go to the first primitive in the reference's order of spheres, planes, triangles;
+ *   the comparison is the strict '<' of Scene.h:226-254).  normal is the unflipped
+ *   HitInfo::normal.  A triangle's index is its index into rt_scene_desc.triangles; a sphere's is
+ *   the scene's index (also for scenes of more than 64 spheres, which the renderer holds in a
+ *   spatial order of its own).  material is the seven doubles of the primitive's rt_material in
+ *   member order, as uploaded — what rt_direct_light accepts per point.
+ * Miss: t = +inf and prim = {0, -1} (the G-buffer's rule), normal = point = material = +0.0.
+ * Of opts only RT_FLAG_NO_BVH is read; opts == NULL gives the defaults.  Lights and the area
+ * light are not read.
+ * RT_ERR_INVALID_ARG: outputs == 0, an unknown bit in outputs, out NULL or a requested output's
+ * pointer NULL (pointers of outputs not requested are ignored), NULL rays with n > 0, a NULL
+ * context or scene.  n == 0 returns RT_OK.  Host pointers, synchronous. */
+#define RT_CH_T        0x01  /* double  [n]     HitInfo::distance                                */
+#define RT_CH_PRIM     0x02  /* int32_t [n][2]  {type, index}, as rt_intersect_rays / RT_GB_PRIM */
+#define RT_CH_NORMAL   0x04  /* double  [n][3]  HitInfo::normal, unflipped                       */
+#define RT_CH_POINT    0x08  /* double  [n][3]  HitInfo::hitPoint = o + d*t                      */
+#define RT_CH_MATERIAL 0x10  /* double  [n][7]  HitInfo::material as rt_material                 */
+#define RT_CH_ALL      0x1f
+struct rt_closest_out {
+    void* t;
+    void* prim;
+    void* normal;
+    void* point;
+    void* material;
+};
+rt_status rt_closest_rays(rt_context* ctx, const rt_scene* scene, const rt_render_opts* opts,
+                          const double* rays, size_t n, int outputs,
+                          const struct rt_closest_out* out);
+/* The same on device pointers (d_rays: n*6 doubles; the members of d_out sized as above),
+ * asynchronous on the context's stream; no host memory is touched. */
+rt_status rt_closest_rays_device(rt_context* ctx, const rt_scene* scene,
+                                 const rt_render_opts* opts, const void* d_rays, size_t n,
+                                 int outputs, const struct rt_closest_out* d_out);
+
+/* rt_trace_rays on device pointers: d_rays n*6 doubles, d_rgb n*3 doubles, asynchronous on the
+ * context's stream.  No staging copy is made, no host memory is touched and no stats are taken
+ * (ray counting stays with the host entry).  The kernel is the one rt_trace_rays selects for the
+ * scene and opts, so the bytes are the host entry's; the same members of opts apply
+ * (max_recursion, bias, seed, RT_FLAG_NO_BVH), and RT_ERR_UNSUPPORTED for a max_recursion above
+ * the kernels' limit with reflective or transparent materials.  RT_ERR_INVALID_ARG: a NULL
+ * context or scene, a NULL pointer with n > 0.  n == 0 returns RT_OK. */
+rt_status rt_trace_rays_device(rt_context* ctx, const rt_scene* scene, const rt_render_opts* opts,
+                               const void* d_rays, size_t n, void* d_rgb);
 
 /* Device tonemap of host FP64 radiance: op in [0, RT_TONEMAP_COUNT) writes n*3 bytes;
  * op == RT_TONEMAP_COUNT writes all seven operators, tonemapAll() order, 7*n*3 bytes. */

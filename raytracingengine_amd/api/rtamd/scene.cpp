@@ -539,6 +539,41 @@ std::vector<Vec3> Scene::TraceRays(const std::vector<Rayon>& rays, double bias) 
     return rgb;
 }
 
+std::vector<Rayon> Scene::CameraRays(int sample) const {
+    static_assert(sizeof(Rayon) == 6 * sizeof(double), "Rayon is not six packed doubles");
+    rtamd::t_device = device_;
+    rt_context* ctx = rtamd::thread_context(device_);
+    const rt_camera cam = cameraDesc();
+    const rt_render_opts o = optsDesc(RT_TONEMAP_NONE);
+    std::vector<Rayon> rays(camera.width * camera.height, Rayon(Vec3(0, 0, 0), Vec3(0, 0, 0)));
+    // with no pixel the entry still checks the camera and the sample
+    double none[6];
+    rtamd::check(rt_camera_rays(ctx, &cam, &o, sample,
+                                rays.empty() ? none : reinterpret_cast<double*>(rays.data())),
+                 "rt_camera_rays");
+    return rays;
+}
+
+rtamd::Hits Scene::IntersectClosest(const std::vector<Rayon>& rays) const {
+    static_assert(sizeof(Rayon) == 6 * sizeof(double), "Rayon is not six packed doubles");
+    static_assert(sizeof(rt_material) == 7 * sizeof(double), "rt_material is not seven doubles");
+    rtamd::Hits h;
+    const size_t n = rays.size();
+    if (n == 0) return h;
+    rt_scene* sc = upload();
+    h.t.resize(n);
+    h.prim.resize(2 * n);
+    h.normal.assign(n, Vec3(0, 0, 0));
+    h.point.assign(n, Vec3(0, 0, 0));
+    h.material.resize(n);
+    const rt_closest_out out{h.t.data(), h.prim.data(), h.normal.data(), h.point.data(),
+                             h.material.data()};
+    rtamd::check(rt_closest_rays(dev_->ctx, sc, nullptr, reinterpret_cast<const double*>(rays.data()),
+                                 n, RT_CH_ALL, &out),
+                 "rt_closest_rays");
+    return h;
+}
+
 std::optional<HitInfo> Scene::CalculatePixelDepth(size_t x, size_t y, bool aa) const {
     return IntersectClosest(camera.getRay(x, y, aa));
 }

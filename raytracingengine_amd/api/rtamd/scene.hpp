@@ -18,6 +18,8 @@
 //   ScatterRays(rays, terminal) → rt_scatter_rays (one TraceRay level, Scene.h:131-198, before
 //                              its children are traced)
 //   TraceRays(rays, bias)      → rt_trace_rays (TraceRay(ray, 0, bias) for n rays at once)
+//   CameraRays(sample)         → rt_camera_rays (Camera::getRay for every pixel, Math.h:99-121)
+//   IntersectClosest(rays)     → rt_closest_rays (Scene.h:218-257 for n rays at once)
 // The single-ray IntersectAnyBefore(ray, maxDist) of the reference's signature stays a host
 // utility over the shapes' Intersect members: one ray per launch would pay an upload, a launch
 // and a download to learn one bit; the batch overloads give the same answers for many rays.
@@ -72,6 +74,16 @@ struct Scatter {
     std::vector<double> refractionWeight;  // transparency * (1 - fresnel); 0 where absent
     std::vector<double> reflectionWeight;  // fresnel, or material.specular; 0 where absent
     std::vector<uint8_t> flags;            // bit 0 hit, bit 1 refraction ray, bit 2 reflection ray
+};
+
+// The batch Scene::IntersectClosest's result: per ray the HitInfo members as arrays
+// (rt_capi.h, rt_closest_rays).  A miss holds t +inf, prim {0, -1}, zeros elsewhere.
+struct Hits {
+    std::vector<double> t;              // HitInfo::distance
+    std::vector<int32_t> prim;          // {type, index} pairs as rt_intersect_rays reports them
+    std::vector<Vec3> normal;           // HitInfo::normal (unflipped)
+    std::vector<Vec3> point;            // HitInfo::hitPoint
+    std::vector<rt_material> material;  // HitInfo::material, as uploaded
 };
 }  // namespace rtamd
 
@@ -182,6 +194,15 @@ public:
     rtamd::Scatter ScatterRays(const std::vector<Rayon>& rays, bool terminal = false) const;
     // TraceRay(ray, 0, bias) for every ray in one launch (rt_trace_rays), with maxRecursion.
     std::vector<Vec3> TraceRays(const std::vector<Rayon>& rays, double bias = 1e-3) const;
+    // camera.getRay(x, y, sample > 0 && antiAliasingAmount > 1) for every pixel in one launch
+    // (rt_camera_rays), row-major (GetPixelIndex): the rays RenderImage traces for AA sample
+    // `sample` (0 <= sample < max(1, antiAliasingAmount)), with the device's jitter of that sample.
+    std::vector<Rayon> CameraRays(int sample = 0) const;
+    // IntersectClosest(rays[i]) for every ray in one launch (rt_closest_rays): the members of the
+    // single-ray method's HitInfo as arrays, with the hit primitive's material.  prim holds the
+    // C-ABI's {type, index}: a triangle's index counts the standalone triangles first, then each
+    // model's.
+    rtamd::Hits IntersectClosest(const std::vector<Rayon>& rays) const;
     void SetDevice(int device) { device_ = device; dev_.reset(); devices_.clear(); }
     // RenderImage / RenderImageTonemapped / RenderImageF32 over several GPUs of the node from
     // this process: one scene copy per GPU, block-cyclic rows, assembled on the host (distinct

@@ -59,6 +59,18 @@ SC_ALL = 0x1F
 SC_OUTPUTS = [("value", SC_VALUE, np.float64, 3), ("refract_rays", SC_REFRACT, np.float64, 6),
               ("reflect_rays", SC_REFLECT, np.float64, 6), ("weights", SC_WEIGHTS, np.float64, 2),
               ("flags", SC_FLAGS, np.uint8, 0)]
+# closest-hit outputs (rt_capi.h RT_CH_*)
+CH_T = 0x01
+CH_PRIM = 0x02
+CH_NORMAL = 0x04
+CH_POINT = 0x08
+CH_MATERIAL = 0x10
+CH_ALL = 0x1F
+# per output, in bit order: name (the key of DeviceScene.closest's dict and the field of
+# rt_closest_out), bit, element type, elements per ray (0: a flat [n] array)
+CH_OUTPUTS = [("t", CH_T, np.float64, 0), ("prim", CH_PRIM, np.int32, 2),
+              ("normal", CH_NORMAL, np.float64, 3), ("point", CH_POINT, np.float64, 3),
+              ("material", CH_MATERIAL, np.float64, 7)]
 # per output, in bit order: name (the key of DeviceScene.gbuffer's dict and the field of
 # rt_gbuffer), bit, element type, elements per pixel
 GB_OUTPUTS = [("depth", GB_DEPTH, np.float64, 1), ("depth_norm", GB_DEPTH_NORM, np.float32, 1),
@@ -87,6 +99,9 @@ EXPORTED = [
     "rt_direct_light", "rt_direct_light_device",
     "rt_direct_light_rays", "rt_direct_light_rays_device",
     "rt_scatter_rays", "rt_scatter_rays_device",
+    "rt_camera_rays", "rt_camera_rays_device",
+    "rt_closest_rays", "rt_closest_rays_device",
+    "rt_trace_rays_device",
 ]
 
 
@@ -166,6 +181,16 @@ def _sc_check(outputs: int):
         raise ValueError("outputs: a non-empty combination of SC_* bits")
 
 
+class ClosestPtrs(ctypes.Structure):
+    """struct rt_closest_out: one pointer per output, in RT_CH_* bit order."""
+    _fields_ = [(name, ctypes.c_void_p) for name, *_ in CH_OUTPUTS]
+
+
+def _ch_check(outputs: int):
+    if outputs == 0 or outputs & ~CH_ALL:
+        raise ValueError("outputs: a non-empty combination of CH_* bits")
+
+
 def _dl_check(outputs: int):
     if outputs == 0 or outputs & ~DL_ALL:
         raise ValueError("outputs: a non-empty combination of DL_* bits")
@@ -236,6 +261,11 @@ def load_library(path: str = LIB_PATH):
         "rt_direct_light_rays_device": [vp, vp, vp, vp, ctypes.c_size_t, i32, vp],
         "rt_scatter_rays": [vp, vp, vp, vp, ctypes.c_size_t, i32, vp],
         "rt_scatter_rays_device": [vp, vp, vp, vp, ctypes.c_size_t, i32, vp],
+        "rt_camera_rays": [vp, vp, vp, i32, vp],
+        "rt_camera_rays_device": [vp, vp, vp, i32, vp],
+        "rt_closest_rays": [vp, vp, vp, vp, ctypes.c_size_t, i32, vp],
+        "rt_closest_rays_device": [vp, vp, vp, vp, ctypes.c_size_t, i32, vp],
+        "rt_trace_rays_device": [vp, vp, vp, vp, ctypes.c_size_t, vp],
         "rt_tonemap": [vp, vp, ctypes.c_size_t, i32, vp],
         "rt_debug_f64_ops": [vp, vp, vp, ctypes.c_size_t, vp],
         "rt_debug_vec_ops": [vp, vp, ctypes.c_size_t, vp],
@@ -789,6 +819,116 @@ class DeviceScene:
                                            rays.data_ptr() if n else None, n, outputs,
                                            ctypes.byref(ptrs)))
         return res
+
+    def _camera_record(self, cam):
+        """(the rt_camera record, width, height) of `cam`, or of the scene's camera for None."""
+        rec = self.camera if cam is None else np.ascontiguousarray(cam).reshape(-1)[:1]
+        return rec, int(rec["width"][0]), int(rec["height"][0])
+
+    def camera_rays(self, sample: int = 0, cam=None, **opts) -> np.ndarray:
+        """The camera rays of AA sample `sample` (rt_camera_rays): Camera::getRay for every pixel
+        of the row set of opts (seed, row_begin, row_end, row_block, row_cycle), float64
+        [rows*W, 6] {o, d}, rows-local like render's pixels.  cam: an rt_camera record as
+        `cameras()` makes; None: the scene's camera.  Sample 0 is never jittered."""
+        rec, w, h = self._camera_record(cam)
+        o = default_opts(**opts)
+        out = np.empty((rendered_rows(o, h) * w, 6), np.float64)
+        _check(_lib.rt_camera_rays(self.ctx.handle, rec.ctypes.data, ctypes.byref(o), sample,
+                                   out.ctypes.data or 8))
+        return out
+
+    def camera_rays_device(self, sample: int = 0, cam=None, out=None, **opts):
+        """Asynchronous rt_camera_rays_device on the context's stream: the rays of camera_rays()
+        as a float64 [rows*W, 6] torch tensor on the context's device (`out`: a contiguous float64
+        tensor of at least rows*W*6 elements to write into, returned as it is)."""
+        import torch
+        dev = torch.device(f"cuda:{self.ctx.device}")
+        rec, w, h = self._camera_record(cam)
+        o = default_opts(**opts)
+        n = rendered_rows(o, h) * w
+        if out is None:
+            out = torch.empty((n, 6), dtype=torch.float64, device=dev)
+        elif (out.dtype != torch.float64 or out.device != dev or out.numel() < 6 * n
+              or not out.is_contiguous()):
+            raise ValueError("out: a contiguous float64 tensor of at least rows*W*6 elements on "
+                             "the device")
+        _check(_lib.rt_camera_rays_device(self.ctx.handle, rec.ctypes.data, ctypes.byref(o),
+                                          sample, out.data_ptr() or 8))
+        return out
+
+    def closest(self, rays: np.ndarray, outputs: int = CH_ALL, no_bvh: bool = False) -> dict:
+        """Batch IntersectClosest with selectable outputs (rt_closest_rays): rays [n,6] ->
+        {"t" [n] float64, "prim" [n,2] int32 {type, index}, "normal" [n,3], "point" [n,3],
+        "material" [n,7] float64} for the CH_* bits of `outputs`.  A miss: t = +inf, prim =
+        {0, -1}, zeros elsewhere."""
+        rays = np.ascontiguousarray(rays, np.float64).reshape(-1, 6)
+        n = rays.shape[0]
+        _ch_check(outputs)
+        res = {name: np.empty((n, k) if k else (n,), dt)
+               for name, bit, dt, k in CH_OUTPUTS if outputs & bit}
+        ptrs = ClosestPtrs(**{k: (v.ctypes.data or 8) for k, v in res.items()})
+        o = default_opts(flags=RT_FLAG_NO_BVH if no_bvh else 0)
+        _check(_lib.rt_closest_rays(self.ctx.handle, self._h, ctypes.byref(o),
+                                    rays.ctypes.data if n else None, n, outputs,
+                                    ctypes.byref(ptrs)))
+        return res
+
+    def closest_device(self, rays, outputs: int = CH_ALL, out=None, no_bvh: bool = False) -> dict:
+        """Asynchronous rt_closest_rays_device on the context's stream: rays a contiguous float64
+        [n,6] tensor on this context's device.  Returns the dict of closest() as torch tensors;
+        `out` may hold a tensor per requested name to write into."""
+        import torch
+        dev = torch.device(f"cuda:{self.ctx.device}")
+        if rays.dtype != torch.float64 or rays.device != dev or not rays.is_contiguous():
+            raise ValueError("rays: a contiguous float64 tensor on the context's device")
+        n = rays.numel() // 6
+        if rays.numel() != 6 * n:
+            raise ValueError("rays: n*6 elements")
+        _ch_check(outputs)
+        res = {}
+        for name, bit, dt, k in CH_OUTPUTS:
+            if not outputs & bit:
+                continue
+            tdt = torch.int32 if dt is np.int32 else torch.float64
+            t = None if out is None else out.get(name)
+            if t is None:
+                t = torch.empty((n, k) if k else (n,), dtype=tdt, device=dev)
+            elif (t.dtype != tdt or t.device != dev or t.numel() < max(k, 1) * n
+                  or not t.is_contiguous()):
+                raise ValueError(f"out[{name!r}]: a contiguous {tdt} tensor of at least "
+                                 f"n*{max(k, 1)} elements on the device")
+            res[name] = t
+        # never a NULL pointer for a requested output, an empty tensor's included
+        ptrs = ClosestPtrs(**{k: (v.data_ptr() or 8) for k, v in res.items()})
+        o = default_opts(flags=RT_FLAG_NO_BVH if no_bvh else 0)
+        _check(_lib.rt_closest_rays_device(self.ctx.handle, self._h, ctypes.byref(o),
+                                           rays.data_ptr() if n else None, n, outputs,
+                                           ctypes.byref(ptrs)))
+        return res
+
+    def trace_rays_device(self, rays, out=None, **opts):
+        """Asynchronous rt_trace_rays_device on the context's stream: TraceRay at depth 0 for a
+        contiguous float64 [n,6] tensor on this context's device -> float64 [n,3] (`out`: a
+        contiguous float64 tensor of at least n*3 elements to write into, returned as it is).
+        opts as trace_rays (max_recursion, bias, seed, flags)."""
+        import torch
+        dev = torch.device(f"cuda:{self.ctx.device}")
+        if rays.dtype != torch.float64 or rays.device != dev or not rays.is_contiguous():
+            raise ValueError("rays: a contiguous float64 tensor on the context's device")
+        n = rays.numel() // 6
+        if rays.numel() != 6 * n:
+            raise ValueError("rays: n*6 elements")
+        if out is None:
+            out = torch.empty((n, 3), dtype=torch.float64, device=dev)
+        elif (out.dtype != torch.float64 or out.device != dev or out.numel() < 3 * n
+              or not out.is_contiguous()):
+            raise ValueError("out: a contiguous float64 tensor of at least n*3 elements on the "
+                             "device")
+        o = default_opts(**opts)
+        _check(_lib.rt_trace_rays_device(self.ctx.handle, self._h, ctypes.byref(o),
+                                         rays.data_ptr() if n else None, n,
+                                         out.data_ptr() if n else None))
+        return out
 
     def debug_tile_order(self):
         """The packet kernel's tile-order state for this scene's camera (rt_debug_tile_order):

@@ -1038,6 +1038,32 @@ rt_status rt_trace_rays(rt_context* ctx, const rt_scene* sc, const rt_render_opt
     return RT_OK;
 }
 
+// rt_trace_rays on device pointers: the same parameters and kernel selection, no staging copy,
+// no counting pass, no synchronisation.
+rt_status rt_trace_rays_device(rt_context* ctx, const rt_scene* sc, const rt_render_opts* opts,
+                               const void* d_rays, size_t n, void* d_rgb) {
+    if (!ctx || (n && (!d_rays || !d_rgb)))
+        return fail(RT_ERR_INVALID_ARG, "NULL argument to rt_trace_rays_device");
+    DeviceGuard g(ctx->device);
+    const rt_camera cam = batch_camera();
+    rt_render_opts o;
+    if (opts) o = *opts;
+    else rt_render_opts_default(&o);
+    o.row_begin = 0;
+    o.row_end = 0;
+    TraceParams p;
+    int path;
+    bool lds;
+    size_t lds_bytes;
+    uint32_t rows;
+    rt_status st = build_params(ctx, sc, &cam, &o, p, path, lds, lds_bytes, rows);
+    if (st != RT_OK) return st;
+    if (n == 0) return RT_OK;
+    RT_HIP(launch_trace_rays(p, path, false, static_cast<const double*>(d_rays), n,
+                             static_cast<double*>(d_rgb), ctx->stream));
+    return RT_OK;
+}
+
 rt_status rt_intersect_rays(rt_context* ctx, const rt_scene* sc, const double* rays, size_t n,
                             double* hits) {
     if (!ctx || (n && (!rays || !hits)))
@@ -1471,6 +1497,157 @@ rt_status rt_scatter_rays(rt_context* ctx, const rt_scene* sc, const rt_render_o
     for (int k = 0; k < 5; ++k)
         if (outputs & (1 << k))
             RT_HIP(hipMemcpyAsync(host[k], *slot[k], n * kScBytes[k], hipMemcpyDeviceToHost,
+                                  ctx->stream));
+    RT_HIP(hipStreamSynchronize(ctx->stream));
+    return RT_OK;
+}
+
+// ---- camera rays (rt_camera_rays.hip) -------------------------------------------------------
+// The argument checks of the two camera-ray entries and the camera part of build_params: no scene
+// is involved, and of opts only the row set and the seed are read.
+static rt_status camera_rays_params(const rt_context* ctx, const rt_camera* cam,
+                                    const rt_render_opts* opts, int sample, const void* out,
+                                    const char* entry, TraceParams& p) {
+    const std::string name(entry);
+    if (!ctx || !cam || !out) return fail(RT_ERR_INVALID_ARG, "NULL argument to " + name);
+    if (cam->width == 0 || cam->height == 0)
+        return fail(RT_ERR_INVALID_ARG, "zero camera width or height passed to " + name);
+    if (static_cast<uint64_t>(cam->width) * cam->height > (1ull << 31))
+        return fail(RT_ERR_UNSUPPORTED, "image larger than 2^31 pixels passed to " + name);
+    if (sample < 0 || sample >= std::max(1, cam->aa_samples))
+        return fail(RT_ERR_INVALID_ARG, "sample " + std::to_string(sample) +
+                                            " outside [0, max(1, aa_samples)) passed to " + name);
+    rt_render_opts o;
+    rt_render_opts_default(&o);
+    if (opts) {
+        o.seed = opts->seed;
+        o.row_begin = opts->row_begin;
+        o.row_end = opts->row_end;
+        o.row_block = opts->row_block;
+        o.row_cycle = opts->row_cycle;
+    }
+    const uint32_t r1 = o.row_end ? o.row_end : cam->height;
+    if (r1 > cam->height || o.row_begin >= r1)
+        return fail(RT_ERR_INVALID_ARG, "row range [" + std::to_string(o.row_begin) + "," +
+                                            std::to_string(r1) + ") invalid for height " +
+                                            std::to_string(cam->height) + " passed to " + name);
+    if (o.row_cycle > 1 && o.row_block == 0)
+        return fail(RT_ERR_INVALID_ARG, "row_cycle > 1 without row_block >= 1 passed to " + name);
+    std::memset(&p, 0, sizeof p);
+    for (int i = 0; i < 3; ++i) p.cam_pos[i] = cam->position[i];
+    p.focal = cam->focal;
+    p.width = cam->width;
+    p.height = cam->height;
+    p.aa = cam->aa_samples;
+    p.seed = o.seed;
+    p.row0 = o.row_begin;
+    if (o.row_cycle > 1) {
+        p.row_block = o.row_block;
+        p.row_stride = static_cast<uint32_t>(o.row_block) * o.row_cycle;
+    }
+    p.rows = rendered_rows(o, cam->height);
+    return RT_OK;
+}
+
+rt_status rt_camera_rays_device(rt_context* ctx, const rt_camera* cam, const rt_render_opts* opts,
+                                int sample, void* d_rays) {
+    TraceParams p;
+    rt_status st = camera_rays_params(ctx, cam, opts, sample, d_rays, "rt_camera_rays_device", p);
+    if (st != RT_OK) return st;
+    DeviceGuard g(ctx->device);
+    RT_HIP(launch_camera_rays(p, sample, static_cast<double*>(d_rays), ctx->stream));
+    return RT_OK;
+}
+
+rt_status rt_camera_rays(rt_context* ctx, const rt_camera* cam, const rt_render_opts* opts,
+                         int sample, double* rays_out) {
+    TraceParams p;
+    rt_status st = camera_rays_params(ctx, cam, opts, sample, rays_out, "rt_camera_rays", p);
+    if (st != RT_OK) return st;
+    DeviceGuard g(ctx->device);
+    const size_t bytes = static_cast<size_t>(p.rows) * p.width * 6 * sizeof(double);
+    RT_HIP(ctx->rays.ensure(bytes));
+    double* d_rays = static_cast<double*>(ctx->rays.ptr);
+    RT_HIP(launch_camera_rays(p, sample, d_rays, ctx->stream));
+    RT_HIP(hipMemcpyAsync(rays_out, d_rays, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    RT_HIP(hipStreamSynchronize(ctx->stream));
+    return RT_OK;
+}
+
+// ---- closest hit with selectable outputs (rt_closest.hip) -----------------------------------
+// Bytes per ray of each output, in RT_CH_* bit order (every one a multiple of 8).
+static constexpr size_t kChBytes[5] = {8, 8, 24, 24, 56};
+
+// rt_scatter_rays' checks in its order, made before anything touches a device.
+static rt_status check_closest_args(const rt_context* ctx, int outputs, const rt_closest_out* out,
+                                    bool inputs_ok, const char* entry) {
+    const std::string name(entry);
+    if (outputs == 0) return fail(RT_ERR_INVALID_ARG, "no output requested from " + name);
+    if (outputs & ~RT_CH_ALL) return fail(RT_ERR_INVALID_ARG, "unknown output bit passed to " + name);
+    if (!out) return fail(RT_ERR_INVALID_ARG, "NULL output record passed to " + name);
+    const void* ptr[5] = {out->t, out->prim, out->normal, out->point, out->material};
+    for (int k = 0; k < 5; ++k)
+        if ((outputs & (1 << k)) && !ptr[k])
+            return fail(RT_ERR_INVALID_ARG, "NULL pointer of a requested output passed to " + name);
+    if (!inputs_ok) return fail(RT_ERR_INVALID_ARG, "NULL argument to " + name);
+    if (!ctx) return fail(RT_ERR_INVALID_ARG, "NULL context passed to " + name);
+    return RT_OK;
+}
+
+static ChOut closest_outputs(int outputs, const rt_closest_out& o) {
+    return ChOut{(outputs & RT_CH_T) ? static_cast<double*>(o.t) : nullptr,
+                 (outputs & RT_CH_PRIM) ? static_cast<int32_t*>(o.prim) : nullptr,
+                 (outputs & RT_CH_NORMAL) ? static_cast<double*>(o.normal) : nullptr,
+                 (outputs & RT_CH_POINT) ? static_cast<double*>(o.point) : nullptr,
+                 (outputs & RT_CH_MATERIAL) ? static_cast<double*>(o.material) : nullptr};
+}
+
+rt_status rt_closest_rays_device(rt_context* ctx, const rt_scene* sc, const rt_render_opts* opts,
+                                 const void* d_rays, size_t n, int outputs,
+                                 const struct rt_closest_out* d_out) {
+    rt_status st = check_closest_args(ctx, outputs, d_out, !n || d_rays, "rt_closest_rays_device");
+    if (st != RT_OK) return st;
+    if (n == 0) return RT_OK;
+    DeviceGuard g(ctx->device);
+    TraceParams p;
+    st = occluded_params(ctx, sc, opts, p);  // of opts only RT_FLAG_NO_BVH
+    if (st != RT_OK) return st;
+    RT_HIP(launch_closest_rays(p, static_cast<const double*>(d_rays), n,
+                               closest_outputs(outputs, *d_out), ctx->stream));
+    return RT_OK;
+}
+
+rt_status rt_closest_rays(rt_context* ctx, const rt_scene* sc, const rt_render_opts* opts,
+                          const double* rays, size_t n, int outputs,
+                          const struct rt_closest_out* out) {
+    rt_status st = check_closest_args(ctx, outputs, out, !n || rays, "rt_closest_rays");
+    if (st != RT_OK) return st;
+    if (n == 0) return RT_OK;
+    DeviceGuard g(ctx->device);
+    TraceParams p;
+    st = occluded_params(ctx, sc, opts, p);
+    if (st != RT_OK) return st;
+    // ctx->rays: n rays (6 doubles), then each requested output in bit order
+    size_t bytes = n * 6 * sizeof(double);
+    for (int k = 0; k < 5; ++k)
+        if (outputs & (1 << k)) bytes += n * kChBytes[k];
+    RT_HIP(ctx->rays.ensure(bytes));
+    char* at = static_cast<char*>(ctx->rays.ptr);
+    double* d_rays = reinterpret_cast<double*>(at);
+    at += n * 6 * sizeof(double);
+    rt_closest_out d{nullptr, nullptr, nullptr, nullptr, nullptr};
+    void** slot[5] = {&d.t, &d.prim, &d.normal, &d.point, &d.material};
+    void* const host[5] = {out->t, out->prim, out->normal, out->point, out->material};
+    for (int k = 0; k < 5; ++k)
+        if (outputs & (1 << k)) {
+            *slot[k] = at;
+            at += n * kChBytes[k];
+        }
+    RT_HIP(hipMemcpyAsync(d_rays, rays, n * 6 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    RT_HIP(launch_closest_rays(p, d_rays, n, closest_outputs(outputs, d), ctx->stream));
+    for (int k = 0; k < 5; ++k)
+        if (outputs & (1 << k))
+            RT_HIP(hipMemcpyAsync(host[k], *slot[k], n * kChBytes[k], hipMemcpyDeviceToHost,
                                   ctx->stream));
     RT_HIP(hipStreamSynchronize(ctx->stream));
     return RT_OK;

@@ -302,6 +302,22 @@ struct ScOut {
 };
 hipError_t launch_scatter_rays(const TraceParams& p, bool opaque, const double* rays, size_t n,
                                const ScOut& out, hipStream_t stream);
+// Camera rays (rt_camera_rays.hip): Camera::getRay(x, y, sample > 0 && p.aa > 1) for every pixel
+// of p's row set, {o, d} per pixel at its rows-local index; the jitter key is the render
+// kernels' (p.seed, y_image * W + x, sample).  out: p.rows * p.width * 6 doubles.
+hipError_t launch_camera_rays(const TraceParams& p, int sample, double* out, hipStream_t stream);
+// Closest-hit query (rt_closest.hip): IntersectClosest per ray, each output a plane of its own.
+// A null output is not written; at least one is set.  A miss: t = +inf, prim = {0, -1}, +0.0
+// elsewhere.
+struct ChOut {
+    double* t;         // [n]    HitInfo::distance
+    int32_t* prim;     // [n][2] {type, index}
+    double* normal;    // [n][3] geometric normal, as rt_intersect_rays
+    double* point;     // [n][3] o + d * t
+    double* material;  // [n][7] the hit primitive's material, rt_material's member order
+};
+hipError_t launch_closest_rays(const TraceParams& p, const double* rays, size_t n, const ChOut& out,
+                               hipStream_t stream);
 hipError_t launch_tonemap(const double* hdr, size_t n, int op, uint8_t* out, hipStream_t stream);
 hipError_t launch_debug_f64(const double* x, const double* y, size_t n, double* out,
                             hipStream_t stream);

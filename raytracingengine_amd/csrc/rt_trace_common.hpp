@@ -132,20 +132,38 @@ __device__ __forceinline__ bool bvh_box(const double* nd, d3 o, d3 d, d3 inv, do
 // (t, index) minimum, and a node is skipped only when its entry bound exceeds the current best
 // t by a 1e-9 margin (so a tie can never be skipped).  The merge with the sphere/plane result is
 // the reference's strict '<'.
+// STK: where the traversal keeps its kBvhStack node indices.  BvhStackPrivate (a tag): in an
+// array of the thread's private memory, declared here (every kernel but rt_closest.hip's).
+// BvhStackLds: in the workgroup's LDS, entry i of a thread at base[i * stride] with base = the
+// array + the thread's index and stride = the workgroup's thread count, so a lane's bank depends
+// on the lane alone.
+struct BvhStackPrivate {
+    static constexpr bool kPrivate = true;
+};
+struct BvhStackLds {
+    static constexpr bool kPrivate = false;
+    int* base;
+    int stride;
+};
+template <class STK>
 __device__ __forceinline__ void bvh_triangles(const double* tri, const double* bvh,
                                               const int32_t* order, d3 o, d3 d, bool& found,
-                                              double& best, int& kind, int& idx) {
+                                              double& best, int& kind, int& idx, const STK& ext) {
     const d3 inv = mk(d.x != 0.0 ? 1.0 / d.x : 0.0, d.y != 0.0 ? 1.0 / d.y : 0.0,
                       d.z != 0.0 ? 1.0 / d.z : 0.0);
     bool tf = false;
     double tb = 0.0;
     int ti = 0;
-    int stk[kBvhStack];
+    int priv[STK::kPrivate ? kBvhStack : 1];
+    auto stk = [&](int i) -> int& {
+        if constexpr (STK::kPrivate) return priv[i];
+        else return ext.base[i * ext.stride];
+    };
     int sp = 0;
     double tn;
-    if (bvh_box(bvh, o, d, inv, tn)) stk[sp++] = 0;
+    if (bvh_box(bvh, o, d, inv, tn)) stk(sp++) = 0;
     while (sp > 0) {
-        const double* nd = bvh + kBvhNodeStride * stk[--sp];
+        const double* nd = bvh + kBvhNodeStride * stk(--sp);
         const int first = __double2loint(nd[6]), count = __double2hiint(nd[6]);
         if (count > 0) {
             for (int j = first; j < first + count; ++j) {
@@ -166,12 +184,12 @@ __device__ __forceinline__ void bvh_triangles(const double* tri, const double* b
         const bool h1 = bvh_box(bvh + kBvhNodeStride * (first + 1), o, d, inv, t1) && !(t1 > lim);
         if (h0 && h1) {  // nearer child on top
             const bool near0 = !(t1 < t0);
-            stk[sp++] = near0 ? first + 1 : first;
-            stk[sp++] = near0 ? first : first + 1;
+            stk(sp++) = near0 ? first + 1 : first;
+            stk(sp++) = near0 ? first : first + 1;
         } else if (h0) {
-            stk[sp++] = first;
+            stk(sp++) = first;
         } else if (h1) {
-            stk[sp++] = first + 1;
+            stk(sp++) = first + 1;
         }
     }
     if (tf && (!found || tb < best)) {
@@ -187,8 +205,10 @@ __device__ __forceinline__ void bvh_triangles(const double* tri, const double* b
 // MASKED: only the spheres of `mask` (a wave-uniform set of spheres 0..63 that contains every
 // sphere the ray can hit, wf_shadow_mask), visited in ascending index order as the full loop
 // visits them, so ties resolve alike.
-template <bool MASKED>
-__device__ __forceinline__ bool closest_t(const SceneView& S, d3 o, d3 d, Hit& h, uint64_t mask) {
+// stk: the BVH traversal's stack (bvh_triangles).
+template <bool MASKED, class STK>
+__device__ __forceinline__ bool closest_stk(const SceneView& S, d3 o, d3 d, Hit& h, uint64_t mask,
+                                            const STK& stk) {
     bool found = false;
     double best = 0.0;
     int kind = 0, idx = -1;
@@ -244,7 +264,7 @@ __device__ __forceinline__ bool closest_t(const SceneView& S, d3 o, d3 d, Hit& h
     }
 #ifndef RT_LEAN_GENERIC  // the lean build (rt_trace_lean.hip) serves scenes without triangles
     if (S.bvh) {
-        bvh_triangles(S.tri, S.bvh, S.bvh_tri, o, d, found, best, kind, idx);
+        bvh_triangles(S.tri, S.bvh, S.bvh_tri, o, d, found, best, kind, idx, stk);
     } else {
         for (int i = 0; i < S.nt; ++i) {
             double t;
@@ -262,8 +282,17 @@ __device__ __forceinline__ bool closest_t(const SceneView& S, d3 o, d3 d, Hit& h
     h.idx = idx;
     return found;
 }
+template <bool MASKED>
+__device__ __forceinline__ bool closest_t(const SceneView& S, d3 o, d3 d, Hit& h, uint64_t mask) {
+    BvhStackPrivate stk;
+    return closest_stk<MASKED>(S, o, d, h, mask, stk);
+}
 __device__ __forceinline__ bool closest(const SceneView& S, d3 o, d3 d, Hit& h) {
     return closest_t<false>(S, o, d, h, 0ull);
+}
+// closest with the traversal stack in LDS (rt_closest.hip): the same body, no private memory.
+__device__ __forceinline__ bool closest(const SceneView& S, d3 o, d3 d, Hit& h, BvhStackLds stk) {
+    return closest_stk<false>(S, o, d, h, 0ull, stk);
 }
 
 // Image row of the launch's row-local row yl (contiguous, or block-cyclic for multi-GPU).
