@@ -778,6 +778,13 @@ rt_status rt_debug_shadow_table(rt_context* ctx, uint64_t* with_table, uint64_t*
  * RTAMD_PK_TILE_CLASS=0 in the environment, read per launch, turns them off. */
 rt_status rt_debug_tile_class(rt_context* ctx, uint64_t* with_words, uint64_t* without_words);
 
+/* Test hook (read-only): the same count for the shadow-plane keep masks — frames enqueued with
+ * class words whose per-light masks were formed (*with_masks: the uniform path leaves the planes
+ * a mask drops out of its shadow classification) and frames without class words or with all-ones
+ * masks (*without_masks).  RTAMD_PK_PLANE_CLEAR=0 in the environment, read per launch, forms
+ * all-ones masks. */
+rt_status rt_debug_plane_clear(rt_context* ctx, uint64_t* with_masks, uint64_t* without_masks);
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif

@@ -93,6 +93,7 @@ EXPORTED = [
     "rt_debug_cone_table",
     "rt_debug_shadow_table",
     "rt_debug_tile_class",
+    "rt_debug_plane_clear",
     "rt_occluded_rays", "rt_occluded_rays_device",
     "rt_transmittance_rays", "rt_transmittance_rays_device",
     "rt_light_transmittance", "rt_light_transmittance_device",
@@ -293,6 +294,7 @@ def load_library(path: str = LIB_PATH):
         "rt_debug_cone_table": [vp, vp, vp],
         "rt_debug_shadow_table": [vp, vp, vp],
         "rt_debug_tile_class": [vp, vp, vp],
+        "rt_debug_plane_clear": [vp, vp, vp],
         "rt_debug_assemble_rows": [vp, vp, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_uint32,
                                    ctypes.c_uint32, ctypes.c_uint32, vp],
     }.items():
@@ -435,6 +437,12 @@ class Context:
         """Packet-kernel frames enqueued so far (with, without) tile class words."""
         a, b = ctypes.c_uint64(), ctypes.c_uint64()
         _check(_lib.rt_debug_tile_class(self._h, ctypes.byref(a), ctypes.byref(b)))
+        return a.value, b.value
+
+    def debug_plane_clear(self) -> tuple[int, int]:
+        """Packet-kernel frames enqueued so far (with, without) shadow-plane keep masks."""
+        a, b = ctypes.c_uint64(), ctypes.c_uint64()
+        _check(_lib.rt_debug_plane_clear(self._h, ctypes.byref(a), ctypes.byref(b)))
         return a.value, b.value
 
     def debug_vec_ops(self, v: np.ndarray) -> np.ndarray:

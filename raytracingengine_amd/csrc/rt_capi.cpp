@@ -350,6 +350,10 @@ rt_status enqueue_frames(rt_context* ctx, const rt_scene* sc, const rt_camera* c
         for (int f = 0; f < nframes; ++f)  // rt_debug_tile_class
             ++((nframes > 1 ? p.fr_ctab[f] : p.class_tab) ? ctx->tile_class_frames
                                                           : ctx->tile_noclass_frames);
+        for (int f = 0; f < nframes; ++f)  // rt_debug_plane_clear
+            ++(((nframes > 1 ? p.fr_ctab[f] : p.class_tab) && p.plane_masks)
+                   ? ctx->plane_mask_frames
+                   : ctx->plane_nomask_frames);
     }
     // the fix-up variant of the packet kernel (undecided shadow rays re-rendered per pixel after
     // the launch) uses the context's fix-up list: ordered across streams like the counters
@@ -1741,6 +1745,14 @@ rt_status rt_debug_tile_class(rt_context* ctx, uint64_t* with_words, uint64_t* w
         return fail(RT_ERR_INVALID_ARG, "NULL argument to rt_debug_tile_class");
     *with_words = ctx->tile_class_frames;
     *without_words = ctx->tile_noclass_frames;
+    return RT_OK;
+}
+
+rt_status rt_debug_plane_clear(rt_context* ctx, uint64_t* with_masks, uint64_t* without_masks) {
+    if (!ctx || !with_masks || !without_masks)
+        return fail(RT_ERR_INVALID_ARG, "NULL argument to rt_debug_plane_clear");
+    *with_masks = ctx->plane_mask_frames;
+    *without_masks = ctx->plane_nomask_frames;
     return RT_OK;
 }
 

@@ -86,6 +86,8 @@ struct rt_context {
     uint64_t shadow_tab_frames = 0, shadow_notab_frames = 0;
     // ... and with / without tile class words (rt_debug_tile_class)
     uint64_t tile_class_frames = 0, tile_noclass_frames = 0;
+    // ... and with class words that carry shadow-plane keep masks / without (rt_debug_plane_clear)
+    uint64_t plane_mask_frames = 0, plane_nomask_frames = 0;
     // rt_render_multi: RCCL communicators over the devices of the last context list this
     // context led (rt_multi.cpp); destroyed with the context
     std::vector<rt_context*> group_ctxs;

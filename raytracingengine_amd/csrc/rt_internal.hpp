@@ -120,7 +120,9 @@ struct TraceParams {
     // packet kernel frame batch: nframes > 0 replaces cam_pos / pk_image / pk_pub / pk_epoch
     // by fr[blockIdx.z]; frame z writes its outputs frame_px pixels after frame z - 1's
     uint32_t nframes;
-    uint32_t _pad2;
+    // host only (rt_debug_plane_clear): the class words handed to this launch carry real
+    // shadow-plane keep masks (shadow_plane_keep), not all ones
+    uint32_t plane_masks;
     uint64_t frame_px;
     PkFrame fr[kPkMaxBatch];
     // camera-ray terms that are constant over a frame, formed once on the host (camera_consts)
@@ -145,8 +147,10 @@ struct TraceParams {
     // the fix-up variant of those: the class word of every wave tile (tile_class_word,
     // rt_shadow_table.hpp), one per tile at (tby · gx + tbx) · waves + wave in the same buffer
     // after the shadow words — 0: the general path, else the tile sees only sky or only one
-    // plane and casts no shadow ray a sphere can meet (pk_uniform_tile).  Null: no tile is
-    // classified.  fr_ctab[f]: frame f's
+    // plane and casts no shadow ray a sphere can meet (pk_uniform_tile).  The class is the
+    // word's bits 0-7; bits 8 + 8·l … 15 + 8·l hold light l's shadow-plane keep mask
+    // (shadow_plane_keep; all ones: every plane is classified), on general tiles too, so readers
+    // test tile_class_of(word).  Null: no tile is classified.  fr_ctab[f]: frame f's
     const unsigned long long* class_tab;
     const unsigned long long* fr_ctab[kPkMaxBatch];
 };
@@ -224,7 +228,8 @@ struct PkConeJobs {
     // the job's cone words: dst[j] + tiles
     int32_t shadow_nl;
     // != 0 (with shadow_nl > 0 only): the tile class words too, one per tile after the shadow
-    // words: dst[j] + tiles · (1 + shadow_nl)
+    // words: dst[j] + tiles · (1 + shadow_nl); 2: with the shadow-plane keep masks formed
+    // (shadow_plane_keep), 1: with all-ones masks
     int32_t class_words;
 };
 hipError_t launch_packet_cone_tables(const TraceParams& p, const PkConeJobs& jobs,

@@ -55,7 +55,8 @@ hipError_t launch_packet_image_batch(const TraceParams& p, const PkImageJobs& jo
 // (rt_shadow_table.hpp), which depend on the cone mask it just formed: nl words per tile after
 // the job's cone words, so a batch of new cameras pays no launch of its own for them.
 // With J.class_words the lane closes with the tile's class word (tile_class_word), one per tile
-// after the shadow words: which tiles the fix-up variant renders on its uniform path.
+// after the shadow words: which tiles the fix-up variant renders on its uniform path, and which
+// planes each light's shadow rays of the tile must still classify (bits 8 and up).
 // The kernel waits more than it issues (dependent FP64 chains, one lane per tile), so it is
 // built for 5 waves per SIMD (96 VGPRs, 104 B of scratch; by itself it compiles to 3): the
 // measured times are in DESIGN §4 and profiles/shadow_table_pmc.txt.
@@ -98,10 +99,17 @@ __global__ __launch_bounds__(kConeThreads, 5) void packet_cone_table_kernel(Trac
     SB.ok = false;
     if (cone == 0)
         SB = shadow_tile_bound<2>(q, P.half_w, P.half_h, camp, dz, img + kPkSph * ns, P.np, P.bias);
-    unsigned long long any = 0;
+    // (with J.class_words == 2 each light's shadow-plane keep mask too, shadow_plane_keep: it
+    // rides in the class word, tile_class_pack; 1: all ones, nothing is taken as proven)
+    unsigned long long any = 0, keep = 0;
     for (int l = 0; l < J.shadow_nl; ++l) {
         sw[l] = shadow_tile_word(SB, P.lt + kLtStride * l, P.bias, s_ctr, 3, s_terms + 7, 8, ns);
         any |= sw[l];
+        const unsigned k = J.class_words == 2
+                               ? shadow_plane_keep<2>(SB, P.lt + kLtStride * l, img + kPkSph * ns,
+                                                      P.np, camp, P.bias)
+                               : kPlaneKeepAll;
+        keep |= static_cast<unsigned long long>(k) << (8 + 8 * l);
     }
     if (J.class_words == 0) return;
     // the tile's class word (tile_class_word), after every tile's shadow words; s_pln of the
@@ -109,7 +117,7 @@ __global__ __launch_bounds__(kConeThreads, 5) void packet_cone_table_kernel(Trac
     // stands for them (zero iff every one is; the launcher checked shadow_nl <= kShadowTabLights)
     const double* pln = img + kPkSph * ns + kPlStride * P.np + kLtStride * P.nl;
     J.dst[blockIdx.y][static_cast<size_t>(gx) * gy * waves * (1 + J.shadow_nl) + t] =
-        tile_class_word(cone, SB, &any, 1, pln, P.np);
+        tile_class_word(cone, SB, &any, 1, pln, P.np) | keep;
 }
 
 hipError_t launch_packet_cone_tables(const TraceParams& p, const PkConeJobs& jobs,
@@ -120,6 +128,7 @@ hipError_t launch_packet_cone_tables(const TraceParams& p, const PkConeJobs& job
     if (jobs.shadow_nl != 0 && jobs.shadow_nl != packet_shadow_table_lights(p))
         return hipErrorInvalidValue;
     if (jobs.class_words != 0 && jobs.shadow_nl <= 0) return hipErrorInvalidValue;
+    if (jobs.class_words < 0 || jobs.class_words > 2) return hipErrorInvalidValue;
     for (int j = 0; j < jobs.n; ++j) {
         const int f = jobs.frame[j];
         if (!jobs.dst[j] || f < -1 || f >= static_cast<int>(p.nframes) ||

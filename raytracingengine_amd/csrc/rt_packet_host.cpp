@@ -232,6 +232,11 @@ rt_status packet_image_entry(rt_context* ctx, const rt_scene* sc, const double* 
 // says whether the buffer holds them), cache entry, ring entry and caps, and counted in the
 // ring's accounting.  RTAMD_PK_TILE_CLASS=0 (read per launch): none are formed or passed, and a
 // cached table formed that way is one of its own.
+// The shadow-plane keep masks (shadow_plane_keep) ride in the class words' bits 8 and up, so they
+// share the class words' buffer, cache entry, ring entry and accounting; the key word that says
+// the buffer holds class words also says whether their masks were formed.  RTAMD_PK_PLANE_CLEAR=0
+// (read per launch): the class words carry all-ones masks — every plane is classified — and a
+// cached table formed that way is one of its own.
 constexpr size_t kMaxConeTabs = 8;
 // The ring's table memory per entry (kPkBatchRing entries), counted in cone words: a 32-frame
 // 1080p batch takes 8.3 MB (259 KB a frame), a 4K frame 1 MB; frames past the cap go without a
@@ -243,10 +248,12 @@ struct TabsWanted {
     bool cone, shadow;
     int shadow_nl;  // shadow words per tile this launch's tables hold (0: cone masks only)
     bool cls;       // the tile class words too, one per tile after the shadow words
+    bool clear;     // ... with their shadow-plane keep masks formed (else all ones)
+    int cls_kind() const { return cls ? (clear ? 2 : 1) : 0; }  // PkConeJobs.class_words
     bool any() const { return cone || shadow; }
 };
 TabsWanted tables_wanted(const rt_scene* sc, const TraceParams& p) {
-    TabsWanted w{false, false, 0, false};
+    TabsWanted w{false, false, 0, false, false};
     if (!packet_reads_cone_table(p, sc->max_specular > 0.0)) return w;
     const char* e = std::getenv("RTAMD_PK_CONE_TAB");
     w.cone = !(e && std::atoi(e) == 0);
@@ -255,6 +262,8 @@ TabsWanted tables_wanted(const rt_scene* sc, const TraceParams& p) {
     w.shadow_nl = w.shadow ? packet_shadow_table_lights(p) : 0;
     e = std::getenv("RTAMD_PK_TILE_CLASS");
     w.cls = w.cone && w.shadow && !(e && std::atoi(e) == 0);
+    e = std::getenv("RTAMD_PK_PLANE_CLEAR");
+    w.clear = w.cls && !(e && std::atoi(e) == 0);
     return w;
 }
 
@@ -267,7 +276,7 @@ TabsWanted tables_wanted(const rt_scene* sc, const TraceParams& p) {
 // bias bit for bit: the words formed at one bias are wrong masks at a larger one.  Returns the
 // table's size.
 constexpr size_t kConeKeyWords = rt_scene::PkImage::ConeTab::kKeyWords;
-size_t cone_table_key(const TraceParams& p, double dz, int shadow_nl, bool cls,
+size_t cone_table_key(const TraceParams& p, double dz, int shadow_nl, int cls,
                       uint32_t (&key)[kConeKeyWords], size_t* tiles = nullptr) {
     uint32_t gx, gy, waves;
     packet_grid(p, gx, gy, waves);
@@ -283,7 +292,8 @@ size_t cone_table_key(const TraceParams& p, double dz, int shadow_nl, bool cls,
     if (shadow_nl > 0) {
         key[15] = static_cast<uint32_t>(shadow_nl);
         std::memcpy(key + 16, &p.bias, sizeof p.bias);
-        key[18] = cls ? 1u : 0u;  // the class words follow the shadow words
+        // the class words follow the shadow words (1), with their keep masks formed (3)
+        key[18] = cls == 2 ? 3u : (cls ? 1u : 0u);
     }
     const size_t n = static_cast<size_t>(gx) * gy * waves;
     if (tiles) *tiles = n;
@@ -295,7 +305,7 @@ size_t cone_table_key(const TraceParams& p, double dz, int shadow_nl, bool cls,
 // after the launch that formed it), or a new entry whose table the caller forms (*fresh) and
 // whose event it records; null when the camera's table list is full.
 rt_status cone_table_entry(rt_context* ctx, rt_scene::PkImage& im, const TraceParams& p,
-                           double dz, int shadow_nl, bool cls,
+                           double dz, int shadow_nl, int cls,
                            rt_scene::PkImage::ConeTab** tab, bool* fresh) {
     *tab = nullptr;
     *fresh = false;
@@ -346,7 +356,7 @@ rt_status cone_table_single(rt_context* ctx, const rt_scene* sc, rt_scene::PkIma
     rt_scene::PkImage::ConeTab* t = nullptr;
     bool fresh = false;
     const rt_status st =
-        cone_table_entry(ctx, im, p, p.cam_dz, want.shadow_nl, want.cls, &t, &fresh);
+        cone_table_entry(ctx, im, p, p.cam_dz, want.shadow_nl, want.cls_kind(), &t, &fresh);
     if (st != RT_OK || !t) return st;
     if (fresh) {
         PkConeJobs jobs;
@@ -355,7 +365,7 @@ rt_status cone_table_single(rt_context* ctx, const rt_scene* sc, rt_scene::PkIma
         jobs.frame[0] = -1;
         jobs.n = 1;
         jobs.shadow_nl = want.shadow_nl;
-        jobs.class_words = want.cls ? 1 : 0;
+        jobs.class_words = want.cls_kind();
         hipError_t e = launch_packet_cone_tables(p, jobs, ctx->stream);
         if (e == hipSuccess) e = hipEventRecord(t->ready, ctx->stream);
         if (e != hipSuccess) {
@@ -365,11 +375,12 @@ rt_status cone_table_single(rt_context* ctx, const rt_scene* sc, rt_scene::PkIma
     }
     uint32_t key[kConeKeyWords];
     size_t tiles = 0;
-    (void)cone_table_key(p, p.cam_dz, want.shadow_nl, want.cls, key, &tiles);
+    (void)cone_table_key(p, p.cam_dz, want.shadow_nl, want.cls_kind(), key, &tiles);
     const unsigned long long* words = static_cast<const unsigned long long*>(t->buf.ptr);
     if (want.cone) p.cone_tab = words;
     if (want.shadow) p.shadow_tab = words + tiles;
     if (want.cls) p.class_tab = words + tiles * (1 + static_cast<size_t>(want.shadow_nl));
+    p.plane_masks = want.clear ? 1u : 0u;
     return RT_OK;
 }
 
@@ -523,7 +534,8 @@ rt_status packet_batch_images(rt_context* ctx, const rt_scene* sc, const rt_came
     uint32_t key[kConeKeyWords];
     size_t tiles = 0;
     const size_t tab_bytes =  // (the sizes only)
-        (cone_table_key(p, 0.0, want.shadow_nl, want.cls, key, &tiles) + 255) & ~size_t(255);
+        (cone_table_key(p, 0.0, want.shadow_nl, want.cls_kind(), key, &tiles) + 255) &
+        ~size_t(255);
     // (the cap counts the cone words and the class words; the shadow words come on top)
     const size_t cone_bytes =
         (sizeof(unsigned long long) * tiles * (want.cls ? 2 : 1) + 255) & ~size_t(255);
@@ -547,7 +559,8 @@ rt_status packet_batch_images(rt_context* ctx, const rt_scene* sc, const rt_came
     PkConeJobs cj;
     std::memset(&cj, 0, sizeof cj);
     cj.shadow_nl = want.shadow_nl;
-    cj.class_words = want.cls ? 1 : 0;
+    cj.class_words = want.cls_kind();
+    p.plane_masks = want.clear ? 1u : 0u;
     // the kernel's pointers of a frame whose table is (or will be) at `words`
     auto hand = [&](int f, const unsigned long long* words) {
         p.fr_tab[f] = want.cone ? words : nullptr;
@@ -578,8 +591,8 @@ rt_status packet_batch_images(rt_context* ctx, const rt_scene* sc, const rt_came
         } else {
             rt_scene::PkImage::ConeTab* t = nullptr;
             bool fresh = false;
-            st = cone_table_entry(ctx, *ent[f], p, p.fr_dz[f][0], want.shadow_nl, want.cls, &t,
-                                  &fresh);
+            st = cone_table_entry(ctx, *ent[f], p, p.fr_dz[f][0], want.shadow_nl,
+                                  want.cls_kind(), &t, &fresh);
             if (st != RT_OK || !t) continue;
             hand(f, static_cast<const unsigned long long*>(t->buf.ptr));
             if (!fresh) continue;

@@ -336,9 +336,9 @@ __device__ __forceinline__ void pk_light_record(const PacketScene& S, const Trac
     }
 }
 
-// A uniform tile of the fix-up variant (class word `cls` ≠ 0: tile_class_word,
+// A uniform tile of the fix-up variant (class c = tile_class_of(cls) ≠ 0: tile_class_word,
 // rt_shadow_table.hpp): every camera ray of the wave misses everything (kTileSky) or ends on the
-// one plane k = cls − kTilePlane0, and no shadow ray of the tile can meet a sphere.  The wave's
+// one plane k = c − kTilePlane0, and no shadow ray of the tile can meet a sphere.  The wave's
 // scene is then that plane's record, oriented normal and material row, the np ≤ 2 plane records
 // of the shadow classification and the light records: wave-uniform, read from the global packet
 // image `img` (pk_build_image's layout, no chunk bounds: ns ≤ 63) and the scene through the
@@ -350,13 +350,19 @@ __device__ __forceinline__ void pk_light_record(const PacketScene& S, const Trac
 // (the class's ordering argument), the normal is s_pln's, pk_light runs with active = true and a
 // table word of 0 (pk_occlusion_t<1, FEAT, false>: the plane loop over every plane, M.pm all
 // ones), and the shading is the kernel's own.
+// `cls` is the table's whole word: the class in its low byte and, per light, the planes the
+// tile's shadow rays must still classify (shadow_plane_keep, rt_shadow_table.hpp: a plane it
+// drops leaves the classification at a `continue` for every casting lane of the tile, so leaving
+// it out changes neither `blocked` nor `undecided`).  A light whose mask is 0 — most of C2's:
+// the kept plane lies behind its own shadow origins, the other one beyond the light — runs no
+// classification and loads no `oth` record; all ones classifies every plane as before.
 template <int MAXC, int FEAT>
 __device__ __forceinline__ d3 pk_uniform_tile(const PacketScene& S, const TraceParams& P,
                                               const double* img, unsigned long long cls, d3 cam,
                                               d3 d, int ns, int np, int nl, double bias,
                                               bool& fix) {
-    if (cls == kTileSky) return sky(d);
-    const int k = static_cast<int>(cls - kTilePlane0);
+    if (tile_class_of(cls) == kTileSky) return sky(d);
+    const int k = static_cast<int>(tile_class_of(cls) - kTilePlane0);
     const pk_cdp pl = (pk_cdp)img + kPkSph * ns;
     const pk_cdp rec = pl + kPlStride * k;
     const pk_cdp on = pl + kPlStride * np + kLtStride * nl + 4 * k;
@@ -390,13 +396,16 @@ __device__ __forceinline__ d3 pk_uniform_tile(const PacketScene& S, const TraceP
         const bool need = reach && !(ndl <= 0.0) && !(dist <= bias);
         const d3 so = hp + n * bias;
         if (!__ballot(need)) continue;  // no lane casts this shadow ray (uniform)
-        // pk_occlusion_t<1, FEAT, false>'s plane classification, every plane
+        // pk_occlusion_t<1, FEAT, false>'s plane classification, every plane the tile's mask
+        // for this light keeps (uniform: scalar branches)
         bool blocked = false, undecided = false;
-        if (need) {
+        const unsigned keep = tile_plane_keep(cls, l);
+        if (keep != 0 && need) {
             const double max_dist = dist - bias;
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
                 if (i >= np) break;
+                if (((keep >> (i == 0 ? k : 1 - k)) & 1u) == 0) continue;
                 const d3 qp = i == 0 ? pp : mk(oth[0], oth[1], oth[2]);
                 const d3 qn = i == 0 ? pn : mk(oth[3], oth[4], oth[5]);
                 const double dn = dot(qn, L);
@@ -505,7 +514,8 @@ __global__ __launch_bounds__(64 * kWgWavesX * WGY, pk_waves(MAXC, FEAT, COUNT, M
     }
     const d3 cam = mk(camp[0], camp[1], camp[2]);
     constexpr int kThreads = 64 * kWgWavesX * WGY;
-    // This wave's class word (0: the general path) and whether the workgroup stages the image:
+    // This wave's class word (class field 0: the general path; the bits above it are the
+    // lights' shadow-plane keep masks) and whether the workgroup stages the image:
     // every wave reads the adjacent words of all the workgroup's waves (one scalar load) and
     // forms the same test, so the barrier count stays uniform; a workgroup of uniform waves
     // reads no LDS afterwards (pk_uniform_tile, the epilogue) and skips the copy and its barrier.
@@ -520,7 +530,7 @@ __global__ __launch_bounds__(64 * kWgWavesX * WGY, pk_waves(MAXC, FEAT, COUNT, M
 #pragma unroll
             for (uint32_t i = 0; i < kWgWavesX * WGY; ++i) {
                 const unsigned long long c = cw[i];
-                all = all && c != kTileGeneral;
+                all = all && tile_class_of(c) != kTileGeneral;
                 if (i == w) cls = c;
             }
             staged = !all;
@@ -651,7 +661,8 @@ __global__ __launch_bounds__(64 * kWgWavesX * WGY, pk_waves(MAXC, FEAT, COUNT, M
         d3 col;
         if (P.max_rec <= 0) {
             col = sky(d);  // TraceRay at depth >= maxRecursion (Scene.h:132-134)
-        } else if (kUni && cls != kTileGeneral) {  // uniform (cls is only set with max_rec > 0)
+        } else if (kUni && tile_class_of(cls) != kTileGeneral) {
+            // uniform (cls is only set with max_rec > 0)
             if constexpr (kUni)
                 col = pk_uniform_tile<MAXC, FEAT>(S, P, pk_img, cls, cam, d, ns, np, nl, bias, fix);
         } else {

@@ -338,4 +338,107 @@ RT_CT_HD inline unsigned long long tile_class_word(unsigned long long cone,
     return kTilePlane0 + static_cast<unsigned long long>((i + kIndexOff) % np);
 }
 
+// The planes a tile's shadow rays towards the light at L must still classify: bit i stands for
+// plane i of `planes`, kPlaneKeepAll says nothing is proven.  The class word carries one such
+// mask per light next to the class (tile_class_pack), and pk_uniform_tile (rt_packet_kernel.hpp)
+// leaves a dropped plane out of its shadow classification.
+//
+// What the kernel computes.  A casting lane (`need`) has its hit point hp on the ball's plane,
+// within the ball; so = hp + n·bias with the plane's oriented unit normal n; D = unit(L − hp),
+// dist = |L − hp| > bias, max_dist = dist − bias.  For plane i (point p, stored normal q, N = |q|,
+// u = q/N) it forms dn = q·D and nm = (p − so)·q, A = nm·sign(dn), B = |dn|, and leaves the
+// plane at a `continue` — neither `blocked` nor `undecided` — when |dn| ≤ 1e-6, when
+// A < −1e-300·B, or when A ≥ max_dist·B·(1 + 1e-9).  A plane that always leaves this way can be
+// left out: no bit of T, of `fix` or of the pixel depends on it.  Below, s(x) = (x − p)·u is the
+// signed distance from plane i, m = margin·scale, and
+//   scale = |cam|₁ + |c|₁ + |L|₁ + |p|₁ + R + |bias|
+// for the ball (c, R), which bounds every coordinate and every distance that appears (hp and so
+// lie in the ball, dist ≤ |L|₁ + |c|₁ + R); 2^-200 ≤ scale ≤ 2^200 or the plane is kept, and
+// 2^-20 ≤ |q|₁ ≤ 2 holds for every plane of a bound that is ok (shadow_tile_bound).
+//
+// The ball's own plane is dropped when bias ≥ 1e-7·scale.  `need` has n·D > 0 and q = ±N·n up to
+// rounding, so dn has the sign of ±1 or |dn| ≤ 1e-6 (the first exit).  Otherwise
+// nm = (p − hp)·q − bias·(n·q) = ∓bias·N + e, A = −bias·N ± e: hp is within 6e-10·|hp − cam| of
+// the plane (the rounding budget of the ball, above) and the dot product adds 4ε·(|p|₁ + |so|₁),
+// so |e| ≤ 1e-8·scale·N, a tenth of bias·N.  A ≤ −0.9e-7·scale·N < −1e-300·B: the second exit.
+// A bias that is negative or small against the scene's coordinates keeps the plane.
+//
+// Another plane i is dropped when L and the ball lie strictly on one side of it:
+//   s(L) and s(c) have one sign,  |s(c)| − R ≥ 1e-6·scale,  |s(L)| − 2·|bias| ≥ 1e-6·scale.
+// Take s(c) > 0 (the other sign mirrors q, which leaves A and B as they are).  Every so has
+// s(so) ≥ m, so nm = −s(so)·N within 4ε·scale·N: negative, |nm| ≥ m·N·(1 − 1e-9).  dn carries
+// ≤ 5ε·|q|₁ ≤ 2.3e-15 of error, so beyond the first exit its sign is exact.  dn > 0: A = nm < 0,
+// the second exit.  dn < 0: the ray descends, s(so + t·D) = s(so) − t·B/N, and its end
+// so + max_dist·D = L + bias·(n − D) has s ≥ s(L) − 2·|bias| ≥ m.  Hence
+// s(so)·N − max_dist·B ≥ m·N, and with max_dist·B/N ≤ dist + |bias| ≤ 2·scale
+//   A / (max_dist·B) ≥ 1 + m/(2·scale) = 1 + 5e-7
+// against the third exit's 1e-9 and the relative errors of the computed A (1e-9: 4ε·scale·N
+// over m·N), B (2.3e-9: 2.3e-15 over 1e-6) and the products (4ε): 125× their sum.  The 2·|bias|
+// is needed: the ray ends bias·(n − D) off L, which can lie across the plane when n leans over
+// it and the light is closer to the plane than that.
+// The distances formed here carry ≤ 8ε·scale, ≪ m.  Any comparison that fails — a NaN, an
+// infinity, a scale out of range — keeps the plane.
+//
+// kSideOfBall = false exists for the host test's mutant only (the light's side alone decides).
+constexpr unsigned kPlaneKeepAll = 0xffu;
+template <int kMaxPlanes, bool kSideOfBall = true>
+RT_CT_HD inline unsigned shadow_plane_keep(const ShadowBound<kMaxPlanes>& B, const double* L,
+                                           const double* planes, int np, const double* cam,
+                                           double bias) {
+    if (!B.ok || np < 1 || np > kMaxPlanes || np > 8) return kPlaneKeepAll;
+    const double ab = fabs(bias);
+    const double base = ((fabs(cam[0]) + fabs(cam[1])) + fabs(cam[2])) +
+                        ((fabs(L[0]) + fabs(L[1])) + fabs(L[2])) + ab;
+    unsigned keep = 0;
+    RT_ST_UNROLL
+    for (int i = 0; i < kMaxPlanes; ++i) {
+        if (i >= np) break;
+        const double* p = planes + 8 * i;
+        const double N = sqrt((p[3] * p[3] + p[4] * p[4]) + p[5] * p[5]);
+        const double p1 = (fabs(p[0]) + fabs(p[1])) + fabs(p[2]);
+        // N·s(L)
+        const double sL = ((L[0] - p[0]) * p[3] + (L[1] - p[1]) * p[4]) + (L[2] - p[2]) * p[5];
+        bool drop = N >= 0x1p-21 && N <= 2.0;
+        RT_ST_UNROLL
+        for (int b = 0; b < kMaxPlanes; ++b) {
+            if (b >= B.n) break;
+            const ShadowBall& S = B.ball[b];
+            const double R = static_cast<double>(S.R);
+            const double scale =
+                (base + p1) + (((fabs(S.c[0]) + fabs(S.c[1])) + fabs(S.c[2])) + R);
+            if (!(scale >= 0x1p-200 && scale <= 0x1p200)) drop = false;
+            if (S.plane == i) {
+                if (!(bias >= 1e-7 * scale)) drop = false;
+                continue;
+            }
+            const double m = 1e-6 * scale * N;
+            const double sc =
+                ((S.c[0] - p[0]) * p[3] + (S.c[1] - p[1]) * p[4]) + (S.c[2] - p[2]) * p[5];
+            if (!((sL > 0.0 && sc > 0.0) || (sL < 0.0 && sc < 0.0)) && kSideOfBall) drop = false;
+            if (!(fabs(sc) - R * N >= m) && kSideOfBall) drop = false;
+            if (!(fabs(sL) - 2.0 * ab * N >= m)) drop = false;
+        }
+        if (!drop) keep |= 1u << i;
+    }
+    return keep;
+}
+
+// The class word as the table holds it: the class in bits 0-7 (tile_class_of), light l's keep
+// mask in bits 8 + 8·l … 15 + 8·l (np ≤ 8, nl ≤ kShadowTabLights).  Every tile carries its
+// masks, the general ones too, so a reader tests the class field, never the word.
+constexpr unsigned long long kTileClassBits = 0xffull;
+RT_CT_HD inline unsigned long long tile_class_of(unsigned long long word) {
+    return word & kTileClassBits;
+}
+RT_CT_HD inline unsigned long long tile_class_pack(unsigned long long cls, const unsigned* keep,
+                                                   int nl) {
+    unsigned long long w = cls & kTileClassBits;
+    for (int l = 0; l < nl && l < kShadowTabLights; ++l)
+        w |= static_cast<unsigned long long>(keep[l] & kPlaneKeepAll) << (8 + 8 * l);
+    return w;
+}
+RT_CT_HD inline unsigned tile_plane_keep(unsigned long long word, int l) {
+    return static_cast<unsigned>(word >> (8 + 8 * l)) & kPlaneKeepAll;
+}
+
 }  // namespace rtamd
