@@ -203,5 +203,17 @@ def ref_render(sc: SceneData, repeat: int = 1, threads: int | None = None, want_
         return img, info["ms"], info["threads"]
 
 
+def ref_current() -> bool:
+    """The harness was built from this tree's ref_harness.cpp (its `version` mode prints the
+    SHA-256 prefix of its source; a binary from before that mode prints nothing)."""
+    import hashlib
+    if not ref_available():
+        return False
+    with open(os.path.join(HERE, "ref_harness.cpp"), "rb") as fh:
+        want = hashlib.sha256(fh.read()).hexdigest()[:16]
+    res = subprocess.run([REF_HARNESS, "version"], capture_output=True, text=True)
+    return res.stdout.strip() == want
+
+
 def ref_run(mode: str, *args: str) -> None:
     subprocess.run([REF_HARNESS, mode, *map(str, args)], check=True, capture_output=True)

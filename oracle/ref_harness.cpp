@@ -12,11 +12,25 @@
 //   curves  <in.f64> <n> <out.f64>            the 7 operator curves before toColor → 7*n*3
 //   kat     sphere|plane|triangle|getray <in.f64> <n> <out.f64>
 //   closest <scene.txt> <rays.f64> <n> <out.f64>   IntersectClosest → n*9 doubles
-//   trace   <scene.txt> <rays.f64> <n> <bias> <out.f64>  Scene::TraceRay(ray, 0, bias) → n*3
+//   trace   <scene.txt> <rays.f64> <n> <bias> <out.f64> [max_recursion]
+//                                             Scene::TraceRay(ray, 0, bias) → n*3, with
+//                                             scene.maxRecursion set when given (default 10)
+//   anybefore <scene.txt> <rays.f64> <dist.f64> <n> <out.u8>
+//                                             Scene::IntersectAnyBefore(ray, maxDist) → n bytes 0/1
+//   transmit <scene.txt> <rays.f64> <dist.f64> <n> <bias> <out.f64>
+//                                             Scene::computeTransmittance(ray, maxDist, bias) → n
+//   direct  <scene.txt> <points.f64 n*9> <materials.f64 n*7> <n> <bias> <out.f64 n*9> [light]
+//                                             Scene::directLightning three times per point
+//                                             {p, normal, view}: → {radiance, diffuse accumulator,
+//                                             specular accumulator}; with `light`, the scene is
+//                                             built with that one light only
 //   ppm     <in.u8> <w> <h> <out.ppm>         writePPM()
+//   version                                   prints the SHA-256 prefix of this file the binary
+//                                             was built from (oracle/Makefile rebuilds on a mismatch)
 // The standard headers come first so that only the reference's own classes are seen with
 // `private` spelled `public` below: mode `trace` calls Scene::TraceRay, a private member of the
-// reference's Scene (Scene.h:131).  The reference's sources are read where they lie, unedited.
+// reference's Scene (Scene.h:131), `transmit` Scene::computeTransmittance (Scene.h:35) and `direct`
+// Scene::directLightning (Scene.h:79).  The reference's sources are read where they lie, unedited.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -172,13 +186,15 @@ Loaded load_scene(const char* path) {
     return L;
 }
 
-Scene build_scene(Loaded& L) {
+// only_light >= 0: the scene gets that one light of the file and no other.
+Scene build_scene(Loaded& L, long only_light = -1) {
     Scene s(L.camera);
     for (auto& x : L.spheres) s.AddSphere(x);
     for (auto& x : L.planes) s.AddPlane(x);
     for (auto& x : L.triangles) s.AddTriangle(x);
     for (auto& x : L.models) s.AddModel(x);
-    for (auto& x : L.lights) s.AddLight(x);
+    for (size_t i = 0; i < L.lights.size(); ++i)
+        if (only_light < 0 || static_cast<size_t>(only_light) == i) s.AddLight(L.lights[i]);
     return s;
 }
 
@@ -341,6 +357,7 @@ int mode_trace(int argc, char** argv) {
     if (argc < 7) return 1;
     Loaded L = load_scene(argv[2]);
     Scene scene = build_scene(L);
+    if (argc > 7) scene.maxRecursion = std::atoi(argv[7]);
     size_t n = std::strtoull(argv[4], nullptr, 10);
     const double bias = std::strtod(argv[5], nullptr);
     auto rays = read_f64(argv[3], 6 * n);
@@ -354,6 +371,92 @@ int mode_trace(int argc, char** argv) {
         out.push_back(c.z);
     }
     write_bytes(argv[6], out.data(), out.size() * sizeof(double));
+    return 0;
+}
+
+// Scene::IntersectAnyBefore(ray, maxDist) per ray and distance: one byte each, 0 or 1.
+int mode_anybefore(int argc, char** argv) {
+    if (argc < 7) return 1;
+    Loaded L = load_scene(argv[2]);
+    Scene scene = build_scene(L);
+    size_t n = std::strtoull(argv[5], nullptr, 10);
+    auto rays = read_f64(argv[3], 6 * n);
+    auto dist = read_f64(argv[4], n);
+    std::vector<uint8_t> out(n);
+    for (size_t i = 0; i < n; ++i) {
+        const double* r = &rays[6 * i];
+        Rayon ray(Vec3(r[0], r[1], r[2]), Vec3(r[3], r[4], r[5]));
+        out[i] = scene.IntersectAnyBefore(ray, dist[i]) ? 1 : 0;
+    }
+    write_bytes(argv[6], out.data(), out.size());
+    return 0;
+}
+
+// Scene::computeTransmittance(ray, maxDist, bias) per ray and distance.
+int mode_transmit(int argc, char** argv) {
+    if (argc < 8) return 1;
+    Loaded L = load_scene(argv[2]);
+    Scene scene = build_scene(L);
+    size_t n = std::strtoull(argv[5], nullptr, 10);
+    const double bias = std::strtod(argv[6], nullptr);
+    auto rays = read_f64(argv[3], 6 * n);
+    auto dist = read_f64(argv[4], n);
+    std::vector<double> out(n);
+    for (size_t i = 0; i < n; ++i) {
+        const double* r = &rays[6 * i];
+        Rayon ray(Vec3(r[0], r[1], r[2]), Vec3(r[3], r[4], r[5]));
+        out[i] = scene.computeTransmittance(ray, dist[i], bias);
+    }
+    write_bytes(argv[7], out.data(), out.size() * sizeof(double));
+    return 0;
+}
+
+// Scene::directLightning(HitInfo{hitPoint, material}, viewDir, normal, bias) per point
+// {p, normal, view} and material {colour, shininess, specular, transparency, refractiveIndex}.
+// The function returns colour * diffuseAccumulation + specularAccumulation * specular
+// (Scene.h:126-128), so its two accumulators are read through two more calls with other
+// materials: colour (1,1,1) and specular 0 closes the specular branch (Scene.h:115) and returns
+// the diffuse accumulator; colour (0,0,0) and specular 1, transparency and shininess unchanged,
+// returns the specular accumulator (0 * diffuseAccumulation is NaN where that is not finite).
+// Where the point's own specular is not > 0 the branch is closed for it: written as zero.
+int mode_direct(int argc, char** argv) {
+    if (argc < 8) return 1;
+    Loaded L = load_scene(argv[2]);
+    Scene scene = build_scene(L, argc > 8 ? std::atol(argv[8]) : -1);
+    size_t n = std::strtoull(argv[5], nullptr, 10);
+    const double bias = std::strtod(argv[6], nullptr);
+    auto pts = read_f64(argv[3], 9 * n);
+    auto mats = read_f64(argv[4], 7 * n);
+    std::vector<double> out;
+    auto push = [&](const Vec3& v) {
+        out.push_back(v.x);
+        out.push_back(v.y);
+        out.push_back(v.z);
+    };
+    for (size_t i = 0; i < n; ++i) {
+        const double* p = &pts[9 * i];
+        const double* m = &mats[7 * i];
+        const Vec3 normal(p[3], p[4], p[5]), view(p[6], p[7], p[8]);
+        Material own;
+        own.color = Vec3(m[0], m[1], m[2]);
+        own.shininess = m[3];
+        own.specular = m[4];
+        own.transparency = m[5];
+        own.refractiveIndex = m[6];
+        HitInfo hit{HitType::NONE, 0.0, 0, own, normal, Vec3(p[0], p[1], p[2])};
+        push(scene.directLightning(hit, view, normal, bias));
+        hit.material.color = Vec3(1.0, 1.0, 1.0);
+        hit.material.specular = 0.0;
+        push(scene.directLightning(hit, view, normal, bias));
+        if (own.specular > 0.0) {
+            hit.material.color = Vec3(0.0, 0.0, 0.0);
+            hit.material.specular = 1.0;
+            push(scene.directLightning(hit, view, normal, bias));
+        } else {
+            push(Vec3(0.0, 0.0, 0.0));
+        }
+    }
+    write_bytes(argv[7], out.data(), out.size() * sizeof(double));
     return 0;
 }
 
@@ -391,10 +494,17 @@ int mode_obj(int argc, char** argv) {
 
 int main(int argc, char** argv) {
     if (argc < 2) {
-        std::fprintf(stderr, "usage: ref_harness render|tonemap|curves|kat|closest|trace|ppm ...\n");
+        std::fprintf(stderr, "usage: ref_harness render|tonemap|curves|kat|closest|trace|anybefore|transmit|"
+                             "direct|ppm|obj ...\n");
         return 1;
     }
     std::string m = argv[1];
+    if (m == "version") {
+#ifdef HARNESS_SHA
+        std::printf("%s\n", HARNESS_SHA);
+#endif
+        return 0;
+    }
     int rc = 1;
     if (m == "render") rc = mode_render(argc, argv);
     else if (m == "tonemap") rc = mode_tonemap(argc, argv);
@@ -402,6 +512,9 @@ int main(int argc, char** argv) {
     else if (m == "kat") rc = mode_kat(argc, argv);
     else if (m == "closest") rc = mode_closest(argc, argv);
     else if (m == "trace") rc = mode_trace(argc, argv);
+    else if (m == "anybefore") rc = mode_anybefore(argc, argv);
+    else if (m == "transmit") rc = mode_transmit(argc, argv);
+    else if (m == "direct") rc = mode_direct(argc, argv);
     else if (m == "ppm") rc = mode_ppm(argc, argv);
     else if (m == "obj") rc = mode_obj(argc, argv);
     if (rc == 1) std::fprintf(stderr, "bad arguments for mode %s\n", m.c_str());

@@ -6,7 +6,12 @@
  * used as the parity checker by tests/, __graft_entry__.smoke() and bench.py's cpu_baseline
  * leg ("port").  Its equality with the compiled reference (oracle/_ref, built by
  * oracle/Makefile from the reference sources where they lie) is pinned by the golden vectors
- * under tests/golden/ (tests/test_oracle_golden.py).
+ * under tests/golden/ (tests/test_oracle_golden.py).  The batch queries are pinned by
+ * tests/golden/query_tables.npz (tests/test_reference_queries.py): oracle_transmittance on the
+ * scene, grid, crafted, non-finite and shadow-ray tables, oracle_closest_rays on every crafted
+ * and non-finite ray set, oracle_trace_rays at max_recursion 0, 1, 2, 3 and 16 and on the
+ * non-finite rays, and — through tests/occlusion_sets.py — the per-shape Intersect functions
+ * against Scene::IntersectAnyBefore.
  *
  * The scene structs below have the byte layout of include/rt_capi.h's rt_* structs (the same
  * host buffers are handed to both), but the oracle does not include that header: it stays

@@ -227,6 +227,41 @@ def lowspec_set() -> dict:
                 **expected(sc, h["points"], h["materials"]))
 
 
+def bias_edge_transparencies(bias: float = BIAS) -> tuple:
+    """bias itself, one unit in the last place above it and one below."""
+    return (bias, raysets.step(bias, 1), raysets.step(bias, -1))
+
+
+def bias_edge_scene(bias: float = BIAS) -> SceneData:
+    """Three triangles side by side in the plane y = 5 under one light, their transparencies
+    bias_edge_transparencies: a shadow ray crosses one triangle once, so the clamp leaves that
+    transparency and T = 1.0 * transparency is it exactly.  directLightning drops the light at
+    T <= bias (Scene.h:105): under the first and the third triangle, not under the second."""
+    sc = SceneData(raysets._cam(), name="dl_bias_edge")
+    for k, tr in enumerate(bias_edge_transparencies(bias)):
+        x = 4.0 * (k - 1)
+        sc.add_triangle((x - 2.0, 5.0, -3.0), (x + 2.0, 5.0, -3.0), (x, 5.0, 4.0),
+                        Material((0.9, 0.9, 1.0), transparency=tr))
+    sc.add_light((0.0, 50.0, 0.0), (1.0, 0.9, 0.8), 4000.0)
+    return sc
+
+
+BIAS_EDGE_POINTS = 4   # per triangle
+
+
+@functools.lru_cache(maxsize=None)
+def bias_edge_set(bias: float = BIAS) -> dict:
+    """Points on the plane y = 0 under each triangle of bias_edge_scene (BIAS_EDGE_POINTS each,
+    triangle after triangle), facing up, with an opaque specular material."""
+    sc = bias_edge_scene(bias)
+    pts = np.array([[4.0 * (k - 1) + 0.125 * j, 0.0, 0.125 * j, 0.0, 1.0, 0.0, 0.25, 1.0, -0.5]
+                    for k in range(3) for j in range(BIAS_EDGE_POINTS)], np.float64)
+    mats = np.array([[0.8, 0.7, 0.6, 16.0, 0.4, 0.0, 1.0]], np.float64)
+    pts.setflags(write=False)
+    mats.setflags(write=False)
+    return dict(sc=sc, points=pts, materials=mats, bias=bias, **expected(sc, pts, mats, bias))
+
+
 # ------------------------------------------------------------------ non-finite inputs
 SPECIALS = (0.0, -0.0, np.nan, np.inf, -np.inf, 2.0 ** 500, -(2.0 ** -500), 5e-324)
 

@@ -10,15 +10,18 @@ and the reference's outputs for them.  The reference has no tests or fixtures of
     python tests/golden/make_golden.py --full [name ...]  # full-size frames (FULL2_SCENES)
     python tests/golden/make_golden.py --oracle-full      # C5 (no reference semantics): oracle
     python tests/golden/make_golden.py --rays             # ray_queries.npz only (tests/raysets.py)
+    python tests/golden/make_golden.py --queries          # query_tables.npz only (the batch queries)
 """
 from __future__ import annotations
 
 import hashlib
+import io
 import json
 import os
 import subprocess
 import sys
 import tempfile
+import zipfile
 
 import numpy as np
 
@@ -331,8 +334,93 @@ def ray_queries_golden():
     print("ray_queries.npz", os.path.getsize(path), "bytes")
 
 
+def save_npz(path, arrays: dict):
+    """np.savez_compressed with every member's timestamp fixed: the same arrays give the same
+    bytes, so a regenerated fixture can be compared with the committed one."""
+    with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED, compresslevel=9) as zf:
+        for key, a in arrays.items():
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, np.asanyarray(a), allow_pickle=False)
+            info = zipfile.ZipInfo(key + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            info.external_attr = 0o644 << 16
+            zf.writestr(info, buf.getvalue(), compresslevel=9)
+
+
+def run_query_case(c, td):
+    """One reference_query_sets case through oracle/_ref/ref_harness: the answer as an array."""
+    scene_path, out = os.path.join(td, "scene.txt"), os.path.join(td, "out.bin")
+    c["sc"].write(scene_path)
+    paths = []
+    for k, a in enumerate(c["inputs"]):
+        paths.append(os.path.join(td, f"in{k}.f64"))
+        a.tofile(paths[-1])
+    n = len(c["inputs"][0])
+    mode = c["mode"]
+    if mode == "anybefore":
+        run(mode, scene_path, *paths, n, out)
+        return np.fromfile(out, np.uint8)
+    if mode == "transmit":
+        run(mode, scene_path, *paths, n, repr(c["bias"]), out)
+        return np.fromfile(out, np.float64)
+    if mode == "direct":
+        run(mode, scene_path, *paths, n, repr(c["bias"]), out, *c["extra"])
+        return np.fromfile(out, np.float64).reshape(n, 9)
+    if mode == "trace":
+        run(mode, scene_path, *paths, n, repr(c["bias"]), out, *c["extra"])
+        return np.fromfile(out, np.float64).reshape(n, 3)
+    if mode == "closest":
+        run(mode, scene_path, *paths, n, out)
+        return np.fromfile(out, np.float64).reshape(n, 9)
+    raise ValueError(mode)
+
+
+def queries_golden(out_dir=HERE):
+    """``--queries``: what the compiled reference answers to every case of
+    tests/reference_query_sets.py — Scene::IntersectAnyBefore, computeTransmittance,
+    directLightning, TraceRay at several recursion limits and IntersectClosest on the inputs the
+    batch-query tests use.  Writes <out_dir>/query_tables.npz: per case `key` the
+    answer and `key#in`, the SHA-256 of the scene text and of each input array and the trailing
+    parameters; the inputs themselves are not stored.  A one-light directLightning case keeps its
+    diffuse accumulator only.  Written next to this file, it also records its provenance under
+    "queries" in golden_meta.json.  Returns the path."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import reference_query_sets as rq
+    if not po.ref_current():      # absent, or built from another ref_harness.cpp
+        po.build()
+    assert po.ref_current(), "oracle/_ref/ref_harness missing or stale (needs the reference sources)"
+    out = {"bias": np.float64(rq.BIAS)}
+    with tempfile.TemporaryDirectory() as td:
+        for c in rq.cases():
+            ans = run_query_case(c, td)
+            if c["key"].startswith("dl/light/"):
+                ans = np.ascontiguousarray(ans[:, 3:6])
+            out[c["key"]] = ans
+            out[c["key"] + "#in"] = rq.case_hashes(c)
+    path = os.path.join(out_dir, rq.FIXTURE)
+    save_npz(path, out)
+    if os.path.abspath(out_dir) == HERE:
+        modes = sorted({c["mode"] for c in rq.cases()})
+        meta_path = os.path.join(HERE, "golden_meta.json")
+        with open(meta_path) as fh:
+            meta = json.load(fh)
+        meta["queries"] = {
+            "fixture": rq.FIXTURE, "generator": "tests/golden/make_golden.py --queries",
+            "cases": "tests/reference_query_sets.py cases()", "n_cases": (len(out) - 1) // 2,
+            "harness_modes": modes, "bias": rq.BIAS, "trace_max_recursion": list(rq.TRACE_DEPTHS),
+            "seeds": "tests/raysets.py _rng: numpy default_rng([20261019, crc32(set name)]); "
+                     "sph300: SplitMix64(0x5EED0300)",
+            "stored": "answers and SHA-256 of scene text and input arrays; inputs not stored"}
+        with open(meta_path, "w") as fh:
+            json.dump(meta, fh, indent=1, sort_keys=True)
+    print(rq.FIXTURE, os.path.getsize(path), "bytes,", (len(out) - 1) // 2, "cases")
+    return path
+
+
 if __name__ == "__main__":
-    if "--rays" in sys.argv:
+    if "--queries" in sys.argv:
+        queries_golden()
+    elif "--rays" in sys.argv:
         ray_queries_golden()
     elif "--refapp" in sys.argv:
         refapp_golden()
