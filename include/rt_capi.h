@@ -28,6 +28,10 @@
  *   rt_closest_rays[_device]       std::optional<HitInfo> Scene::IntersectClosest(ray) const
  *                                  Scene.h:218-257 (and HitInfo::material, Shape.h:28-38)
  *   rt_trace_rays[_device]         Vec3 Scene::TraceRay(ray, 0, bias) const   Scene.h:131-198
+ *   rt_accumulate_samples[_device] the sample loop of Scene::GeneratePixelAt   Scene.h:283-304
+ *                                  (Scene.h:289-297, for a range of its AA samples, into a resident sum)
+ *   rt_resolve[_device]            GeneratePixelAt's division by the sample count   Scene.h:298-300,
+ *                                  then tonemap()/toColor() as rt_tonemap
  *   rt_tonemap                     tonemap() RaytracingEngine.cpp:165-174 and the operators of
  *                                  tonemapAll() RaytracingEngine.cpp:176-214, each followed by
  *                                  toColor() RaytracingEngine.cpp:113-121
@@ -728,6 +732,63 @@ rt_status rt_closest_rays_device(rt_context* ctx, const rt_scene* scene,
  * context or scene, a NULL pointer with n > 0.  n == 0 returns RT_OK. */
 rt_status rt_trace_rays_device(rt_context* ctx, const rt_scene* scene, const rt_render_opts* opts,
                                const void* d_rays, size_t n, void* d_rgb);
+
+/* Progressive frames: Scene::GeneratePixelAt (Scene.h:283-304) cut at any AA sample.  For every
+ * pixel px of the row set of opts:
+ *   sum[px] = (sample_begin == 0 ? +0.0 : sum[px]);
+ *   for s in [sample_begin, sample_end):
+ *       sum[px] = sum[px] + TraceRay(camera ray of sample s at px, 0, bias)
+ * the loop of Scene.h:289-297 in its order, so that
+ *   rt_render_device == rt_resolve_device(rt_accumulate_samples_device(0, N), N),  N = aa_samples,
+ * bit for bit wherever the frame equals its samples' TraceRay summed in order (rt_camera_rays
+ * above), and the frame can be cut after any sample: a preview after the first, refinement while
+ * the camera rests, 28 samples added to 4 that exist.
+ * d_sum: rows*W*3 doubles, row-major and rows-local like rt_render_device's hdr64.
+ * Which rays: the ray of sample s is rt_camera_rays' ray, Camera::getRay(x, y, s > 0 &&
+ *   aa_samples > 1): sample 0 is never jittered, samples above 0 only when aa_samples > 1, and the
+ *   RNG key is the image pixel y_image*W + x (with opts->seed and s).
+ * Which TraceRay: the device function rt_trace_rays selects for the scene and opts (no secondary
+ *   ray, reflection chain or refraction tree), with its RT_ERR_UNSUPPORTED for a max_recursion
+ *   above the kernels' limit with reflective or transparent materials.
+ * Area light: with an area light attached its random numbers are keyed by (pixel, s), as the
+ *   render kernels key them — not by a ray's index, as rt_trace_rays keys them — so the frame of
+ *   an area-light scene is reproduced too.
+ * The sum: with sample_begin == 0 the previous contents of d_sum are not read (no memset is
+ *   needed, NaN garbage is harmless); with sample_begin > 0 they are.  The fold is sequential:
+ *   only continuing ONE sum is bit-exact.  Adding two separately accumulated ranges,
+ *   accumulate(0, k) + accumulate'(k, N), rounds in another order than the reference and is not
+ *   its frame.
+ * Of opts the call reads max_recursion, bias, seed, the row set (row_begin / row_end / row_block /
+ *   row_cycle) and RT_FLAG_NO_BVH; tonemap and the other flags are ignored.  opts == NULL gives
+ *   the defaults.  The packet, box and breadth-first render kernels are not used: one thread per
+ *   pixel runs the generic TraceRay.
+ * RT_ERR_INVALID_ARG: sample_begin < 0, sample_begin >= sample_end, sample_end > max(1,
+ *   aa_samples), a NULL context, scene, camera or sum, zero width or height, a row set outside the
+ *   image.  Asynchronous on the context's stream; no host memory is touched. */
+rt_status rt_accumulate_samples_device(rt_context* ctx, const rt_scene* scene,
+                                       const rt_camera* cam, const rt_render_opts* opts,
+                                       int sample_begin, int sample_end, void* d_sum);
+/* The same on a host sum (in and out: read only when sample_begin > 0), synchronous. */
+rt_status rt_accumulate_samples(rt_context* ctx, const rt_scene* scene, const rt_camera* cam,
+                                const rt_render_opts* opts, int sample_begin, int sample_end,
+                                double* sum);
+
+/* Resolve a sum, or any FP64 radiance buffer, on the device: per pixel v = sum / (double)samples
+ * (GeneratePixelAt's division, Scene.h:298-300, the render kernels' own), then what a render
+ * writes: d_hdr64 (v, n*3 doubles), d_hdr32 ((float)v, n*3 floats) and d_ldr (toColor(op(v))).
+ * Any output may be NULL, not all of them.  d_hdr64 may be d_sum itself.
+ * tonemap in [0, RT_TONEMAP_COUNT): n*3 bytes; RT_TONEMAP_COUNT: seven planes in tonemapAll()
+ * order, 7*n*3 bytes, as rt_tonemap; RT_TONEMAP_NONE only with d_ldr NULL.
+ * Device tonemap: rt_resolve_device(ctx, d_hdr, n, 1, op, NULL, NULL, d_ldr) is rt_tonemap on
+ * device pointers — the division by 1.0 is exact — with rt_tonemap's bytes.
+ * RT_ERR_INVALID_ARG: samples < 1, an unknown tonemap, every output NULL, d_ldr with
+ * RT_TONEMAP_NONE, a NULL sum with n_pixels > 0, a NULL context.  n_pixels == 0 returns RT_OK.
+ * Asynchronous on the context's stream; no host memory is touched. */
+rt_status rt_resolve_device(rt_context* ctx, const void* d_sum, size_t n_pixels, int samples,
+                            int tonemap, void* d_hdr64, void* d_hdr32, void* d_ldr);
+/* The same on host pointers, synchronous. */
+rt_status rt_resolve(rt_context* ctx, const double* sum, size_t n_pixels, int samples, int tonemap,
+                     double* hdr64, float* hdr32, uint8_t* ldr);
 
 /* Device tonemap of host FP64 radiance: op in [0, RT_TONEMAP_COUNT) writes n*3 bytes;
  * op == RT_TONEMAP_COUNT writes all seven operators, tonemapAll() order, 7*n*3 bytes. */

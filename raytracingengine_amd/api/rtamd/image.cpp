@@ -49,4 +49,25 @@ std::vector<std::vector<Color>> tonemapAll(const std::vector<Vec3> pixels) {
     return all;
 }
 
+std::vector<Vec3> resolve(const std::vector<Vec3>& sum, int samples) {
+    std::vector<Vec3> out(sum.size(), Vec3(0, 0, 0));
+    double none[3];  // with no pixel the entry still checks `samples`
+    check(rt_resolve(thread_context(current_device()),
+                     reinterpret_cast<const double*>(sum.data()), sum.size(), samples,
+                     RT_TONEMAP_NONE, out.empty() ? none : reinterpret_cast<double*>(out.data()),
+                     nullptr, nullptr),
+          "rt_resolve");
+    return out;
+}
+
+std::vector<Color> resolveTonemapped(const std::vector<Vec3>& sum, int samples, int op) {
+    std::vector<Color> out(sum.size());
+    uint8_t none[3];
+    check(rt_resolve(thread_context(current_device()),
+                     reinterpret_cast<const double*>(sum.data()), sum.size(), samples, op, nullptr,
+                     nullptr, out.empty() ? none : reinterpret_cast<uint8_t*>(out.data())),
+          "rt_resolve");
+    return out;
+}
+
 }  // namespace rtamd

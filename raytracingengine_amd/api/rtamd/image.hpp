@@ -26,6 +26,14 @@ std::vector<Color> tonemap(const std::vector<Vec3>& pixels);
 // tonemapAll(): simple, reinhardSimple, reinhardExtended, reinhardExtendedLuminance,
 // reinhardJodie, uncharted2, aces — one device pass (RaytracingEngine.cpp:176-214).
 std::vector<std::vector<Color>> tonemapAll(const std::vector<Vec3> pixels);
+// A sum of AA samples (Scene::AccumulateSamples) as a frame, on the GPU (rt_resolve):
+// sum[i] / (double)samples, GeneratePixelAt's division (Scene.h:298-300) — with every sample of
+// the camera in the sum, RenderImage()'s pixels.  samples >= 1.
+std::vector<Vec3> resolve(const std::vector<Vec3>& sum, int samples);
+// The byte form: toColor(op(sum[i] / samples)) in the same pass; op is an rt_tonemap_op.  With
+// samples = 1 it is tonemapOp(sum, op).
+std::vector<Color> resolveTonemapped(const std::vector<Vec3>& sum, int samples,
+                                     int op = 6 /* RT_TONEMAP_ACES, tonemap()'s */);
 }  // namespace rtamd
 
 #ifdef RTAMD_GLOBAL_TONEMAP

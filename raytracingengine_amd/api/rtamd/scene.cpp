@@ -554,6 +554,21 @@ std::vector<Rayon> Scene::CameraRays(int sample) const {
     return rays;
 }
 
+void Scene::AccumulateSamples(int begin, int end, std::vector<Vec3>& sum) const {
+    static_assert(sizeof(Vec3) == 3 * sizeof(double), "Vec3 is not three packed doubles");
+    const size_t n = camera.width * camera.height;
+    if (begin == 0) sum.assign(n, Vec3(0, 0, 0));
+    else if (sum.size() != n)
+        throw std::runtime_error("AccumulateSamples: begin > 0 needs the frame's sum so far");
+    rt_scene* sc = upload();
+    const rt_camera cam = cameraDesc();
+    const rt_render_opts o = optsDesc(RT_TONEMAP_NONE);
+    double none[3];  // with no pixel the entry still checks the camera and the sample range
+    rtamd::check(rt_accumulate_samples(dev_->ctx, sc, &cam, &o, begin, end,
+                                       sum.empty() ? none : reinterpret_cast<double*>(sum.data())),
+                 "rt_accumulate_samples");
+}
+
 rtamd::Hits Scene::IntersectClosest(const std::vector<Rayon>& rays) const {
     static_assert(sizeof(Rayon) == 6 * sizeof(double), "Rayon is not six packed doubles");
     static_assert(sizeof(rt_material) == 7 * sizeof(double), "rt_material is not seven doubles");

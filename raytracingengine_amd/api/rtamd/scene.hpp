@@ -20,6 +20,9 @@
 //   TraceRays(rays, bias)      → rt_trace_rays (TraceRay(ray, 0, bias) for n rays at once)
 //   CameraRays(sample)         → rt_camera_rays (Camera::getRay for every pixel, Math.h:99-121)
 //   IntersectClosest(rays)     → rt_closest_rays (Scene.h:218-257 for n rays at once)
+//   AccumulateSamples(b, e, sum) → rt_accumulate_samples (GeneratePixelAt's sample loop,
+//                              Scene.h:289-297, for a range of its samples; rtamd::resolve in
+//                              image.hpp divides, Scene.h:298-300)
 // The single-ray IntersectAnyBefore(ray, maxDist) of the reference's signature stays a host
 // utility over the shapes' Intersect members: one ray per launch would pay an upload, a launch
 // and a download to learn one bit; the batch overloads give the same answers for many rays.
@@ -203,6 +206,13 @@ public:
     // C-ABI's {type, index}: a triangle's index counts the standalone triangles first, then each
     // model's.
     rtamd::Hits IntersectClosest(const std::vector<Rayon>& rays) const;
+    // Progressive frames (rt_accumulate_samples): for every pixel (row-major, GetPixelIndex),
+    // sum += TraceRay(CameraRays(s) of the pixel, 0, bias) for s in [begin, end), GeneratePixelAt's
+    // loop (Scene.h:289-297) in its order.  begin == 0 starts the sum (it is resized to the frame
+    // and its contents are not read); begin > 0 continues it (it must hold the frame's pixels).
+    // 0 <= begin < end <= max(1, antiAliasingAmount).  rtamd::resolve(sum, end) (image.hpp) is the
+    // frame after `end` samples; with end = antiAliasingAmount it is RenderImage(), bit for bit.
+    void AccumulateSamples(int begin, int end, std::vector<Vec3>& sum) const;
     void SetDevice(int device) { device_ = device; dev_.reset(); devices_.clear(); }
     // RenderImage / RenderImageTonemapped / RenderImageF32 over several GPUs of the node from
     // this process: one scene copy per GPU, block-cyclic rows, assembled on the host (distinct

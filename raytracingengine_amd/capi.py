@@ -103,6 +103,8 @@ EXPORTED = [
     "rt_camera_rays", "rt_camera_rays_device",
     "rt_closest_rays", "rt_closest_rays_device",
     "rt_trace_rays_device",
+    "rt_accumulate_samples", "rt_accumulate_samples_device",
+    "rt_resolve", "rt_resolve_device",
 ]
 
 
@@ -267,6 +269,10 @@ def load_library(path: str = LIB_PATH):
         "rt_closest_rays": [vp, vp, vp, vp, ctypes.c_size_t, i32, vp],
         "rt_closest_rays_device": [vp, vp, vp, vp, ctypes.c_size_t, i32, vp],
         "rt_trace_rays_device": [vp, vp, vp, vp, ctypes.c_size_t, vp],
+        "rt_accumulate_samples": [vp, vp, vp, vp, i32, i32, vp],
+        "rt_accumulate_samples_device": [vp, vp, vp, vp, i32, i32, vp],
+        "rt_resolve": [vp, vp, ctypes.c_size_t, i32, i32, vp, vp, vp],
+        "rt_resolve_device": [vp, vp, ctypes.c_size_t, i32, i32, vp, vp, vp],
         "rt_tonemap": [vp, vp, ctypes.c_size_t, i32, vp],
         "rt_debug_f64_ops": [vp, vp, vp, ctypes.c_size_t, vp],
         "rt_debug_vec_ops": [vp, vp, ctypes.c_size_t, vp],
@@ -348,6 +354,17 @@ def default_opts(**kw) -> RenderOpts:
 
 def device_count() -> int:
     return load_library().rt_device_count()
+
+
+def progressive_schedule(aa_samples: int) -> list:
+    """The default steps of DeviceScene.render_progressive: the sample counts 1, 2, 4, ... below
+    max(1, aa_samples), then that count itself.  A pure function."""
+    n = max(1, int(aa_samples))
+    steps, k = [], 1
+    while k < n:
+        steps.append(k)
+        k *= 2
+    return steps + [n]
 
 
 class Context:
@@ -937,6 +954,127 @@ class DeviceScene:
                                          rays.data_ptr() if n else None, n,
                                          out.data_ptr() if n else None))
         return out
+
+    def accumulate(self, sample_begin: int, sample_end: int, sum=None, cam=None,
+                   **opts) -> np.ndarray:
+        """Add the AA samples [sample_begin, sample_end) of every pixel of the row set of opts to
+        a host sum (rt_accumulate_samples): float64 [rows*W, 3], GeneratePixelAt's loop in its
+        order.  sum: the sum so far, required when sample_begin > 0 (a contiguous float64 array of
+        rows*W*3 elements is updated in place and returned); with sample_begin == 0 its contents
+        are not read.  cam as camera_rays; opts: max_recursion, bias, seed, the row set, flags."""
+        rec, w, h = self._camera_record(cam)
+        o = default_opts(**opts)
+        n = rendered_rows(o, h) * w
+        if sum is None:
+            if sample_begin > 0:
+                raise ValueError("sum: required when sample_begin > 0")
+            sum = np.empty((n, 3), np.float64)
+        elif not (isinstance(sum, np.ndarray) and sum.dtype == np.float64
+                  and sum.flags.c_contiguous and sum.flags.writeable and sum.size == 3 * n):
+            sum = np.array(sum, np.float64).reshape(n, 3)
+        _check(_lib.rt_accumulate_samples(self.ctx.handle, self._h, rec.ctypes.data,
+                                          ctypes.byref(o), sample_begin, sample_end,
+                                          sum.ctypes.data or 8))
+        return sum.reshape(n, 3)
+
+    def accumulate_device(self, sample_begin: int, sample_end: int, sum=None, cam=None, **opts):
+        """Asynchronous rt_accumulate_samples_device on the context's stream: the sum of
+        accumulate() as a float64 [rows*W, 3] torch tensor on the context's device.  sum: the
+        tensor to add to (contiguous float64, at least rows*W*3 elements, returned as it is),
+        required when sample_begin > 0; with sample_begin == 0 it need not be initialised."""
+        import torch
+        dev = torch.device(f"cuda:{self.ctx.device}")
+        rec, w, h = self._camera_record(cam)
+        o = default_opts(**opts)
+        n = rendered_rows(o, h) * w
+        if sum is None:
+            if sample_begin > 0:
+                raise ValueError("sum: required when sample_begin > 0")
+            sum = torch.empty((n, 3), dtype=torch.float64, device=dev)
+        elif (sum.dtype != torch.float64 or sum.device != dev or sum.numel() < 3 * n
+              or not sum.is_contiguous()):
+            raise ValueError("sum: a contiguous float64 tensor of at least rows*W*3 elements on "
+                             "the device")
+        _check(_lib.rt_accumulate_samples_device(self.ctx.handle, self._h, rec.ctypes.data,
+                                                 ctypes.byref(o), sample_begin, sample_end,
+                                                 sum.data_ptr() or 8))
+        return sum
+
+    def resolve(self, sum, samples: int, tonemap: int = TONEMAP_NONE, hdr64: bool = True,
+                hdr32: bool = False) -> dict:
+        """sum / samples as render's outputs (rt_resolve): {"hdr64" float64 [n,3], "hdr32" float32
+        [n,3], "ldr" uint8 [n,3] — [7,n,3] for TONEMAP_ALL — when tonemap is not TONEMAP_NONE}
+        from a float64 [n,3] host sum.  With samples = 1 the bytes are Context.tonemap's."""
+        sum = np.ascontiguousarray(sum, np.float64).reshape(-1, 3)
+        n = sum.shape[0]
+        out = {}
+        if hdr64:
+            out["hdr64"] = np.empty((n, 3), np.float64)
+        if hdr32:
+            out["hdr32"] = np.empty((n, 3), np.float32)
+        if tonemap != TONEMAP_NONE:
+            out["ldr"] = np.empty((7, n, 3) if tonemap == TONEMAP_ALL else (n, 3), np.uint8)
+        ptr = {k: (v.ctypes.data or 8) for k, v in out.items()}
+        _check(_lib.rt_resolve(self.ctx.handle, sum.ctypes.data or 8, n, samples, tonemap,
+                               ptr.get("hdr64"), ptr.get("hdr32"), ptr.get("ldr")))
+        return out
+
+    def resolve_device(self, sum, samples: int, tonemap: int = TONEMAP_NONE, hdr64: bool = True,
+                       hdr32: bool = False, out=None) -> dict:
+        """Asynchronous rt_resolve_device on the context's stream: resolve() on a contiguous
+        float64 [n,3] tensor on the context's device, the outputs torch tensors there (`out` may
+        hold a tensor per requested name to write into).  No host synchronisation: after
+        accumulate_device on the same context the sum is read in stream order."""
+        import torch
+        dev = torch.device(f"cuda:{self.ctx.device}")
+        if sum.dtype != torch.float64 or sum.device != dev or not sum.is_contiguous():
+            raise ValueError("sum: a contiguous float64 tensor on the context's device")
+        n = sum.numel() // 3
+        if sum.numel() != 3 * n:
+            raise ValueError("sum: n*3 elements")
+        want = []
+        if hdr64:
+            want.append(("hdr64", torch.float64, (n, 3)))
+        if hdr32:
+            want.append(("hdr32", torch.float32, (n, 3)))
+        if tonemap != TONEMAP_NONE:
+            want.append(("ldr", torch.uint8, (7, n, 3) if tonemap == TONEMAP_ALL else (n, 3)))
+        res = {}
+        for name, tdt, shape in want:
+            t = None if out is None else out.get(name)
+            if t is None:
+                t = torch.empty(shape, dtype=tdt, device=dev)
+            elif (t.dtype != tdt or t.device != dev or t.numel() < int(np.prod(shape))
+                  or not t.is_contiguous()):
+                raise ValueError(f"out[{name!r}]: a contiguous {tdt} tensor of at least "
+                                 f"{int(np.prod(shape))} elements on the device")
+            res[name] = t
+        ptr = {k: (v.data_ptr() or 8) for k, v in res.items()}
+        # never a NULL pointer for a requested output or the sum, an empty tensor's included
+        _check(_lib.rt_resolve_device(self.ctx.handle, sum.data_ptr() or 8, n, samples, tonemap,
+                                      ptr.get("hdr64"), ptr.get("hdr32"), ptr.get("ldr")))
+        return res
+
+    def render_progressive(self, schedule=None, tonemap: int = TONEMAP_NONE, hdr64: bool = True,
+                           hdr32: bool = False, cam=None, **opts):
+        """A generator over a frame that refines: after each step k of `schedule` (increasing
+        sample counts ending at max(1, aa_samples); None: progressive_schedule) it yields
+        (k, outputs), outputs = resolve_device(the sum of samples [0, k), k) as device tensors,
+        enqueued on the context's stream and not synchronised.  One sum is continued from step to
+        step, so the last step's outputs are the frame's, and each step's outputs are new
+        tensors.  Stop iterating to stop rendering."""
+        rec, _, _ = self._camera_record(cam)
+        aa = max(1, int(rec["aa_samples"][0]))
+        steps = progressive_schedule(aa) if schedule is None else [int(k) for k in schedule]
+        if (not steps or steps[0] < 1 or steps[-1] != aa
+                or any(b <= a for a, b in zip(steps, steps[1:]))):
+            raise ValueError("schedule: increasing sample counts from at least 1, ending at "
+                             "max(1, aa_samples)")
+        acc, done = None, 0
+        for k in steps:
+            acc = self.accumulate_device(done, k, sum=acc, cam=cam, **opts)
+            done = k
+            yield k, self.resolve_device(acc, k, tonemap=tonemap, hdr64=hdr64, hdr32=hdr32)
 
     def debug_tile_order(self):
         """The packet kernel's tile-order state for this scene's camera (rt_debug_tile_order):

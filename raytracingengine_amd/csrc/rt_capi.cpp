@@ -1657,6 +1657,144 @@ rt_status rt_closest_rays(rt_context* ctx, const rt_scene* sc, const rt_render_o
     return RT_OK;
 }
 
+// ---- progressive frames (rt_accumulate.hip) -------------------------------------------------
+// The argument checks of the two accumulate entries, made before the context or the scene is
+// dereferenced, then build_params with the members of opts the call reads: the kernel selection
+// (path) and the RT_ERR_UNSUPPORTED of rt_trace_rays for the scene and opts.
+static rt_status accumulate_params(rt_context* ctx, const rt_scene* sc, const rt_camera* cam,
+                                   const rt_render_opts* opts, int s0, int s1, const void* sum,
+                                   const char* entry, TraceParams& p, int& path) {
+    const std::string name(entry);
+    if (!ctx || !sc || !cam || !sum) return fail(RT_ERR_INVALID_ARG, "NULL argument to " + name);
+    if (cam->width == 0 || cam->height == 0)
+        return fail(RT_ERR_INVALID_ARG, "zero camera width or height passed to " + name);
+    if (s0 < 0 || s0 >= s1 || s1 > std::max(1, cam->aa_samples))
+        return fail(RT_ERR_INVALID_ARG, "sample range [" + std::to_string(s0) + "," +
+                                            std::to_string(s1) +
+                                            ") empty or outside [0, max(1, aa_samples)] passed to " +
+                                            name);
+    rt_render_opts o;
+    rt_render_opts_default(&o);
+    if (opts) {
+        o.max_recursion = opts->max_recursion;
+        o.bias = opts->bias;
+        o.seed = opts->seed;
+        o.row_begin = opts->row_begin;
+        o.row_end = opts->row_end;
+        o.row_block = opts->row_block;
+        o.row_cycle = opts->row_cycle;
+        o.flags = opts->flags & RT_FLAG_NO_BVH;
+    }
+    o.tonemap = RT_TONEMAP_NONE;
+    const uint32_t r1 = o.row_end ? o.row_end : cam->height;
+    if (r1 > cam->height || o.row_begin >= r1)
+        return fail(RT_ERR_INVALID_ARG, "row range [" + std::to_string(o.row_begin) + "," +
+                                            std::to_string(r1) + ") invalid for height " +
+                                            std::to_string(cam->height) + " passed to " + name);
+    if (o.row_cycle > 1 && o.row_block == 0)
+        return fail(RT_ERR_INVALID_ARG, "row_cycle > 1 without row_block >= 1 passed to " + name);
+    bool lds;
+    size_t lds_bytes;
+    uint32_t rows;
+    const rt_status st = build_params(ctx, sc, cam, &o, p, path, lds, lds_bytes, rows);
+    if (st != RT_OK) return fail(st, g_last_error + ", passed to " + name);
+    return RT_OK;
+}
+
+rt_status rt_accumulate_samples_device(rt_context* ctx, const rt_scene* sc, const rt_camera* cam,
+                                       const rt_render_opts* opts, int sample_begin,
+                                       int sample_end, void* d_sum) {
+    TraceParams p;
+    int path;
+    rt_status st = accumulate_params(ctx, sc, cam, opts, sample_begin, sample_end, d_sum,
+                                     "rt_accumulate_samples_device", p, path);
+    if (st != RT_OK) return st;
+    DeviceGuard g(ctx->device);
+    RT_HIP(launch_accumulate_samples(p, path, sample_begin, sample_end,
+                                     static_cast<double*>(d_sum), ctx->stream));
+    return RT_OK;
+}
+
+rt_status rt_accumulate_samples(rt_context* ctx, const rt_scene* sc, const rt_camera* cam,
+                                const rt_render_opts* opts, int sample_begin, int sample_end,
+                                double* sum) {
+    TraceParams p;
+    int path;
+    rt_status st = accumulate_params(ctx, sc, cam, opts, sample_begin, sample_end, sum,
+                                     "rt_accumulate_samples", p, path);
+    if (st != RT_OK) return st;
+    DeviceGuard g(ctx->device);
+    const size_t bytes = static_cast<size_t>(p.rows) * p.width * 3 * sizeof(double);
+    RT_HIP(ctx->out64.ensure(bytes));
+    double* d_sum = static_cast<double*>(ctx->out64.ptr);
+    if (sample_begin > 0)  // the sum so far; with sample_begin == 0 nothing of it is read
+        RT_HIP(hipMemcpyAsync(d_sum, sum, bytes, hipMemcpyHostToDevice, ctx->stream));
+    RT_HIP(launch_accumulate_samples(p, path, sample_begin, sample_end, d_sum, ctx->stream));
+    RT_HIP(hipMemcpyAsync(sum, d_sum, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    RT_HIP(hipStreamSynchronize(ctx->stream));
+    return RT_OK;
+}
+
+// The checks of the two resolve entries, before the context is dereferenced.
+static rt_status check_resolve_args(const rt_context* ctx, const void* sum, size_t n, int samples,
+                                    int tonemap, const void* hdr64, const void* hdr32,
+                                    const void* ldr, const char* entry) {
+    const std::string name(entry);
+    if (samples < 1)
+        return fail(RT_ERR_INVALID_ARG, "samples " + std::to_string(samples) + " < 1 passed to " + name);
+    if (tonemap < RT_TONEMAP_NONE || tonemap > RT_TONEMAP_COUNT)
+        return fail(RT_ERR_INVALID_ARG, "unknown tonemap operator passed to " + name);
+    if (!hdr64 && !hdr32 && !ldr) return fail(RT_ERR_INVALID_ARG, "no output passed to " + name);
+    if (ldr && tonemap == RT_TONEMAP_NONE)
+        return fail(RT_ERR_INVALID_ARG, "bytes requested with RT_TONEMAP_NONE from " + name);
+    if (!sum && n > 0) return fail(RT_ERR_INVALID_ARG, "NULL sum passed to " + name);
+    if (!ctx) return fail(RT_ERR_INVALID_ARG, "NULL context passed to " + name);
+    return RT_OK;
+}
+
+rt_status rt_resolve_device(rt_context* ctx, const void* d_sum, size_t n, int samples, int tonemap,
+                            void* d_hdr64, void* d_hdr32, void* d_ldr) {
+    rt_status st = check_resolve_args(ctx, d_sum, n, samples, tonemap, d_hdr64, d_hdr32, d_ldr,
+                                      "rt_resolve_device");
+    if (st != RT_OK) return st;
+    if (n == 0) return RT_OK;
+    DeviceGuard g(ctx->device);
+    RT_HIP(launch_resolve(static_cast<const double*>(d_sum), n, samples, tonemap,
+                          static_cast<double*>(d_hdr64), static_cast<float*>(d_hdr32),
+                          static_cast<uint8_t*>(d_ldr), ctx->stream));
+    return RT_OK;
+}
+
+rt_status rt_resolve(rt_context* ctx, const double* sum, size_t n, int samples, int tonemap,
+                     double* hdr64, float* hdr32, uint8_t* ldr) {
+    rt_status st = check_resolve_args(ctx, sum, n, samples, tonemap, hdr64, hdr32, ldr, "rt_resolve");
+    if (st != RT_OK) return st;
+    if (n == 0) return RT_OK;
+    DeviceGuard g(ctx->device);
+    const size_t planes = tonemap == RT_TONEMAP_COUNT ? RT_TONEMAP_COUNT : 1;
+    RT_HIP(ctx->tm_in.ensure(n * 3 * sizeof(double)));
+    if (hdr64) RT_HIP(ctx->out64.ensure(n * 3 * sizeof(double)));
+    if (hdr32) RT_HIP(ctx->out32.ensure(n * 3 * sizeof(float)));
+    if (ldr) RT_HIP(ctx->tm_out.ensure(planes * n * 3));
+    RT_HIP(hipMemcpyAsync(ctx->tm_in.ptr, sum, n * 3 * sizeof(double), hipMemcpyHostToDevice,
+                          ctx->stream));
+    RT_HIP(launch_resolve(static_cast<const double*>(ctx->tm_in.ptr), n, samples, tonemap,
+                          hdr64 ? static_cast<double*>(ctx->out64.ptr) : nullptr,
+                          hdr32 ? static_cast<float*>(ctx->out32.ptr) : nullptr,
+                          ldr ? static_cast<uint8_t*>(ctx->tm_out.ptr) : nullptr, ctx->stream));
+    if (hdr64)
+        RT_HIP(hipMemcpyAsync(hdr64, ctx->out64.ptr, n * 3 * sizeof(double), hipMemcpyDeviceToHost,
+                              ctx->stream));
+    if (hdr32)
+        RT_HIP(hipMemcpyAsync(hdr32, ctx->out32.ptr, n * 3 * sizeof(float), hipMemcpyDeviceToHost,
+                              ctx->stream));
+    if (ldr)
+        RT_HIP(hipMemcpyAsync(ldr, ctx->tm_out.ptr, planes * n * 3, hipMemcpyDeviceToHost,
+                              ctx->stream));
+    RT_HIP(hipStreamSynchronize(ctx->stream));
+    return RT_OK;
+}
+
 rt_status rt_tonemap(rt_context* ctx, const double* hdr, size_t n, int op, uint8_t* out) {
     if (!ctx || (!hdr && n) || (!out && n))
         return fail(RT_ERR_INVALID_ARG, "NULL argument to rt_tonemap");

@@ -323,6 +323,16 @@ struct ChOut {
 };
 hipError_t launch_closest_rays(const TraceParams& p, const double* rays, size_t n, const ChOut& out,
                                hipStream_t stream);
+// Progressive frames (rt_accumulate.hip).  launch_accumulate_samples: for every pixel of p's row
+// set, sum = (s0 == 0 ? +0.0 : sum) + TraceRay(camera ray of sample s) for s in [s0, s1) in
+// order, with the render kernels' keys (pix = y_image * W + x, s) for the jitter and the area
+// light; sum: p.rows * p.width * 3 doubles, rows-local.  launch_resolve: per pixel sum / samples,
+// written as doubles, floats and tonemapped bytes (op in [0, 7), or 7: seven planes in
+// tonemapAll() order; op is read only with ldr set); a null output is not written.
+hipError_t launch_accumulate_samples(const TraceParams& p, int path, int s0, int s1, double* sum,
+                                     hipStream_t stream);
+hipError_t launch_resolve(const double* sum, size_t n, int samples, int op, double* out64,
+                          float* out32, uint8_t* ldr, hipStream_t stream);
 hipError_t launch_tonemap(const double* hdr, size_t n, int op, uint8_t* out, hipStream_t stream);
 hipError_t launch_debug_f64(const double* x, const double* y, size_t n, double* out,
                             hipStream_t stream);
