@@ -55,7 +55,8 @@ def lib():
         L.oracle_render.argtypes = [vp, vp, vp, vp, vp, vp]
         L.oracle_render.restype = ctypes.c_int
         L.oracle_tonemap.argtypes = [vp, ctypes.c_size_t, ctypes.c_int, vp]
-        L.oracle_u01.argtypes = [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32]
+        L.oracle_tonemap_curves.argtypes = [vp, ctypes.c_size_t, ctypes.c_int, vp]
+        L.oracle_u01.argtypes =[ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32]
         L.oracle_u01.restype = ctypes.c_double
         for n in ("oracle_sphere_intersect", "oracle_plane_intersect", "oracle_triangle_intersect"):
             getattr(L, n).argtypes = [vp, vp, dp]
@@ -112,6 +113,15 @@ def tonemap(hdr: np.ndarray, op: int) -> np.ndarray:
     hdr = np.ascontiguousarray(hdr, dtype=np.float64).reshape(-1, 3)
     out = np.empty(hdr.shape, np.uint8)
     if lib().oracle_tonemap(hdr.ctypes.data, hdr.shape[0], op, out.ctypes.data) != 0:
+        raise ValueError(op)
+    return out
+
+
+def curves(hdr: np.ndarray, op: int) -> np.ndarray:
+    """The operator's value before toColor: hdr [n,3] -> float64 [n,3], NaNs included."""
+    hdr = np.ascontiguousarray(hdr, dtype=np.float64).reshape(-1, 3)
+    out = np.empty(hdr.shape, np.float64)
+    if lib().oracle_tonemap_curves(hdr.ctypes.data, hdr.shape[0], op, out.ctypes.data) != 0:
         raise ValueError(op)
     return out
 

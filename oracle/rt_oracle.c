@@ -493,6 +493,17 @@ int oracle_tonemap(const double* hdr, size_t n, int op, uint8_t* out) {
     return 0;
 }
 
+int oracle_tonemap_curves(const double* hdr, size_t n, int op, double* out) {
+    if (op < 0 || op > 6) return -1;
+    for (size_t i = 0; i < n; ++i) {
+        V v = tonemap_op(ld3(hdr + 3 * i), op);
+        out[3 * i + 0] = v.x;
+        out[3 * i + 1] = v.y;
+        out[3 * i + 2] = v.z;
+    }
+    return 0;
+}
+
 /* ---------------------------------------------------------------- known-answer helpers */
 int oracle_sphere_intersect(const double* ray, const o_sphere* s, double* t) {
     return sphere_hit(ld3(ray), ld3(ray + 3), s, t);

@@ -79,6 +79,9 @@ int oracle_trace_rays(const o_scene* sc, const o_opts* opt, const double* rays, 
 
 /* Tonemap operator `op` (0..6, tonemapAll order) + toColor() for n pixels → n*3 bytes. */
 int oracle_tonemap(const double* hdr, size_t n, int op, uint8_t* out);
+/* The operator's Vec3 before toColor() (RaytracingEngine.cpp:123-163, 89-98) for n pixels → n*3
+ * doubles, NaNs included (a black pixel under the luminance operators is 0/0). */
+int oracle_tonemap_curves(const double* hdr, size_t n, int op, double* out);
 
 /* Known-answer helpers (one call per query). ray = {ox,oy,oz,dx,dy,dz}.
  * *_intersect return 1 and set *t on a hit, 0 on a miss. */

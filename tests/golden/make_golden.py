@@ -11,6 +11,7 @@ and the reference's outputs for them.  The reference has no tests or fixtures of
     python tests/golden/make_golden.py --oracle-full      # C5 (no reference semantics): oracle
     python tests/golden/make_golden.py --rays             # ray_queries.npz only (tests/raysets.py)
     python tests/golden/make_golden.py --queries          # query_tables.npz only (the batch queries)
+    python tests/golden/make_golden.py --tonemap-edges    # tonemap_edges.npz only (tests/tonemap_sets.py)
 """
 from __future__ import annotations
 
@@ -417,8 +418,50 @@ def queries_golden(out_dir=HERE):
     return path
 
 
+def tonemap_edges_golden(out_dir=HERE):
+    """``--tonemap-edges``: what the compiled reference answers on the byte-boundary table of
+    tests/tonemap_sets.py — the 8 byte planes of ``ref_harness tonemap`` (tonemapAll's seven
+    operators, then tonemap()) and operator 4's curve before toColor (``ref_harness curves``).
+    Writes <out_dir>/tonemap_edges.npz with the thresholds and the SHA-256 of the input array; the
+    inputs are rebuilt from the thresholds, not stored.  Returns the path."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import tonemap_sets as tm
+    if not po.ref_current():
+        po.build()
+    assert po.ref_current(), "oracle/_ref/ref_harness missing or stale (needs the reference sources)"
+    thr = tm.thresholds()
+    px = tm.inputs(thr)
+    with tempfile.TemporaryDirectory() as td:
+        inp, b8, cv = (os.path.join(td, n) for n in ("px.f64", "tm.u8", "cv.f64"))
+        px.tofile(inp)
+        run("tonemap", inp, len(px), b8)
+        run("curves", inp, len(px), cv)
+        planes = np.fromfile(b8, np.uint8).reshape(8, len(px), 3)
+        jodie = np.fromfile(cv, np.float64).reshape(7, len(px), 3)[tm.JODIE]
+    path = os.path.join(out_dir, tm.FIXTURE)
+    save_npz(path, {"thresholds": thr, "inputs_sha256": np.array(tm.sha(px)), "bytes": planes,
+                    "jodie_curve": jodie})
+    if os.path.abspath(out_dir) == HERE:
+        meta_path = os.path.join(HERE, "golden_meta.json")
+        with open(meta_path) as fh:
+            meta = json.load(fh)
+        meta["tonemap_edges"] = {
+            "fixture": tm.FIXTURE, "generator": "tests/golden/make_golden.py --tonemap-edges",
+            "inputs": "tests/tonemap_sets.py inputs(thresholds)", "n_pixels": len(px),
+            "harness_modes": ["curves", "tonemap"], "ulp_offsets": list(tm.ULPS),
+            "gray_max": tm.G_MAX, "seed": tm.SEED,
+            "stored": "thresholds, SHA-256 of the inputs, the 8 byte planes and operator 4's "
+                      "curve; inputs not stored"}
+        with open(meta_path, "w") as fh:
+            json.dump(meta, fh, indent=1, sort_keys=True)
+    print(tm.FIXTURE, os.path.getsize(path), "bytes,", len(px), "pixels")
+    return path
+
+
 if __name__ == "__main__":
-    if "--queries" in sys.argv:
+    if "--tonemap-edges" in sys.argv:
+        tonemap_edges_golden()
+    elif "--queries" in sys.argv:
         queries_golden()
     elif "--rays" in sys.argv:
         ray_queries_golden()
