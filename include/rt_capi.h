@@ -846,6 +846,13 @@ rt_status rt_debug_tile_class(rt_context* ctx, uint64_t* with_words, uint64_t* w
  * all-ones masks. */
 rt_status rt_debug_plane_clear(rt_context* ctx, uint64_t* with_masks, uint64_t* without_masks);
 
+/* Test hook (read-only): frames enqueued through the fix-up variant of the packet kernel as a
+ * split launch (*split: the uniform tiles in a kernel of their own over the frame's tile list,
+ * the general workgroups over theirs) and as its single launch (*single).  A batch is split when
+ * every frame has tile lists next to its class words and no tile order applies;
+ * RTAMD_PK_TILE_SPLIT=0 in the environment, read per launch, keeps the single launch. */
+rt_status rt_debug_tile_split(rt_context* ctx, uint64_t* split, uint64_t* single);
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif

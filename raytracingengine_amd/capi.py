@@ -94,6 +94,7 @@ EXPORTED = [
     "rt_debug_shadow_table",
     "rt_debug_tile_class",
     "rt_debug_plane_clear",
+    "rt_debug_tile_split",
     "rt_occluded_rays", "rt_occluded_rays_device",
     "rt_transmittance_rays", "rt_transmittance_rays_device",
     "rt_light_transmittance", "rt_light_transmittance_device",
@@ -301,6 +302,7 @@ def load_library(path: str = LIB_PATH):
         "rt_debug_shadow_table": [vp, vp, vp],
         "rt_debug_tile_class": [vp, vp, vp],
         "rt_debug_plane_clear": [vp, vp, vp],
+        "rt_debug_tile_split": [vp, vp, vp],
         "rt_debug_assemble_rows": [vp, vp, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_uint32,
                                    ctypes.c_uint32, ctypes.c_uint32, vp],
     }.items():
@@ -460,6 +462,12 @@ class Context:
         """Packet-kernel frames enqueued so far (with, without) shadow-plane keep masks."""
         a, b = ctypes.c_uint64(), ctypes.c_uint64()
         _check(_lib.rt_debug_plane_clear(self._h, ctypes.byref(a), ctypes.byref(b)))
+        return a.value, b.value
+
+    def debug_tile_split(self) -> tuple[int, int]:
+        """Fix-up variant frames enqueued so far (as a split launch, as a single launch)."""
+        a, b = ctypes.c_uint64(), ctypes.c_uint64()
+        _check(_lib.rt_debug_tile_split(self._h, ctypes.byref(a), ctypes.byref(b)))
         return a.value, b.value
 
     def debug_vec_ops(self, v: np.ndarray) -> np.ndarray:

@@ -329,12 +329,13 @@ rt_status enqueue_frames(rt_context* ctx, const rt_scene* sc, const rt_camera* c
     const bool packet = packet_path;
     rt_scene::PkImage::TileOrder* rec = nullptr;  // set: this launch records wave durations
     int batch_ring = -1;  // the ring entry of this batch's formed images, if any
+    PkSplit pk_split{0u, 0u, 0u};  // the batch's tile lists, if every frame has them
     if (packet && nframes > 1) {
         // a frame batch: frame f's camera and image source, all formed before the launch by at
         // most one small launch (packet_batch_images)
         p.nframes = static_cast<uint32_t>(nframes);
         p.frame_px = frame_px;
-        st = packet_batch_images(ctx, sc, cams, nframes, p, flags, &rec, &batch_ring);
+        st = packet_batch_images(ctx, sc, cams, nframes, p, flags, &rec, &batch_ring, &pk_split);
         if (st != RT_OK) return st;
     } else if (packet) {
         st = packet_image(ctx, sc, p, flags, &rec);
@@ -368,6 +369,12 @@ rt_status enqueue_frames(rt_context* ctx, const rt_scene* sc, const rt_camera* c
         st = scratch_wait(ctx);
         if (st != RT_OK) return st;
     }
+    // The fix-up variant's split launch (rt_packet.hip launch_packet_split): every frame of the
+    // batch has its tile lists (packet_batch_images formed none under a tile order), and the two
+    // launches go onto the render's stream one after the other
+    if (!fixup || p.tile_order) pk_split.tiles = 0;
+    if (packet && fixup)
+        (pk_split.tiles ? ctx->tile_split_frames : ctx->tile_nosplit_frames) += nframes;
     // generic kernels without triangle / area-light code for scenes that use neither
     const bool lean_generic = p.nt == 0 && p.al_samples == 0;
     // reflection chains of scenes made of planes (and up to kBoxMaxSpheres spheres) take the
@@ -384,7 +391,8 @@ rt_status enqueue_frames(rt_context* ctx, const rt_scene* sc, const rt_camera* c
     auto launch = [&](const TraceParams& q, bool count) {
         if (box)
             return launch_box_chain(q, count, !(flags & RT_FLAG_NO_SAMPLE_PARALLEL), ctx->stream);
-        return packet ? launch_packet_direct(q, count, sc->max_specular > 0.0, ctx->stream)
+        return packet ? launch_packet_direct(q, count, sc->max_specular > 0.0, ctx->stream,
+                                             count ? nullptr : &pk_split)
                       : (lean_generic ? lean::launch_trace(q, path, count, lds, lds_bytes, ctx->stream, spar)
                                       : launch_trace(q, path, count, lds, lds_bytes, ctx->stream, spar));
     };
@@ -821,6 +829,7 @@ rt_status rt_scene_destroy(rt_scene* sc) {
         for (auto& t : im.tabs) {
             t.buf.release();
             if (t.ready) (void)hipEventDestroy(t.ready);
+            if (t.counts) (void)hipHostFree(t.counts);
         }
     }
     for (auto& b : sc->pk_batch_tab) b.release();
@@ -1891,6 +1900,14 @@ rt_status rt_debug_plane_clear(rt_context* ctx, uint64_t* with_masks, uint64_t* 
         return fail(RT_ERR_INVALID_ARG, "NULL argument to rt_debug_plane_clear");
     *with_masks = ctx->plane_mask_frames;
     *without_masks = ctx->plane_nomask_frames;
+    return RT_OK;
+}
+
+rt_status rt_debug_tile_split(rt_context* ctx, uint64_t* split, uint64_t* single) {
+    if (!ctx || !split || !single)
+        return fail(RT_ERR_INVALID_ARG, "NULL argument to rt_debug_tile_split");
+    *split = ctx->tile_split_frames;
+    *single = ctx->tile_nosplit_frames;
     return RT_OK;
 }
 

@@ -88,6 +88,8 @@ struct rt_context {
     uint64_t tile_class_frames = 0, tile_noclass_frames = 0;
     // ... and with class words that carry shadow-plane keep masks / without (rt_debug_plane_clear)
     uint64_t plane_mask_frames = 0, plane_nomask_frames = 0;
+    // ... and through the fix-up variant's split launch / its single launch (rt_debug_tile_split)
+    uint64_t tile_split_frames = 0, tile_nosplit_frames = 0;
     // rt_render_multi: RCCL communicators over the devices of the last context list this
     // context led (rt_multi.cpp); destroyed with the context
     std::vector<rt_context*> group_ctxs;
@@ -153,6 +155,10 @@ struct rt_scene {
             hipEvent_t ready = nullptr;
             hipStream_t stream = nullptr;
             bool done = false;
+            // with tile lists (the key says so): a pinned host word the launch that forms the
+            // table fills with the lists' counts, each plus one — uniform tiles in the low
+            // half, general workgroups in the high half; 0: not formed yet
+            unsigned long long* counts = nullptr;
         };
         std::vector<ConeTab> tabs;
     };
@@ -198,12 +204,13 @@ rt_status check_batch(const rt_camera* cams, int nframes);
 // scene's cache of camera images, a setup launch on a camera's second sighting, or a publish
 // slot (p.pk_pub); a batch: p.fr[f] for every frame and *batch_ring = the ring entry its formed
 // images took, or -1.  Both set p.tile_order / p.tile_cost and *rec, the tile-order entry whose
-// recording launch the caller marks complete.
+// recording launch the caller marks complete.  *split: the batch's split launch (tiles == 0: none).
 rt_status packet_image(rt_context* ctx, const rt_scene* sc, TraceParams& p, int flags,
                        rt_scene::PkImage::TileOrder** rec);
 rt_status packet_batch_images(rt_context* ctx, const rt_scene* sc, const rt_camera* cams,
                               int nframes, TraceParams& p, int flags,
-                              rt_scene::PkImage::TileOrder** rec, int* batch_ring);
+                              rt_scene::PkImage::TileOrder** rec, int* batch_ring,
+                              PkSplit* split);
 // Whether a render takes the breadth-first TraceRay path, whose arena is one per context (as are
 // the ray counters): renders that use them are ordered across streams (scratch_wait/_done).
 bool uses_wavefront_arena(int path, int flags);

@@ -154,6 +154,16 @@ struct TraceParams {
     const unsigned long long* class_tab;
     const unsigned long long* fr_ctab[kPkMaxBatch];
 };
+// The fix-up variant's split launch of a frame batch (packet_uniform_kernel and
+// packet_direct_kernel's kFeatSplit twin, rt_packet.hip): every frame's class words are followed
+// by its tile lists (rt_shadow_table.hpp), at fr_ctab[f] + tiles; tiles == 0: no lists, one
+// launch as before.  uni_n and gen_n: the uniform tiles and general workgroups the two launches
+// cover per frame — the largest count of the batch's frames where the host knows them, every
+// tile or workgroup where it does not.  Host only: TraceParams keeps its size and layout.
+struct PkSplit {
+    uint32_t tiles;
+    uint32_t uni_n, gen_n;
+};
 // the runtime passes at most 4 KiB of kernel arguments (packet_image_batch_kernel and
 // packet_cone_table_kernel take a job list of kPkMaxBatch pointers and ints next to it)
 static_assert(sizeof(TraceParams) + 12 * kPkMaxBatch + 32 <= 4096, "kernel arguments above 4 KiB");
@@ -201,7 +211,7 @@ hipError_t launch_trace(const TraceParams& p, int path, bool count, bool lds, si
 hipError_t launch_box_chain(const TraceParams& p, bool count, bool sample_parallel,
                             hipStream_t stream);
 hipError_t launch_packet_direct(const TraceParams& p, bool count, bool any_specular,
-                                hipStream_t stream);
+                                hipStream_t stream, const PkSplit* split = nullptr);
 size_t packet_lds_bytes(int ns, int np, int nl);
 hipError_t launch_packet_image(const TraceParams& p, double* img, hipStream_t stream);
 // Whether launch_packet_direct takes a fix-up variant for p (then p.fix_list / p.fix_ctl must be
@@ -231,9 +241,23 @@ struct PkConeJobs {
     // words: dst[j] + tiles · (1 + shadow_nl); 2: with the shadow-plane keep masks formed
     // (shadow_plane_keep), 1: with all-ones masks
     int32_t class_words;
+    // != 0 (with class_words only): the tile lists too, after the class words:
+    // dst[j] + tiles · (2 + shadow_nl), tile_list_words(tiles, workgroups) words
+    int32_t lists;
+};
+// host[j], when set, is a pinned host word that receives job j's two list counts once the table
+// is formed: uniform tiles in the low half, general workgroups in the high half, each plus one
+// (0: not yet)
+struct PkListCounts {
+    unsigned long long* host[kPkMaxBatch];
 };
 hipError_t launch_packet_cone_tables(const TraceParams& p, const PkConeJobs& jobs,
-                                     hipStream_t stream);
+                                     hipStream_t stream, const PkListCounts* counts = nullptr);
+// Whether a launch of p may take the split launch at all (RTAMD_PK_TILE_SPLIT, read per launch,
+// a tile grid whose columns and rows a list entry can name, one wave row per workgroup and no
+// tile order: an order names dispatch positions, a list tiles), and the two launches
+// themselves: launch_packet_direct takes them when split->tiles is set.
+bool packet_split_wanted(const TraceParams& p);
 // Whether p's launch is served by a variant that reads a cone table.
 bool packet_reads_cone_table(const TraceParams& p, bool any_specular);
 // Lights per tile of the shadow table such a launch's scene gets (0: none, rt_shadow_table.hpp).

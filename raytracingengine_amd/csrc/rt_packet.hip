@@ -57,6 +57,12 @@ hipError_t launch_packet_image_batch(const TraceParams& p, const PkImageJobs& jo
 // With J.class_words the lane closes with the tile's class word (tile_class_word), one per tile
 // after the shadow words: which tiles the fix-up variant renders on its uniform path, and which
 // planes each light's shadow rays of the tile must still classify (bits 8 and up).
+// With J.lists the lane also files its tile in the frame's tile lists (rt_shadow_table.hpp), after
+// the class words: a wavefront is one run of list positions (position i stands for tile
+// tiles − 1 − i), compacted with three ballots (uniform tiles, general tiles, listed workgroups'
+// first lanes) and given its place in each list by one atomic add per wavefront — tile_list_run
+// is the same run in plain C++, and the helpers that decide are shared with it;
+// the counts were zeroed by packet_list_zero_kernel before this launch.
 // The kernel waits more than it issues (dependent FP64 chains, one lane per tile), so it is
 // built for 5 waves per SIMD (96 VGPRs, 104 B of scratch; by itself it compiles to 3): the
 // measured times are in DESIGN §4 and profiles/shadow_table_pmc.txt.
@@ -78,8 +84,10 @@ __global__ __launch_bounds__(kConeThreads, 5) void packet_cone_table_kernel(Trac
         for (int i = threadIdx.x; i < 3 * ns; i += kConeThreads)
             s_ctr[i] = img[kPkSph * (i / 3) + i % 3];
     __syncthreads();
-    const uint32_t t = blockIdx.x * kConeThreads + threadIdx.x;
-    if (t >= gx * gy * waves) return;
+    const uint32_t pos = blockIdx.x * kConeThreads + threadIdx.x;
+    if (pos >= gx * gy * waves) return;
+    // (every tile has one lane; with lists the lanes take the tiles from the last one down)
+    const uint32_t t = J.lists ? tile_list_tile(pos, gx * gy * waves) : pos;
     const uint32_t wave = t % waves, wg = t / waves, tbx = wg % gx, tby = wg / gx;
     const uint32_t x0 = tbx * (kPkW * kWgWavesX) + (wave % kWgWavesX) * kPkW;
     const uint32_t yl0 = tby * (kPkH * (waves / kWgWavesX)) + (wave / kWgWavesX) * kPkH;
@@ -116,12 +124,50 @@ __global__ __launch_bounds__(kConeThreads, 5) void packet_cone_table_kernel(Trac
     // image follows its planes and lights (pk_build_image).  The OR of the tile's shadow words
     // stands for them (zero iff every one is; the launcher checked shadow_nl <= kShadowTabLights)
     const double* pln = img + kPkSph * ns + kPlStride * P.np + kLtStride * P.nl;
-    J.dst[blockIdx.y][static_cast<size_t>(gx) * gy * waves * (1 + J.shadow_nl) + t] =
-        tile_class_word(cone, SB, &any, 1, pln, P.np) | keep;
+    const unsigned long long cw = tile_class_word(cone, SB, &any, 1, pln, P.np) | keep;
+    J.dst[blockIdx.y][static_cast<size_t>(gx) * gy * waves * (1 + J.shadow_nl) + t] = cw;
+    if (!J.lists) return;
+    // the tile lists: the active lanes of this wavefront are a run's first lanes (lane 0 among
+    // them), and a workgroup's tiles are `waves` adjacent lanes
+    const size_t tiles = static_cast<size_t>(gx) * gy * waves;
+    unsigned long long* hdr = J.dst[blockIdx.y] + tiles * (2 + J.shadow_nl);
+    unsigned long long* uni = hdr + 1;
+    uint32_t* gen = reinterpret_cast<uint32_t*>(hdr + 1 + tiles);
+    const uint32_t lane = threadIdx.x & 63u;
+    const bool is_uni = tile_list_uniform(cw);
+    const uint64_t bu = __ballot(is_uni), bg = __ballot(!is_uni);
+    const bool lead = (lane & (waves - 1u)) == 0 && tile_list_wg_listed(bg, lane, waves);
+    const uint64_t bl = __ballot(lead);
+    uint32_t base_u = 0, base_g = 0;
+    if (lane == 0) {
+        if (bu) base_u = atomicAdd(reinterpret_cast<uint32_t*>(hdr),
+                                   static_cast<uint32_t>(__builtin_popcountll(bu)));
+        if (bl) base_g = atomicAdd(reinterpret_cast<uint32_t*>(hdr) + 1,
+                                   static_cast<uint32_t>(__builtin_popcountll(bl)));
+    }
+    base_u = __shfl(base_u, 0, 64);
+    base_g = __shfl(base_g, 0, 64);
+    const uint64_t below = (1ull << lane) - 1ull;
+    if (is_uni) uni[base_u + __builtin_popcountll(bu & below)] = tile_list_entry(cw, x0, yl0);
+    if (lead) gen[base_g + __builtin_popcountll(bl & below)] = wg;
+}
+
+// The list counts of a table launch's jobs: zeroed before it, and handed to the host after it
+// (each plus one in a pinned word, so 0 says "not yet") where the table has a cache entry.
+__global__ __launch_bounds__(64) void packet_list_zero_kernel(PkConeJobs J, size_t hdr) {
+    if (static_cast<int>(threadIdx.x) < J.n) J.dst[threadIdx.x][hdr] = 0ull;
+}
+__global__ __launch_bounds__(64) void packet_list_counts_kernel(PkConeJobs J, PkListCounts C,
+                                                                size_t hdr) {
+    if (static_cast<int>(threadIdx.x) >= J.n || !C.host[threadIdx.x]) return;
+    const unsigned long long v = J.dst[threadIdx.x][hdr];
+    __hip_atomic_store(C.host[threadIdx.x],
+                       (((v >> 32) + 1ull) << 32) | ((v & 0xffffffffull) + 1ull), __ATOMIC_RELAXED,
+                       __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
 hipError_t launch_packet_cone_tables(const TraceParams& p, const PkConeJobs& jobs,
-                                     hipStream_t stream) {
+                                     hipStream_t stream, const PkListCounts* counts) {
     if (jobs.n <= 0) return hipSuccess;
     if (jobs.n > kPkMaxBatch || p.ns > 64 || p.width == 0 || p.rows == 0)
         return hipErrorInvalidValue;
@@ -129,6 +175,7 @@ hipError_t launch_packet_cone_tables(const TraceParams& p, const PkConeJobs& job
         return hipErrorInvalidValue;
     if (jobs.class_words != 0 && jobs.shadow_nl <= 0) return hipErrorInvalidValue;
     if (jobs.class_words < 0 || jobs.class_words > 2) return hipErrorInvalidValue;
+    if (jobs.lists != 0 && jobs.class_words == 0) return hipErrorInvalidValue;
     for (int j = 0; j < jobs.n; ++j) {
         const int f = jobs.frame[j];
         if (!jobs.dst[j] || f < -1 || f >= static_cast<int>(p.nframes) ||
@@ -138,10 +185,20 @@ hipError_t launch_packet_cone_tables(const TraceParams& p, const PkConeJobs& job
     uint32_t gx, gy, waves;
     packet_grid(p, gx, gy, waves);
     const uint32_t tiles = gx * gy * waves;
+    const size_t hdr = static_cast<size_t>(tiles) * (2 + jobs.shadow_nl);
+    if (jobs.lists) {
+        // (a list entry names a tile by 12-bit column and row: packet_split_wanted)
+        if (gx * kWgWavesX > kListMaxCoord || gy * (waves / kWgWavesX) > kListMaxCoord)
+            return hipErrorInvalidValue;
+        hipLaunchKernelGGL(packet_list_zero_kernel, dim3(1), dim3(64), 0, stream, jobs, hdr);
+    }
     hipLaunchKernelGGL(packet_cone_table_kernel,
                        dim3((tiles + kConeThreads - 1) / kConeThreads,
                             static_cast<unsigned>(jobs.n)),
                        dim3(kConeThreads), 0, stream, p, jobs, gx, gy, waves);
+    if (jobs.lists && counts)
+        hipLaunchKernelGGL(packet_list_counts_kernel, dim3(1), dim3(64), 0, stream, jobs, *counts,
+                           hdr);
     return hipGetLastError();
 }
 
@@ -367,14 +424,108 @@ bool packet_uses_fixup(const TraceParams& p, bool count, bool any_specular) {
     return eligible && (mode == 1 || px >= kPkFixMinPixels);
 }
 
-hipError_t launch_packet_direct(const TraceParams& p, bool count, bool any_specular,
+// The uniform tiles of the fix-up variant's split launch (PkSplit; the general workgroups take
+// packet_direct_kernel<1, kFeatFix | kFeatSplit, false, false, WGY>), one wave per entry of the frame's list of uniform
+// tiles: the entry is the tile's class word with the tile's column and row (rt_shadow_table.hpp),
+// one scalar load.  The wave forms packet_direct_kernel's kLean camera ray for its lane's pixel
+// (clamped into the image as there), calls pk_uniform_tile and ends in the shared epilogue (rt_packet_epilogue.hpp): the calls the
+// general kernel's uniform branch makes, with the same arguments, so the bits are its bits.  No
+// LDS, no barrier, no table pointer beyond the frame's class words.  Grid: (waves of the largest
+// list over kUniWaves, 1, frames); waves past the frame's count return at once.
+#ifndef RT_PACKET_UNI_THREADS
+#define RT_PACKET_UNI_THREADS 256
+#endif
+#ifndef RT_PACKET_UNI_WAVES
+#define RT_PACKET_UNI_WAVES 8
+#endif
+constexpr int kUniThreads = RT_PACKET_UNI_THREADS;
+__global__ __launch_bounds__(kUniThreads, RT_PACKET_UNI_WAVES) void packet_uniform_kernel(TraceParams P, uint32_t tiles) {
+    constexpr int FEAT = kFeatFix;
+    const PkFrame& F = P.fr[blockIdx.z];  // (split launches are frame batches: P.nframes >= 1)
+    const pk_culp hdr = (pk_culp)P.fr_ctab[blockIdx.z] + tiles;
+    const uint32_t i = blockIdx.x * (kUniThreads / 64) +
+                       __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(threadIdx.x) >> 6);
+    if (i >= static_cast<uint32_t>(hdr[0])) return;
+    const unsigned long long e = hdr[1 + i];
+    const unsigned long long cls = e & kListWordMask;
+    const uint32_t col = static_cast<uint32_t>(e >> kListColShift) & kListCoordMask;
+    const uint32_t row = static_cast<uint32_t>(e >> kListRowShift) & kListCoordMask;
+    const d3 cam = mk(F.cam[0], F.cam[1], F.cam[2]);
+    const double cam_dz = P.fr_dz[blockIdx.z][0], cam_dz2 = P.fr_dz[blockIdx.z][1];
+    const uint64_t frame_off = static_cast<uint64_t>(blockIdx.z) * P.frame_px;
+    const uint32_t lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+    const uint32_t x = col * kPkW + (lane % kPkW), yl = row * kPkH + (lane / kPkW);
+    // lanes past the image edge trace a clamped in-image ray and write nothing
+    const uint32_t xc = x < P.width ? x : P.width - 1;
+    const uint32_t y = image_row(P, yl < P.rows ? yl : P.rows - 1);
+    const double sx = static_cast<double>(xc) - P.half_w;
+    const double sy = P.half_h - static_cast<double>(y);
+    const d3 dv = mk(sx - cam.x, sy - cam.y, cam_dz);
+    const d3 d = unit_sq(dv, dv.x * dv.x + dv.y * dv.y + cam_dz2);
+    bool fix = false;
+    PacketScene S;  // (not read: the records come through the scalar cache)
+    S.lt = nullptr;
+    const d3 col3 = pk_uniform_tile<1, FEAT>(S, P, F.img, cls, cam, d, P.ns, P.np, P.nl, P.bias, fix);
+    const d3 acc = mk(0.0, 0.0, 0.0) + col3;  // the sample loop's one addition
+    constexpr int samples = 1;
+    const uint32_t lane_e = lane, x_e = x, yl_e = yl;
+#include "rt_packet_epilogue.hpp"
+}
+
+// RTAMD_PK_TILE_SPLIT=0 (read per launch): the fix-up variant's single launch, no lists formed
+// (a table formed that way is one of its own).
+bool packet_split_wanted(const TraceParams& p) {
+    const char* e = std::getenv("RTAMD_PK_TILE_SPLIT");
+    if (e && std::atoi(e) == 0) return false;
+    uint32_t gx, gy, waves;
+    packet_grid(p, gx, gy, waves);
+    // (one wave row per workgroup: a scene with class words has at most 63 spheres, an image far
+    // below the size at which workgroups take two rows)
+    return !p.tile_order && waves == kWgWavesX && gx * kWgWavesX <= kListMaxCoord &&
+           gy <= kListMaxCoord;
+}
+
+// The fix-up variant's split launch (s.tiles: every frame's class words are followed by
+// its tile lists): packet_uniform_kernel over the uniform tiles and packet_direct_kernel's
+// kFeatSplit twin over the general workgroups, one after the other on the stream.  They touch
+// disjoint pixels and append to one fix-up list with atomics.  (The uniform launch forked onto
+// a second stream measured the same: profiles/tile_split_ab.txt.)
+static void launch_packet_split(const TraceParams& p, const PkSplit& s, size_t lds,
                                 hipStream_t stream) {
+    // (one wave row per workgroup: packet_split_wanted)
+    const dim3 block(64 * kWgWavesX);
+    const dim3 ggrid(s.gen_n, 1u, p.nframes);
+    const dim3 ugrid((s.uni_n + kUniThreads / 64 - 1) / (kUniThreads / 64), 1u, p.nframes);
+    // (RT_PACKET_SPLIT_GENERAL_FIRST: the other order, for A/B builds)
+#ifdef RT_PACKET_SPLIT_GENERAL_FIRST
+    if (s.gen_n)
+        hipLaunchKernelGGL((packet_direct_kernel<1, kFeatFix | kFeatSplit, false, false, 1>),
+                           ggrid, block, lds, stream, p);
+#endif
+    if (s.uni_n)
+        hipLaunchKernelGGL(packet_uniform_kernel, ugrid, dim3(kUniThreads), 0, stream, p,
+                           s.tiles);
+#ifndef RT_PACKET_SPLIT_GENERAL_FIRST
+    if (s.gen_n)
+        hipLaunchKernelGGL((packet_direct_kernel<1, kFeatFix | kFeatSplit, false, false, 1>),
+                           ggrid, block, lds, stream, p);
+#endif
+}
+
+hipError_t launch_packet_direct(const TraceParams& p, bool count, bool any_specular,
+                                hipStream_t stream, const PkSplit* split) {
     const size_t lds = packet_lds_bytes(p.ns, p.np, p.nl);
     const int chunks = (p.ns + 63) / 64;
     int feat = packet_features(p, any_specular);
     if (packet_uses_fixup(p, count, any_specular)) {
         if (!p.fix_list || !p.fix_ctl || !p.fix_next) return hipErrorInvalidValue;
         feat = kFeatFix;
+        // (the host sets split->tiles only for a frame batch whose frames all have lists, which
+        // packet_split_wanted allowed: no tile order, one wave row per workgroup)
+        if (split && split->tiles) {
+            launch_packet_split(p, *split, lds, stream);
+            return hipGetLastError();
+        }
     }
     // the area-light variants live in rt_packet_area.hip (compiled with the default scheduler)
     if (feat == kFeatArea) return launch_packet_area(p, count, lds, chunks, stream);

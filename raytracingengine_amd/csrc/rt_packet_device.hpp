@@ -87,6 +87,12 @@ constexpr int kFeatFix = 128;
 #ifndef RT_PACKET_FIX_WAVES
 #define RT_PACKET_FIX_WAVES 8
 #endif
+// kFeatFix | kFeatSplit: the fix-up variant over a frame's list of general workgroups, without
+// its uniform path (packet_direct_kernel, rt_packet_kernel.hpp); its waves per SIMD
+constexpr int kFeatSplit = 256;
+#ifndef RT_PACKET_GENERAL_WAVES
+#define RT_PACKET_GENERAL_WAVES RT_PACKET_FIX_WAVES
+#endif
 
 // Waves per SIMD of the single-sample variant for <= 64 spheres, point lights and no other
 // feature (C2): 6 with its light records read through the scalar cache (80 VGPRs, 48 B/lane of

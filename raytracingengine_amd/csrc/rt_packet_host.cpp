@@ -12,6 +12,7 @@
 
 #include "rt_context.hpp"
 #include "rt_internal.hpp"
+#include "rt_shadow_table.hpp"
 
 #pragma clang fp contract(off)
 
@@ -224,6 +225,14 @@ rt_status packet_image_entry(rt_context* ctx, const rt_scene* sc, const double* 
 // two biases has two tables, as at two focal lengths.  RTAMD_PK_SHADOW_TAB=0 (read per launch):
 // no shadow words are formed or handed to the kernel (the table kernel does the cone table's
 // work only, and a cached table formed that way is one of its own, whatever the bias).  With
+// The tile lists (rt_shadow_table.hpp) follow the class words in the same buffer, formed by the
+// same launch for the frame batches that take the fix-up variant: same key (the word that says
+// what follows the shadow words has one more bit), cache entry, ring entry and caps; like the
+// shadow words they come on top of the ring's accounting (9/8 of the class words at most).  A
+// cache entry's table also has a pinned host word that receives the lists' two counts once the
+// table is formed, which sizes the split launch's grids; a batch with a ring frame (a camera
+// seen for the first time) forms no lists and stays one launch, as does the batch whose launch
+// forms a table.  RTAMD_PK_TILE_SPLIT=0 (read per launch): no lists.
 // RTAMD_PK_CONE_TAB=0 alone the cone words are still formed — the shadow words depend on them —
 // but only the shadow pointers reach the kernel.
 // The tile class words (tile_class_word, rt_shadow_table.hpp; TraceParams.class_tab / fr_ctab)
@@ -249,11 +258,12 @@ struct TabsWanted {
     int shadow_nl;  // shadow words per tile this launch's tables hold (0: cone masks only)
     bool cls;       // the tile class words too, one per tile after the shadow words
     bool clear;     // ... with their shadow-plane keep masks formed (else all ones)
+    bool lists;     // ... and the tile lists after them (the fix-up variant's split launch)
     int cls_kind() const { return cls ? (clear ? 2 : 1) : 0; }  // PkConeJobs.class_words
     bool any() const { return cone || shadow; }
 };
 TabsWanted tables_wanted(const rt_scene* sc, const TraceParams& p) {
-    TabsWanted w{false, false, 0, false, false};
+    TabsWanted w{false, false, 0, false, false, false};
     if (!packet_reads_cone_table(p, sc->max_specular > 0.0)) return w;
     const char* e = std::getenv("RTAMD_PK_CONE_TAB");
     w.cone = !(e && std::atoi(e) == 0);
@@ -264,6 +274,9 @@ TabsWanted tables_wanted(const rt_scene* sc, const TraceParams& p) {
     w.cls = w.cone && w.shadow && !(e && std::atoi(e) == 0);
     e = std::getenv("RTAMD_PK_PLANE_CLEAR");
     w.clear = w.cls && !(e && std::atoi(e) == 0);
+    // the tile lists serve frame batches that take the fix-up variant, and only those
+    w.lists = w.cls && p.nframes >= 1 && packet_uses_fixup(p, false, sc->max_specular > 0.0) &&
+              packet_split_wanted(p);
     return w;
 }
 
@@ -276,7 +289,7 @@ TabsWanted tables_wanted(const rt_scene* sc, const TraceParams& p) {
 // bias bit for bit: the words formed at one bias are wrong masks at a larger one.  Returns the
 // table's size.
 constexpr size_t kConeKeyWords = rt_scene::PkImage::ConeTab::kKeyWords;
-size_t cone_table_key(const TraceParams& p, double dz, int shadow_nl, int cls,
+size_t cone_table_key(const TraceParams& p, double dz, int shadow_nl, int cls, bool lists,
                       uint32_t (&key)[kConeKeyWords], size_t* tiles = nullptr) {
     uint32_t gx, gy, waves;
     packet_grid(p, gx, gy, waves);
@@ -293,24 +306,26 @@ size_t cone_table_key(const TraceParams& p, double dz, int shadow_nl, int cls,
         key[15] = static_cast<uint32_t>(shadow_nl);
         std::memcpy(key + 16, &p.bias, sizeof p.bias);
         // the class words follow the shadow words (1), with their keep masks formed (3)
-        key[18] = cls == 2 ? 3u : (cls ? 1u : 0u);
+        // ... and the tile lists follow the class words (4)
+        key[18] = (cls == 2 ? 3u : (cls ? 1u : 0u)) | (cls && lists ? 4u : 0u);
     }
     const size_t n = static_cast<size_t>(gx) * gy * waves;
     if (tiles) *tiles = n;
-    return sizeof(unsigned long long) * n *
-           (1 + static_cast<size_t>(shadow_nl > 0 ? shadow_nl + (cls ? 1 : 0) : 0));
+    return sizeof(unsigned long long) *
+           (n * (1 + static_cast<size_t>(shadow_nl > 0 ? shadow_nl + (cls ? 1 : 0) : 0)) +
+            (shadow_nl > 0 && cls && lists ? tile_list_words(n, static_cast<size_t>(gx) * gy) : 0));
 }
 
 // The cached camera's table for p's launch shape: *tab = the existing one (this stream ordered
 // after the launch that formed it), or a new entry whose table the caller forms (*fresh) and
 // whose event it records; null when the camera's table list is full.
 rt_status cone_table_entry(rt_context* ctx, rt_scene::PkImage& im, const TraceParams& p,
-                           double dz, int shadow_nl, int cls,
+                           double dz, int shadow_nl, int cls, bool lists,
                            rt_scene::PkImage::ConeTab** tab, bool* fresh) {
     *tab = nullptr;
     *fresh = false;
     uint32_t key[kConeKeyWords];
-    const size_t bytes = cone_table_key(p, dz, shadow_nl, cls, key);
+    const size_t bytes = cone_table_key(p, dz, shadow_nl, cls, lists, key);
     for (auto& t : im.tabs) {
         if (std::memcmp(t.key, key, sizeof key) != 0) continue;
         if (!t.done && t.stream != ctx->stream) {
@@ -331,8 +346,13 @@ rt_status cone_table_entry(rt_context* ctx, rt_scene::PkImage& im, const TracePa
     t.stream = ctx->stream;
     hipError_t e = t.buf.ensure(bytes);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&t.ready, hipEventDisableTiming);
+    if (e == hipSuccess && lists) {
+        e = hipHostMalloc(reinterpret_cast<void**>(&t.counts), sizeof(unsigned long long));
+        if (e == hipSuccess) __atomic_store_n(t.counts, 0ull, __ATOMIC_RELAXED);
+    }
     if (e != hipSuccess) {
         t.buf.release();
+        if (t.ready) (void)hipEventDestroy(t.ready);
         im.tabs.pop_back();
         return hip_fail(e, "cone table entry");
     }
@@ -345,18 +365,19 @@ void cone_table_drop(rt_scene::PkImage& im) {  // the entry cone_table_entry jus
     auto& t = im.tabs.back();
     t.buf.release();
     if (t.ready) (void)hipEventDestroy(t.ready);
+    if (t.counts) (void)hipHostFree(t.counts);
     im.tabs.pop_back();
 }
 
 // One-frame launches with an image entry (p.pk_image set, formed earlier on the stream).
 rt_status cone_table_single(rt_context* ctx, const rt_scene* sc, rt_scene::PkImage& im,
                             TraceParams& p) {
-    const TabsWanted want = tables_wanted(sc, p);
+    const TabsWanted want = tables_wanted(sc, p);  // (no lists: p.nframes == 0)
     if (!want.any()) return RT_OK;
     rt_scene::PkImage::ConeTab* t = nullptr;
     bool fresh = false;
-    const rt_status st =
-        cone_table_entry(ctx, im, p, p.cam_dz, want.shadow_nl, want.cls_kind(), &t, &fresh);
+    const rt_status st = cone_table_entry(ctx, im, p, p.cam_dz, want.shadow_nl, want.cls_kind(),
+                                          false, &t, &fresh);
     if (st != RT_OK || !t) return st;
     if (fresh) {
         PkConeJobs jobs;
@@ -375,7 +396,7 @@ rt_status cone_table_single(rt_context* ctx, const rt_scene* sc, rt_scene::PkIma
     }
     uint32_t key[kConeKeyWords];
     size_t tiles = 0;
-    (void)cone_table_key(p, p.cam_dz, want.shadow_nl, want.cls_kind(), key, &tiles);
+    (void)cone_table_key(p, p.cam_dz, want.shadow_nl, want.cls_kind(), false, key, &tiles);
     const unsigned long long* words = static_cast<const unsigned long long*>(t->buf.ptr);
     if (want.cone) p.cone_tab = words;
     if (want.shadow) p.shadow_tab = words + tiles;
@@ -428,9 +449,11 @@ rt_status packet_image(rt_context* ctx, const rt_scene* sc, TraceParams& p, int 
 // camera (a static camera), otherwise only an order built earlier for the shape.
 rt_status packet_batch_images(rt_context* ctx, const rt_scene* sc, const rt_camera* cams,
                               int nframes, TraceParams& p, int flags,
-                              rt_scene::PkImage::TileOrder** rec, int* batch_ring) {
+                              rt_scene::PkImage::TileOrder** rec, int* batch_ring,
+                              PkSplit* split) {
     *rec = nullptr;
     *batch_ring = -1;
+    *split = PkSplit{0u, 0u, 0u};
     enum Kind { kCached, kPromote, kRing, kDup };
     Kind kind[kPkMaxBatch];
     int dup_of[kPkMaxBatch];
@@ -526,15 +549,20 @@ rt_status packet_batch_images(rt_context* ctx, const rt_scene* sc, const rt_came
     rollback.armed = false;  // every promoted entry now has its image and its recorded event
     const rt_status ost = kind[0] == kCached ? tile_order(ctx, *ent[0], p, flags, rec, !same_cam)
                                              : scene_tile_order(ctx, sc, p, flags, rec);
-    const TabsWanted want = tables_wanted(sc, p);
+    TabsWanted want = tables_wanted(sc, p);
     if (ost != RT_OK || !want.any()) return ost;
+    // A batch with a first-seen camera (a moving camera) forms no lists and stays one launch: the
+    // host cannot know its counts before the launch, both grids would have to cover every tile,
+    // and the surplus workgroups cost more than the split saves (moving_camera −10 %,
+    // profiles/tile_split_ab.txt)
+    if (any_ring) want.lists = false;
     // The frames' cone tables, after their images on the stream: a cached or promoted camera's
     // from (or into) its entry, a ring frame's into the ring entry's table buffer up to its
     // cap, a duplicate's shared; every table that does not exist yet by ONE launch.
     uint32_t key[kConeKeyWords];
     size_t tiles = 0;
     const size_t tab_bytes =  // (the sizes only)
-        (cone_table_key(p, 0.0, want.shadow_nl, want.cls_kind(), key, &tiles) + 255) &
+        (cone_table_key(p, 0.0, want.shadow_nl, want.cls_kind(), want.lists, key, &tiles) + 255) &
         ~size_t(255);
     // (the cap counts the cone words and the class words; the shadow words come on top)
     const size_t cone_bytes =
@@ -560,6 +588,23 @@ rt_status packet_batch_images(rt_context* ctx, const rt_scene* sc, const rt_came
     std::memset(&cj, 0, sizeof cj);
     cj.shadow_nl = want.shadow_nl;
     cj.class_words = want.cls_kind();
+    cj.lists = want.lists ? 1 : 0;
+    PkListCounts lc;
+    std::memset(&lc, 0, sizeof lc);
+    // a frame's list counts where the host has them (a cache entry's table formed earlier):
+    // {uniform tiles, general workgroups}; a table formed by this call's launch has none yet, and
+    // its batch stays one launch
+    uint32_t gx, gy, waves;
+    packet_grid(p, gx, gy, waves);
+    uint32_t n_uni = 0, n_gen = 0;
+    bool all_lists = want.lists;
+    auto count_frame = [&](const unsigned long long* host) {
+        const unsigned long long v = host ? __atomic_load_n(host, __ATOMIC_RELAXED) : 0ull;
+        const uint32_t u = static_cast<uint32_t>(v), g = static_cast<uint32_t>(v >> 32);
+        if (!u || !g) all_lists = false;
+        n_uni = std::max(n_uni, u ? u - 1u : static_cast<uint32_t>(tiles));
+        n_gen = std::max(n_gen, g ? g - 1u : gx * gy);
+    };
     p.plane_masks = want.clear ? 1u : 0u;
     // the kernel's pointers of a frame whose table is (or will be) at `words`
     auto hand = [&](int f, const unsigned long long* words) {
@@ -584,6 +629,7 @@ rt_status packet_batch_images(rt_context* ctx, const rt_scene* sc, const rt_came
             continue;
         }
         if (kind[f] == kRing) {
+            if (ring_room == 0) all_lists = false;
             if (ring_room == 0) continue;  // past the cap: the wave forms its own mask
             --ring_room;
             dst = reinterpret_cast<unsigned long long*>(ring_tab);
@@ -592,28 +638,35 @@ rt_status packet_batch_images(rt_context* ctx, const rt_scene* sc, const rt_came
             rt_scene::PkImage::ConeTab* t = nullptr;
             bool fresh = false;
             st = cone_table_entry(ctx, *ent[f], p, p.fr_dz[f][0], want.shadow_nl,
-                                  want.cls_kind(), &t, &fresh);
+                                  want.cls_kind(), want.lists, &t, &fresh);
+            if (st != RT_OK || !t) all_lists = false;
             if (st != RT_OK || !t) continue;
             hand(f, static_cast<const unsigned long long*>(t->buf.ptr));
+            if (!fresh) count_frame(t->counts);
             if (!fresh) continue;
+            lc.host[cj.n] = t->counts;
             made[n_made] = ent[f];
             made_tab[n_made] = t;
             ++n_made;
             dst = static_cast<unsigned long long*>(t->buf.ptr);
         }
         hand(f, dst);
+        count_frame(nullptr);  // formed by this call's launch: not known yet
         cj.dst[cj.n] = dst;
         cj.frame[cj.n] = f;
         ++cj.n;
     }
     if (st == RT_OK) {
-        hipError_t ce = launch_packet_cone_tables(p, cj, ctx->stream);
+        hipError_t ce = launch_packet_cone_tables(p, cj, ctx->stream, &lc);
         for (int i = 0; i < n_made && ce == hipSuccess; ++i)
             ce = hipEventRecord(made_tab[i]->ready, ctx->stream);
         if (ce != hipSuccess) st = hip_fail(ce, "packet batch cone tables");
     }
     if (st != RT_OK)  // a table never formed must not be found by a later render
         for (int i = n_made - 1; i >= 0; --i) cone_table_drop(*made[i]);
+    if (st == RT_OK && all_lists) {  // every frame has its lists: the split launch
+        *split = PkSplit{static_cast<uint32_t>(tiles), n_uni, n_gen};
+    }
     return st;
 }
 

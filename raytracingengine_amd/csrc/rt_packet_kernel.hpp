@@ -434,7 +434,9 @@ __device__ __forceinline__ d3 pk_uniform_tile(const PacketScene& S, const TraceP
 
 // Waves per SIMD of a variant (its register budget).
 constexpr int pk_waves(int MAXC, int FEAT, bool COUNT, bool MULTI) {
-    return (FEAT == kFeatFix && MAXC == 1 && !MULTI && !COUNT) ? RT_PACKET_FIX_WAVES
+    return (FEAT == (kFeatFix | kFeatSplit) && MAXC == 1 && !MULTI && !COUNT)
+               ? RT_PACKET_GENERAL_WAVES
+         : (FEAT == kFeatFix && MAXC == 1 && !MULTI && !COUNT) ? RT_PACKET_FIX_WAVES
          : (FEAT == 0 && MAXC == 1 && !MULTI && !COUNT) ? RT_PACKET_SMALL_WAVES
          : (FEAT == (kFeatArea | kFeatNoPL) && !MULTI && !COUNT) ? RT_PACKET_AREA_WAVES
          : FEAT == kFeatTris ? RT_PACKET_TRIS_WAVES
@@ -442,8 +444,17 @@ constexpr int pk_waves(int MAXC, int FEAT, bool COUNT, bool MULTI) {
                 ? (MULTI ? (FEAT == 0 ? RT_PACKET_LEAN_WAVES : 1) : RT_PACKET_AA1_WAVES)
                 : 1);
 }
-template <int MAXC, int FEAT, bool COUNT, bool MULTI, int WGY>  // MULTI = false: one sample (AA = 1)
-__global__ __launch_bounds__(64 * kWgWavesX * WGY, pk_waves(MAXC, FEAT, COUNT, MULTI)) void packet_direct_kernel(TraceParams P) {
+// FEAT_ = kFeatFix | kFeatSplit is the fix-up variant's split launch (rt_packet.hip
+// launch_packet_split): the launch is a row of workgroups per frame, workgroup blockIdx.x renders
+// the blockIdx.x-th entry of the frame's list of general workgroups (rt_shadow_table.hpp, after
+// the frame's class words) and returns at once past the list's count; a wave whose tile is
+// uniform takes part in the staging and its barrier and returns — packet_uniform_kernel renders
+// that tile — so pk_uniform_tile is not compiled into this launch.  The bit is taken off FEAT,
+// so the body reads as it did and every other instantiation keeps its name and its code.
+template <int MAXC, int FEAT_, bool COUNT, bool MULTI, int WGY>  // MULTI = false: one sample (AA = 1)
+__global__ __launch_bounds__(64 * kWgWavesX * WGY, pk_waves(MAXC, FEAT_, COUNT, MULTI)) void packet_direct_kernel(TraceParams P) {
+    constexpr int FEAT = FEAT_ & ~kFeatSplit;
+    constexpr bool SPLIT = (FEAT_ & kFeatSplit) != 0;
     extern __shared__ __attribute__((aligned(16))) double smem[];
     const int tid = threadIdx.x;
     constexpr bool kNoPL = (FEAT & kFeatNoPL) != 0;  // the launcher checked P.np == P.nl == 0
@@ -455,10 +466,15 @@ __global__ __launch_bounds__(64 * kWgWavesX * WGY, pk_waves(MAXC, FEAT, COUNT, M
     // scene, camera and shape: packet_order_kernel) the cheapest tiles fill the end instead.
     const uint32_t lin = blockIdx.y * gridDim.x + blockIdx.x;  // dispatch position
     uint32_t tbx = blockIdx.x, tby = gridDim.y - 1 - blockIdx.y;
-    if (P.tile_order) {
-        const uint32_t t = P.tile_order[lin];
-        tbx = t % gridDim.x;
-        tby = t / gridDim.x;
+    // the tile grid's workgroups per row (tables are indexed by tile, not by dispatch position)
+    // (the split launch's grid is not the tile grid: the launch shape's, packet_grid)
+    const uint32_t gxw = SPLIT ? (P.width + kPkW * kWgWavesX - 1) / (kPkW * kWgWavesX) : gridDim.x;
+    if constexpr (!SPLIT) {
+        if (P.tile_order) {
+            const uint32_t t = P.tile_order[lin];
+            tbx = t % gridDim.x;
+            tby = t / gridDim.x;
+        }
     }
     // the recording launch (the general variant, rt_packet_host.cpp tile_order): each wave's start
     uint64_t t_start = 0;
@@ -494,8 +510,8 @@ __global__ __launch_bounds__(64 * kWgWavesX * WGY, pk_waves(MAXC, FEAT, COUNT, M
     // The fix-up variant of those also reads the tiles' class words (pk_uniform_tile).  The
     // marching variant does not: its undecided lanes march over the LDS image, so it would have
     // to keep the staging, and it stays on the general path as it is.
-    constexpr bool kUni = kTab && FEAT == kFeatFix;
-    const unsigned long long* class_tab = kUni ? P.class_tab : nullptr;
+    constexpr bool kUni = kTab && FEAT == kFeatFix && !SPLIT;
+    const unsigned long long* class_tab = (kUni || SPLIT) ? P.class_tab : nullptr;
     double cam_dz = P.cam_dz, cam_dz2 = P.cam_dz2;
     if (P.nframes) {
         const PkFrame& F = P.fr[blockIdx.z];
@@ -510,7 +526,18 @@ __global__ __launch_bounds__(64 * kWgWavesX * WGY, pk_waves(MAXC, FEAT, COUNT, M
             cone_tab = P.fr_tab[blockIdx.z];
             shadow_tab = P.fr_stab[blockIdx.z];
         }
-        if constexpr (kUni) class_tab = P.fr_ctab[blockIdx.z];
+        if constexpr (kUni || SPLIT) class_tab = P.fr_ctab[blockIdx.z];
+    }
+    if constexpr (SPLIT) {
+        // this workgroup's entry of the frame's general list (the launcher checked that every
+        // frame has class words and lists); past the count: nothing to render (uniform)
+        const uint32_t split_tiles =
+            gxw * ((P.rows + kPkH * WGY - 1) / (kPkH * WGY)) * (kWgWavesX * WGY);
+        const pk_culp hdr = (pk_culp)class_tab + split_tiles;
+        if (lin >= static_cast<uint32_t>(hdr[0] >> 32)) return;
+        const uint32_t t = ((pk_cip)(hdr + 1 + split_tiles))[lin];
+        tbx = t % gxw;
+        tby = t / gxw;
     }
     const d3 cam = mk(camp[0], camp[1], camp[2]);
     constexpr int kThreads = 64 * kWgWavesX * WGY;
@@ -524,7 +551,7 @@ __global__ __launch_bounds__(64 * kWgWavesX * WGY, pk_waves(MAXC, FEAT, COUNT, M
     if constexpr (kUni) {
         if (class_tab && pk_img && P.max_rec > 0) {
             const pk_culp cw =
-                (pk_culp)class_tab + (tby * gridDim.x + tbx) * (kWgWavesX * WGY);
+                (pk_culp)class_tab + (tby * gxw + tbx) * (kWgWavesX * WGY);
             const uint32_t w = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(tid >> 6));
             bool all = true;
 #pragma unroll
@@ -536,12 +563,20 @@ __global__ __launch_bounds__(64 * kWgWavesX * WGY, pk_waves(MAXC, FEAT, COUNT, M
             staged = !all;
         }
     }
+    if constexpr (SPLIT) {
+        // a listed workgroup has a general wave, so it stages; this wave's own word says
+        // whether it goes on after the barrier
+        const uint32_t w = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(tid >> 6));
+        cls = ((pk_culp)class_tab)[(tby * gxw + tbx) * (kWgWavesX * WGY) + w];
+    }
     if (pk_img && staged) {  // the image of this scene and camera, formed once (packet_image_kernel)
         const float4* src = reinterpret_cast<const float4*>(pk_img);
         float4* dst = reinterpret_cast<float4*>(smem);
         const int nv = static_cast<int>(pk_image_bytes(ns, np, nl) / 16);
         for (int i = tid; i < nv; i += kThreads) dst[i] = src[i];
         __syncthreads();
+        if constexpr (SPLIT)
+            if (tile_class_of(cls) != kTileGeneral) return;  // packet_uniform_kernel's tile
     } else if (pk_img) {
         // (a workgroup of uniform tiles: no image in LDS)
     } else if (pk_pub) {
@@ -674,7 +709,7 @@ __global__ __launch_bounds__(64 * kWgWavesX * WGY, pk_waves(MAXC, FEAT, COUNT, M
                         Masks<MAXC> T;
                         const uint32_t w =
                             __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(wave));
-                        T.m[0] = ((pk_culp)cone_tab)[(tby * gridDim.x + tbx) * (kWgWavesX * WGY) + w];
+                        T.m[0] = ((pk_culp)cone_tab)[(tby * gxw + tbx) * (kWgWavesX * WGY) + w];
                         T.pm = ~0ull;
                         return T;
                     }
@@ -742,7 +777,7 @@ __global__ __launch_bounds__(64 * kWgWavesX * WGY, pk_waves(MAXC, FEAT, COUNT, M
                     const uint32_t w =
                         __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(wave));
                     stab = shadow_tab + static_cast<size_t>(
-                               (tby * gridDim.x + tbx) * (kWgWavesX * WGY) + w) * nl;
+                               (tby * gxw + tbx) * (kWgWavesX * WGY) + w) * nl;
                 }
                 for (int l = 0; l < nl; ++l) {
                     d3 L, E;
@@ -831,56 +866,7 @@ __global__ __launch_bounds__(64 * kWgWavesX * WGY, pk_waves(MAXC, FEAT, COUNT, M
     const uint32_t wave_e = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(wave));
     const uint32_t x_e = tbx * (kPkW * kWgWavesX) + (wave_e % kWgWavesX) * kPkW + (lane_e % kPkW);
     const uint32_t yl_e = tby * (kPkH * WGY) + (wave_e / kWgWavesX) * kPkH + (lane_e / kPkW);
-    bool store = x_e < P.width && yl_e < P.rows;
-    if constexpr ((FEAT & kFeatFix) != 0) {
-        // the pixels with an undecided shadow ray: appended to the fix-up list (one atomic per
-        // wave), rendered by packet_fixup_kernel after this launch instead of stored here
-        const bool q = fix && store;
-        const uint64_t bq = __ballot(q);
-        if (bq) {
-            uint32_t base = 0;
-            if (lane_e == static_cast<uint32_t>(__builtin_ctzll(bq)))
-                base = atomicAdd(P.fix_ctl, static_cast<uint32_t>(__builtin_popcountll(bq)));
-            base = __shfl(base, __builtin_ctzll(bq), 64);
-            if (q)
-                P.fix_list[base + __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(bq >> 32),
-                                                            __builtin_amdgcn_mbcnt_lo(
-                                                                static_cast<uint32_t>(bq), 0u))] =
-                    static_cast<uint32_t>(frame_off + static_cast<size_t>(yl_e) * P.width + x_e);
-        }
-        store = store && !fix;
-    }
-    if (store) {
-        // accumulated / samples (Scene.h:298-300); x / 1.0 == x, so AA=1 skips the division
-        const d3 v = samples == 1 ? acc
-                   : (samples > 0 ? sdiv(acc, static_cast<double>(samples)) : mk(0.0, 0.0, 0.0));
-        const size_t o = frame_off + static_cast<size_t>(yl_e) * P.width + x_e;
-        if (P.out64) {
-            P.out64[3 * o + 0] = v.x;
-            P.out64[3 * o + 1] = v.y;
-            P.out64[3 * o + 2] = v.z;
-        }
-        if (P.out32) {
-            P.out32[3 * o + 0] = static_cast<float>(v.x);
-            P.out32[3 * o + 1] = static_cast<float>(v.y);
-            P.out32[3 * o + 2] = static_cast<float>(v.z);
-        }
-        if (P.ldr) {
-            uint8_t r, g, b;
-            if (P.tonemap == 1) {  // uniform: Reinhard, through the FP32 byte decision
-                r = reinhard_byte(v.x);
-                g = reinhard_byte(v.y);
-                b = reinhard_byte(v.z);
-            } else if constexpr ((FEAT & kFeatJodie) != 0) {
-                to_color(tonemap_op(v, P.tonemap), r, g, b);
-            } else {
-                to_color(tonemap_op_nolog(v, P.tonemap), r, g, b);
-            }
-            P.ldr[3 * o + 0] = r;
-            P.ldr[3 * o + 1] = g;
-            P.ldr[3 * o + 2] = b;
-        }
-    }
+#include "rt_packet_epilogue.hpp"
     if constexpr (COUNT) {
         uint32_t t = cnt.trace, sh = cnt.shadow;
         for (int off = 32; off > 0; off >>= 1) {

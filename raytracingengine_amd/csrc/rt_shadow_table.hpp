@@ -56,6 +56,7 @@
 #pragma once
 
 #include <math.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #include "rt_cone_table.hpp"
@@ -439,6 +440,74 @@ RT_CT_HD inline unsigned long long tile_class_pack(unsigned long long cls, const
 }
 RT_CT_HD inline unsigned tile_plane_keep(unsigned long long word, int l) {
     return static_cast<unsigned>(word >> (8 + 8 * l)) & kPlaneKeepAll;
+}
+
+// The tile lists of a frame (packet_uniform_kernel and the split launch of packet_direct_kernel,
+// rt_packet_kernel.hpp): formed from the class words by the lane that forms them, they follow the
+// class words in the table's buffer —
+//   1 word    the counts: uniform tiles in the low half, general workgroups in the high half
+//   T words   the uniform tiles, one entry each (room for every tile)
+//   W/2 words the general workgroups, one 32-bit workgroup index tby · gx + tbx each
+// for T tiles in W workgroups of `waves` tiles.  A tile is *uniform* when its class is not
+// kTileGeneral; a workgroup is *general*, and listed, when at least one of its tiles is not
+// uniform.  Every tile is therefore rendered exactly once: by the uniform kernel when it is
+// uniform, else by its wave of the listed workgroup (whose uniform waves return).
+// A uniform entry is the tile's class word (bits 0-39: the class and up to four keep masks) with
+// the tile's column and row in 8-pixel units above it (12 bits each), so the kernel that reads
+// the list needs no second lookup and no division.
+// The table kernel works on runs of 64 consecutive list positions (one wavefront): position i
+// stands for tile T − 1 − i, so the lists come out roughly bottom-up, the order the general
+// kernel's default dispatch has.  `waves` (2 or 4) divides 64 and T, so the tiles of a workgroup
+// are `waves` adjacent, aligned lanes of one run.  The order of the runs in a list is whatever
+// the runs' atomic adds make it; a list's order only permutes which workgroup renders which tile.
+// kIndexOff and kDropMixed exist for the host test's mutants only (an entry's column off by one;
+// a workgroup listed only when all of its tiles are general).
+constexpr int kListColShift = 40, kListRowShift = 52;
+constexpr unsigned long long kListWordMask = (1ull << kListColShift) - 1ull;
+constexpr uint32_t kListCoordMask = 0xfffu;
+constexpr uint32_t kListMaxCoord = kListCoordMask + 1u;  // tile columns and rows a list can name
+RT_CT_HD inline size_t tile_list_words(size_t tiles, size_t wgs) {
+    return 1 + tiles + (wgs + 1) / 2;
+}
+RT_CT_HD inline uint32_t tile_list_tile(uint32_t pos, uint32_t tiles) { return tiles - 1u - pos; }
+RT_CT_HD inline bool tile_list_uniform(unsigned long long word) {
+    return tile_class_of(word) != kTileGeneral;
+}
+template <int kIndexOff = 0>
+RT_CT_HD inline unsigned long long tile_list_entry(unsigned long long word, uint32_t x0,
+                                                   uint32_t yl0) {
+    return (word & kListWordMask) |
+           (static_cast<unsigned long long>((x0 / 8u + kIndexOff) & kListCoordMask) << kListColShift) |
+           (static_cast<unsigned long long>((yl0 / 8u) & kListCoordMask) << kListRowShift);
+}
+// Whether the workgroup of run lane `lane` is listed, from the run's mask of general tiles.
+template <bool kDropMixed = false>
+RT_CT_HD inline bool tile_list_wg_listed(uint64_t general, unsigned lane, unsigned waves) {
+    const uint64_t group = (waves >= 64u ? ~0ull : (1ull << waves) - 1ull);
+    const uint64_t g = (general >> (lane & ~(waves - 1u))) & group;
+    return kDropMixed ? g == group : g != 0;
+}
+// One run of up to 64 list positions from `pos0` on, as one wavefront of the table kernel forms
+// it: words[] are the frame's class words by tile; the run's uniform entries go to uni[*n_uni …]
+// and its listed workgroups to gen[*n_gen …] (the kernel takes the two bases with one atomic add
+// each).  x0_of / yl0_of give a tile's pixel origin.
+template <int kIndexOff = 0, bool kDropMixed = false, class Origin>
+inline void tile_list_run(const unsigned long long* words, uint32_t tiles, uint32_t waves,
+                          uint32_t pos0, Origin origin, unsigned long long* uni, uint32_t* n_uni,
+                          uint32_t* gen, uint32_t* n_gen) {
+    uint64_t general = 0;
+    for (uint32_t l = 0; l < 64 && pos0 + l < tiles; ++l)
+        if (!tile_list_uniform(words[tile_list_tile(pos0 + l, tiles)])) general |= 1ull << l;
+    for (uint32_t l = 0; l < 64 && pos0 + l < tiles; ++l) {
+        const uint32_t t = tile_list_tile(pos0 + l, tiles);
+        if (tile_list_uniform(words[t])) {
+            uint32_t x0, yl0;
+            origin(t, x0, yl0);
+            uni[(*n_uni)++] = tile_list_entry<kIndexOff>(words[t], x0, yl0);
+        }
+        if ((l & (waves - 1u)) == 0 && tile_list_wg_listed<kDropMixed>(general, l, waves))
+            gen[(*n_gen)++] = t / waves;
+    }
 }
 
 }  // namespace rtamd
