@@ -853,6 +853,18 @@ rt_status rt_debug_plane_clear(rt_context* ctx, uint64_t* with_masks, uint64_t* 
  * RTAMD_PK_TILE_SPLIT=0 in the environment, read per launch, keeps the single launch. */
 rt_status rt_debug_tile_split(rt_context* ctx, uint64_t* split, uint64_t* single);
 
+/* Test hook (read-only): frames enqueued through the fix-up variant of the packet kernel with a
+ * launch over the frame's list of shadowed-plane tiles (*with: tiles that see one plane and whose
+ * shadow rays can meet a sphere, rendered by the uniform kernel's second form between the split
+ * launch's two kernels) and without one (*without: the single launch, a split launch whose tables
+ * were formed without that list, or a batch none of whose frames has such a tile).
+ * RTAMD_PK_TILE_SHADOWED=0 in the environment, read per launch, forms no such list. */
+rt_status rt_debug_tile_shadowed(rt_context* ctx, uint64_t* with, uint64_t* without);
+
+/* Test hook (read-only, waits for the context's stream): the pixels the context's last launch of
+ * the packet kernel's fix-up variant queued for its fix-up launch (0 before the first one). */
+rt_status rt_debug_fixup_count(rt_context* ctx, uint32_t* pixels);
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif

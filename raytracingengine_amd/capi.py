@@ -95,6 +95,7 @@ EXPORTED = [
     "rt_debug_tile_class",
     "rt_debug_plane_clear",
     "rt_debug_tile_split",
+    "rt_debug_tile_shadowed", "rt_debug_fixup_count",
     "rt_occluded_rays", "rt_occluded_rays_device",
     "rt_transmittance_rays", "rt_transmittance_rays_device",
     "rt_light_transmittance", "rt_light_transmittance_device",
@@ -303,6 +304,8 @@ def load_library(path: str = LIB_PATH):
         "rt_debug_tile_class": [vp, vp, vp],
         "rt_debug_plane_clear": [vp, vp, vp],
         "rt_debug_tile_split": [vp, vp, vp],
+        "rt_debug_tile_shadowed": [vp, vp, vp],
+        "rt_debug_fixup_count": [vp, vp],
         "rt_debug_assemble_rows": [vp, vp, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_uint32,
                                    ctypes.c_uint32, ctypes.c_uint32, vp],
     }.items():
@@ -469,6 +472,18 @@ class Context:
         a, b = ctypes.c_uint64(), ctypes.c_uint64()
         _check(_lib.rt_debug_tile_split(self._h, ctypes.byref(a), ctypes.byref(b)))
         return a.value, b.value
+
+    def debug_tile_shadowed(self) -> tuple[int, int]:
+        """Fix-up variant frames enqueued so far (with, without) a launch over shadowed tiles."""
+        a, b = ctypes.c_uint64(), ctypes.c_uint64()
+        _check(_lib.rt_debug_tile_shadowed(self._h, ctypes.byref(a), ctypes.byref(b)))
+        return a.value, b.value
+
+    def debug_fixup_count(self) -> int:
+        """Pixels the last fix-up variant launch of this context queued for its fix-up launch."""
+        n = ctypes.c_uint32()
+        _check(_lib.rt_debug_fixup_count(self._h, ctypes.byref(n)))
+        return n.value
 
     def debug_vec_ops(self, v: np.ndarray) -> np.ndarray:
         v = np.ascontiguousarray(v, np.float64).reshape(-1, 3)

@@ -375,6 +375,9 @@ rt_status enqueue_frames(rt_context* ctx, const rt_scene* sc, const rt_camera* c
     if (!fixup || p.tile_order) pk_split.tiles = 0;
     if (packet && fixup)
         (pk_split.tiles ? ctx->tile_split_frames : ctx->tile_nosplit_frames) += nframes;
+    if (packet && fixup)  // rt_debug_tile_shadowed: the split launch's third kernel
+        ((pk_split.tiles && pk_split.sh_n) ? ctx->tile_shadowed_frames
+                                           : ctx->tile_noshadowed_frames) += nframes;
     // generic kernels without triangle / area-light code for scenes that use neither
     const bool lean_generic = p.nt == 0 && p.al_samples == 0;
     // reflection chains of scenes made of planes (and up to kBoxMaxSpheres spheres) take the
@@ -1908,6 +1911,26 @@ rt_status rt_debug_tile_split(rt_context* ctx, uint64_t* split, uint64_t* single
         return fail(RT_ERR_INVALID_ARG, "NULL argument to rt_debug_tile_split");
     *split = ctx->tile_split_frames;
     *single = ctx->tile_nosplit_frames;
+    return RT_OK;
+}
+
+rt_status rt_debug_tile_shadowed(rt_context* ctx, uint64_t* with, uint64_t* without) {
+    if (!ctx || !with || !without)
+        return fail(RT_ERR_INVALID_ARG, "NULL argument to rt_debug_tile_shadowed");
+    *with = ctx->tile_shadowed_frames;
+    *without = ctx->tile_noshadowed_frames;
+    return RT_OK;
+}
+
+rt_status rt_debug_fixup_count(rt_context* ctx, uint32_t* pixels) {
+    if (!ctx || !pixels) return fail(RT_ERR_INVALID_ARG, "NULL argument to rt_debug_fixup_count");
+    *pixels = 0;
+    if (!ctx->fix_ctl.ptr) return RT_OK;
+    DeviceGuard g(ctx->device);
+    RT_HIP(hipStreamSynchronize(ctx->stream));
+    // the count the last fix-variant launch appended to: its fix-up launch zeroed the other one
+    RT_HIP(hipMemcpy(pixels, static_cast<const uint32_t*>(ctx->fix_ctl.ptr) + (1 - ctx->fix_parity),
+                     sizeof(uint32_t), hipMemcpyDeviceToHost));
     return RT_OK;
 }
 

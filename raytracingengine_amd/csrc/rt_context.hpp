@@ -90,6 +90,8 @@ struct rt_context {
     uint64_t plane_mask_frames = 0, plane_nomask_frames = 0;
     // ... and through the fix-up variant's split launch / its single launch (rt_debug_tile_split)
     uint64_t tile_split_frames = 0, tile_nosplit_frames = 0;
+    // ... and with / without a launch over a list of shadowed-plane tiles (rt_debug_tile_shadowed)
+    uint64_t tile_shadowed_frames = 0, tile_noshadowed_frames = 0;
     // rt_render_multi: RCCL communicators over the devices of the last context list this
     // context led (rt_multi.cpp); destroyed with the context
     std::vector<rt_context*> group_ctxs;
@@ -155,9 +157,10 @@ struct rt_scene {
             hipEvent_t ready = nullptr;
             hipStream_t stream = nullptr;
             bool done = false;
-            // with tile lists (the key says so): a pinned host word the launch that forms the
-            // table fills with the lists' counts, each plus one — uniform tiles in the low
-            // half, general workgroups in the high half; 0: not formed yet
+            // with tile lists (the key says so): two pinned host words the launch that forms the
+            // table fills with the lists' counts, each plus one — uniform tiles in the first
+            // word's low half, general workgroups in its high half, shadowed-plane tiles in the
+            // second word; 0: not formed yet
             unsigned long long* counts = nullptr;
         };
         std::vector<ConeTab> tabs;

@@ -159,10 +159,13 @@ struct TraceParams {
 // by its tile lists (rt_shadow_table.hpp), at fr_ctab[f] + tiles; tiles == 0: no lists, one
 // launch as before.  uni_n and gen_n: the uniform tiles and general workgroups the two launches
 // cover per frame — the largest count of the batch's frames where the host knows them, every
-// tile or workgroup where it does not.  Host only: TraceParams keeps its size and layout.
+// tile or workgroup where it does not.  sh_n: the same for the shadowed-plane tiles
+// (packet_uniform_kernel<true>, between the two; 0 where the tables were formed without that
+// list).  Host only: TraceParams keeps its size and layout.
 struct PkSplit {
     uint32_t tiles;
     uint32_t uni_n, gen_n;
+    uint32_t sh_n;
 };
 // the runtime passes at most 4 KiB of kernel arguments (packet_image_batch_kernel and
 // packet_cone_table_kernel take a job list of kPkMaxBatch pointers and ints next to it)
@@ -242,12 +245,13 @@ struct PkConeJobs {
     // (shadow_plane_keep), 1: with all-ones masks
     int32_t class_words;
     // != 0 (with class_words only): the tile lists too, after the class words:
-    // dst[j] + tiles · (2 + shadow_nl), tile_list_words(tiles, workgroups) words
+    // dst[j] + tiles · (2 + shadow_nl), tile_list_words(tiles, workgroups) words; 2: with the
+    // shadowed-plane tiles marked in their class words and filed in the third list
     int32_t lists;
 };
-// host[j], when set, is a pinned host word that receives job j's two list counts once the table
-// is formed: uniform tiles in the low half, general workgroups in the high half, each plus one
-// (0: not yet)
+// host[j], when set, points at two pinned host words that receive job j's three list counts once
+// the table is formed: uniform tiles in the first word's low half, general workgroups in its high
+// half, shadowed tiles in the second word, each plus one (0: not yet)
 struct PkListCounts {
     unsigned long long* host[kPkMaxBatch];
 };

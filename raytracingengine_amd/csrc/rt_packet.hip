@@ -124,7 +124,11 @@ __global__ __launch_bounds__(kConeThreads, 5) void packet_cone_table_kernel(Trac
     // image follows its planes and lights (pk_build_image).  The OR of the tile's shadow words
     // stands for them (zero iff every one is; the launcher checked shadow_nl <= kShadowTabLights)
     const double* pln = img + kPkSph * ns + kPlStride * P.np + kLtStride * P.nl;
-    const unsigned long long cw = tile_class_word(cone, SB, &any, 1, pln, P.np) | keep;
+    // (J.lists == 2: the shadowed-plane mark too, tile_shadowed_mark.  `any` stands for the words
+    // here as well: a real word has no bit 63, so their OR is all ones iff one of them is)
+    const unsigned long long mark =
+        J.lists == 2 ? tile_shadowed_mark(cone, SB, &any, 1, pln, P.np) : 0ull;
+    const unsigned long long cw = tile_class_word(cone, SB, &any, 1, pln, P.np) | keep | mark;
     J.dst[blockIdx.y][static_cast<size_t>(gx) * gy * waves * (1 + J.shadow_nl) + t] = cw;
     if (!J.lists) return;
     // the tile lists: the active lanes of this wavefront are a run's first lanes (lane 0 among
@@ -134,35 +138,51 @@ __global__ __launch_bounds__(kConeThreads, 5) void packet_cone_table_kernel(Trac
     unsigned long long* uni = hdr + 1;
     uint32_t* gen = reinterpret_cast<uint32_t*>(hdr + 1 + tiles);
     const uint32_t lane = threadIdx.x & 63u;
-    const bool is_uni = tile_list_uniform(cw);
-    const uint64_t bu = __ballot(is_uni), bg = __ballot(!is_uni);
+    const bool is_uni = tile_list_uniform(cw), is_sh = tile_list_shadowed(cw);
+    const uint64_t bu = __ballot(is_uni), bs = __ballot(is_sh), bg = __ballot(!is_uni && !is_sh);
     const bool lead = (lane & (waves - 1u)) == 0 && tile_list_wg_listed(bg, lane, waves);
     const uint64_t bl = __ballot(lead);
-    uint32_t base_u = 0, base_g = 0;
+    uint32_t base_u = 0, base_g = 0, base_s = 0;
     if (lane == 0) {
         if (bu) base_u = atomicAdd(reinterpret_cast<uint32_t*>(hdr),
                                    static_cast<uint32_t>(__builtin_popcountll(bu)));
         if (bl) base_g = atomicAdd(reinterpret_cast<uint32_t*>(hdr) + 1,
                                    static_cast<uint32_t>(__builtin_popcountll(bl)));
+        if (bs)
+            base_s = atomicAdd(reinterpret_cast<uint32_t*>(
+                                   hdr + tile_list_shadowed_count(tiles, static_cast<size_t>(gx) * gy)),
+                               static_cast<uint32_t>(__builtin_popcountll(bs)));
     }
     base_u = __shfl(base_u, 0, 64);
     base_g = __shfl(base_g, 0, 64);
+    base_s = __shfl(base_s, 0, 64);
     const uint64_t below = (1ull << lane) - 1ull;
     if (is_uni) uni[base_u + __builtin_popcountll(bu & below)] = tile_list_entry(cw, x0, yl0);
+    if (is_sh)
+        uni[tile_list_shadowed_slot(base_s + __builtin_popcountll(bs & below),
+                                    static_cast<uint32_t>(tiles))] = tile_shadowed_entry(cw, x0, yl0);
     if (lead) gen[base_g + __builtin_popcountll(bl & below)] = wg;
 }
 
 // The list counts of a table launch's jobs: zeroed before it, and handed to the host after it
 // (each plus one in a pinned word, so 0 says "not yet") where the table has a cache entry.
-__global__ __launch_bounds__(64) void packet_list_zero_kernel(PkConeJobs J, size_t hdr) {
-    if (static_cast<int>(threadIdx.x) < J.n) J.dst[threadIdx.x][hdr] = 0ull;
+// (hdr: the word of the uniform and general counts, hdr_s: the shadowed count's; the host's second
+// word receives that count plus one)
+__global__ __launch_bounds__(64) void packet_list_zero_kernel(PkConeJobs J, size_t hdr,
+                                                              size_t hdr_s) {
+    if (static_cast<int>(threadIdx.x) >= J.n) return;
+    J.dst[threadIdx.x][hdr] = 0ull;
+    J.dst[threadIdx.x][hdr_s] = 0ull;
 }
 __global__ __launch_bounds__(64) void packet_list_counts_kernel(PkConeJobs J, PkListCounts C,
-                                                                size_t hdr) {
+                                                                size_t hdr, size_t hdr_s) {
     if (static_cast<int>(threadIdx.x) >= J.n || !C.host[threadIdx.x]) return;
     const unsigned long long v = J.dst[threadIdx.x][hdr];
+    const unsigned long long s = J.dst[threadIdx.x][hdr_s];
     __hip_atomic_store(C.host[threadIdx.x],
                        (((v >> 32) + 1ull) << 32) | ((v & 0xffffffffull) + 1ull), __ATOMIC_RELAXED,
+                       __HIP_MEMORY_SCOPE_SYSTEM);
+    __hip_atomic_store(C.host[threadIdx.x] + 1, (s & 0xffffffffull) + 1ull, __ATOMIC_RELAXED,
                        __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
@@ -176,6 +196,7 @@ hipError_t launch_packet_cone_tables(const TraceParams& p, const PkConeJobs& job
     if (jobs.class_words != 0 && jobs.shadow_nl <= 0) return hipErrorInvalidValue;
     if (jobs.class_words < 0 || jobs.class_words > 2) return hipErrorInvalidValue;
     if (jobs.lists != 0 && jobs.class_words == 0) return hipErrorInvalidValue;
+    if (jobs.lists < 0 || jobs.lists > 2) return hipErrorInvalidValue;
     for (int j = 0; j < jobs.n; ++j) {
         const int f = jobs.frame[j];
         if (!jobs.dst[j] || f < -1 || f >= static_cast<int>(p.nframes) ||
@@ -186,11 +207,13 @@ hipError_t launch_packet_cone_tables(const TraceParams& p, const PkConeJobs& job
     packet_grid(p, gx, gy, waves);
     const uint32_t tiles = gx * gy * waves;
     const size_t hdr = static_cast<size_t>(tiles) * (2 + jobs.shadow_nl);
+    const size_t hdr_s = hdr + tile_list_shadowed_count(tiles, static_cast<size_t>(gx) * gy);
     if (jobs.lists) {
         // (a list entry names a tile by 12-bit column and row: packet_split_wanted)
         if (gx * kWgWavesX > kListMaxCoord || gy * (waves / kWgWavesX) > kListMaxCoord)
             return hipErrorInvalidValue;
-        hipLaunchKernelGGL(packet_list_zero_kernel, dim3(1), dim3(64), 0, stream, jobs, hdr);
+        hipLaunchKernelGGL(packet_list_zero_kernel, dim3(1), dim3(64), 0, stream, jobs, hdr,
+                           hdr_s);
     }
     hipLaunchKernelGGL(packet_cone_table_kernel,
                        dim3((tiles + kConeThreads - 1) / kConeThreads,
@@ -198,7 +221,7 @@ hipError_t launch_packet_cone_tables(const TraceParams& p, const PkConeJobs& job
                        dim3(kConeThreads), 0, stream, p, jobs, gx, gy, waves);
     if (jobs.lists && counts)
         hipLaunchKernelGGL(packet_list_counts_kernel, dim3(1), dim3(64), 0, stream, jobs, *counts,
-                           hdr);
+                           hdr, hdr_s);
     return hipGetLastError();
 }
 
@@ -438,15 +461,23 @@ bool packet_uses_fixup(const TraceParams& p, bool count, bool any_specular) {
 #ifndef RT_PACKET_UNI_WAVES
 #define RT_PACKET_UNI_WAVES 8
 #endif
+// SPH = true: the same kernel over the frame's list of shadowed-plane tiles (tile_shadowed_mark,
+// rt_shadow_table.hpp: entries of the same format from the end of the uniform list's words
+// downwards, their count after the general list), which also hands pk_uniform_tile the tile's
+// shadow words — P.fr_stab of the frame at the tile the entry's column and row name, nl words —
+// for the sphere block of the shadow classification.  SPH = false is the kernel as it was.
 constexpr int kUniThreads = RT_PACKET_UNI_THREADS;
+template <bool SPH>
 __global__ __launch_bounds__(kUniThreads, RT_PACKET_UNI_WAVES) void packet_uniform_kernel(TraceParams P, uint32_t tiles) {
     constexpr int FEAT = kFeatFix;
     const PkFrame& F = P.fr[blockIdx.z];  // (split launches are frame batches: P.nframes >= 1)
     const pk_culp hdr = (pk_culp)P.fr_ctab[blockIdx.z] + tiles;
     const uint32_t i = blockIdx.x * (kUniThreads / 64) +
                        __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(threadIdx.x) >> 6);
-    if (i >= static_cast<uint32_t>(hdr[0])) return;
-    const unsigned long long e = hdr[1 + i];
+    // (one wave row per workgroup, packet_split_wanted: tiles / kWgWavesX workgroups)
+    if (i >= static_cast<uint32_t>(hdr[SPH ? tile_list_shadowed_count(tiles, tiles / kWgWavesX) : 0]))
+        return;
+    const unsigned long long e = hdr[1 + (SPH ? tile_list_shadowed_slot(i, tiles) : i)];
     const unsigned long long cls = e & kListWordMask;
     const uint32_t col = static_cast<uint32_t>(e >> kListColShift) & kListCoordMask;
     const uint32_t row = static_cast<uint32_t>(e >> kListRowShift) & kListCoordMask;
@@ -465,7 +496,17 @@ __global__ __launch_bounds__(kUniThreads, RT_PACKET_UNI_WAVES) void packet_unifo
     bool fix = false;
     PacketScene S;  // (not read: the records come through the scalar cache)
     S.lt = nullptr;
-    const d3 col3 = pk_uniform_tile<1, FEAT>(S, P, F.img, cls, cam, d, P.ns, P.np, P.nl, P.bias, fix);
+    d3 col3;
+    if constexpr (SPH) {
+        // the tile's index in the frame's tables: row · (tile columns) + column
+        const uint32_t cols = (P.width + kPkW * kWgWavesX - 1) / (kPkW * kWgWavesX) * kWgWavesX;
+        const unsigned long long* stab =
+            P.fr_stab[blockIdx.z] + static_cast<size_t>(row * cols + col) * P.nl;
+        col3 = pk_uniform_tile<1, FEAT, true>(S, P, F.img, cls, cam, d, P.ns, P.np, P.nl, P.bias,
+                                              fix, stab);
+    } else {
+        col3 = pk_uniform_tile<1, FEAT>(S, P, F.img, cls, cam, d, P.ns, P.np, P.nl, P.bias, fix);
+    }
     const d3 acc = mk(0.0, 0.0, 0.0) + col3;  // the sample loop's one addition
     constexpr int samples = 1;
     const uint32_t lane_e = lane, x_e = x, yl_e = yl;
@@ -487,15 +528,17 @@ bool packet_split_wanted(const TraceParams& p) {
 
 // The fix-up variant's split launch (s.tiles: every frame's class words are followed by
 // its tile lists): packet_uniform_kernel over the uniform tiles and packet_direct_kernel's
-// kFeatSplit twin over the general workgroups, one after the other on the stream.  They touch
-// disjoint pixels and append to one fix-up list with atomics.  (The uniform launch forked onto
-// a second stream measured the same: profiles/tile_split_ab.txt.)
+// kFeatSplit twin over the general workgroups, one after the other on the stream, with
+// packet_uniform_kernel<true> over the shadowed-plane tiles between them where the tables list
+// those (s.sh_n).  They touch disjoint pixels and append to one fix-up list with atomics.  (The
+// uniform launch forked onto a second stream measured the same: profiles/tile_split_ab.txt.)
 static void launch_packet_split(const TraceParams& p, const PkSplit& s, size_t lds,
                                 hipStream_t stream) {
     // (one wave row per workgroup: packet_split_wanted)
     const dim3 block(64 * kWgWavesX);
     const dim3 ggrid(s.gen_n, 1u, p.nframes);
     const dim3 ugrid((s.uni_n + kUniThreads / 64 - 1) / (kUniThreads / 64), 1u, p.nframes);
+    const dim3 sgrid((s.sh_n + kUniThreads / 64 - 1) / (kUniThreads / 64), 1u, p.nframes);
     // (RT_PACKET_SPLIT_GENERAL_FIRST: the other order, for A/B builds)
 #ifdef RT_PACKET_SPLIT_GENERAL_FIRST
     if (s.gen_n)
@@ -503,7 +546,11 @@ static void launch_packet_split(const TraceParams& p, const PkSplit& s, size_t l
                            ggrid, block, lds, stream, p);
 #endif
     if (s.uni_n)
-        hipLaunchKernelGGL(packet_uniform_kernel, ugrid, dim3(kUniThreads), 0, stream, p,
+        hipLaunchKernelGGL(packet_uniform_kernel<false>, ugrid, dim3(kUniThreads), 0, stream, p,
+                           s.tiles);
+    // (a table without the third list has a count of 0 for it: no launch)
+    if (s.sh_n)
+        hipLaunchKernelGGL(packet_uniform_kernel<true>, sgrid, dim3(kUniThreads), 0, stream, p,
                            s.tiles);
 #ifndef RT_PACKET_SPLIT_GENERAL_FIRST
     if (s.gen_n)

@@ -233,6 +233,11 @@ rt_status packet_image_entry(rt_context* ctx, const rt_scene* sc, const double* 
 // table is formed, which sizes the split launch's grids; a batch with a ring frame (a camera
 // seen for the first time) forms no lists and stays one launch, as does the batch whose launch
 // forms a table.  RTAMD_PK_TILE_SPLIT=0 (read per launch): no lists.
+// The shadowed-plane tiles (tile_shadowed_mark) are marked in the class words and filed in a third
+// list by the same launch, in the same words (the list fills the uniform list's free end, its
+// count is one word more, and the pinned host words are two: three counts); the key word has one
+// more bit for them.  RTAMD_PK_TILE_SHADOWED=0 (read per launch): no mark and no third list, and a
+// cached table formed that way is one of its own.
 // RTAMD_PK_CONE_TAB=0 alone the cone words are still formed — the shadow words depend on them —
 // but only the shadow pointers reach the kernel.
 // The tile class words (tile_class_word, rt_shadow_table.hpp; TraceParams.class_tab / fr_ctab)
@@ -259,11 +264,13 @@ struct TabsWanted {
     bool cls;       // the tile class words too, one per tile after the shadow words
     bool clear;     // ... with their shadow-plane keep masks formed (else all ones)
     bool lists;     // ... and the tile lists after them (the fix-up variant's split launch)
+    bool shadowed;  // ... with the shadowed-plane tiles marked and in a third list
+    int list_kind() const { return lists ? (shadowed ? 2 : 1) : 0; }  // PkConeJobs.lists
     int cls_kind() const { return cls ? (clear ? 2 : 1) : 0; }  // PkConeJobs.class_words
     bool any() const { return cone || shadow; }
 };
 TabsWanted tables_wanted(const rt_scene* sc, const TraceParams& p) {
-    TabsWanted w{false, false, 0, false, false, false};
+    TabsWanted w{false, false, 0, false, false, false, false};
     if (!packet_reads_cone_table(p, sc->max_specular > 0.0)) return w;
     const char* e = std::getenv("RTAMD_PK_CONE_TAB");
     w.cone = !(e && std::atoi(e) == 0);
@@ -277,6 +284,8 @@ TabsWanted tables_wanted(const rt_scene* sc, const TraceParams& p) {
     // the tile lists serve frame batches that take the fix-up variant, and only those
     w.lists = w.cls && p.nframes >= 1 && packet_uses_fixup(p, false, sc->max_specular > 0.0) &&
               packet_split_wanted(p);
+    e = std::getenv("RTAMD_PK_TILE_SHADOWED");
+    w.shadowed = w.lists && !(e && std::atoi(e) == 0);
     return w;
 }
 
@@ -289,7 +298,7 @@ TabsWanted tables_wanted(const rt_scene* sc, const TraceParams& p) {
 // bias bit for bit: the words formed at one bias are wrong masks at a larger one.  Returns the
 // table's size.
 constexpr size_t kConeKeyWords = rt_scene::PkImage::ConeTab::kKeyWords;
-size_t cone_table_key(const TraceParams& p, double dz, int shadow_nl, int cls, bool lists,
+size_t cone_table_key(const TraceParams& p, double dz, int shadow_nl, int cls, int lists,
                       uint32_t (&key)[kConeKeyWords], size_t* tiles = nullptr) {
     uint32_t gx, gy, waves;
     packet_grid(p, gx, gy, waves);
@@ -306,8 +315,10 @@ size_t cone_table_key(const TraceParams& p, double dz, int shadow_nl, int cls, b
         key[15] = static_cast<uint32_t>(shadow_nl);
         std::memcpy(key + 16, &p.bias, sizeof p.bias);
         // the class words follow the shadow words (1), with their keep masks formed (3)
-        // ... and the tile lists follow the class words (4)
-        key[18] = (cls == 2 ? 3u : (cls ? 1u : 0u)) | (cls && lists ? 4u : 0u);
+        // ... and the tile lists follow the class words (4), the shadowed-plane tiles marked
+        // and listed (8)
+        key[18] = (cls == 2 ? 3u : (cls ? 1u : 0u)) | (cls && lists ? 4u : 0u) |
+                  (cls && lists == 2 ? 8u : 0u);
     }
     const size_t n = static_cast<size_t>(gx) * gy * waves;
     if (tiles) *tiles = n;
@@ -320,7 +331,7 @@ size_t cone_table_key(const TraceParams& p, double dz, int shadow_nl, int cls, b
 // after the launch that formed it), or a new entry whose table the caller forms (*fresh) and
 // whose event it records; null when the camera's table list is full.
 rt_status cone_table_entry(rt_context* ctx, rt_scene::PkImage& im, const TraceParams& p,
-                           double dz, int shadow_nl, int cls, bool lists,
+                           double dz, int shadow_nl, int cls, int lists,
                            rt_scene::PkImage::ConeTab** tab, bool* fresh) {
     *tab = nullptr;
     *fresh = false;
@@ -347,8 +358,10 @@ rt_status cone_table_entry(rt_context* ctx, rt_scene::PkImage& im, const TracePa
     hipError_t e = t.buf.ensure(bytes);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&t.ready, hipEventDisableTiming);
     if (e == hipSuccess && lists) {
-        e = hipHostMalloc(reinterpret_cast<void**>(&t.counts), sizeof(unsigned long long));
+        // (two words: {uniform, general} and the shadowed count, PkListCounts)
+        e = hipHostMalloc(reinterpret_cast<void**>(&t.counts), 2 * sizeof(unsigned long long));
         if (e == hipSuccess) __atomic_store_n(t.counts, 0ull, __ATOMIC_RELAXED);
+        if (e == hipSuccess) __atomic_store_n(t.counts + 1, 0ull, __ATOMIC_RELAXED);
     }
     if (e != hipSuccess) {
         t.buf.release();
@@ -377,7 +390,7 @@ rt_status cone_table_single(rt_context* ctx, const rt_scene* sc, rt_scene::PkIma
     rt_scene::PkImage::ConeTab* t = nullptr;
     bool fresh = false;
     const rt_status st = cone_table_entry(ctx, im, p, p.cam_dz, want.shadow_nl, want.cls_kind(),
-                                          false, &t, &fresh);
+                                          0, &t, &fresh);
     if (st != RT_OK || !t) return st;
     if (fresh) {
         PkConeJobs jobs;
@@ -396,7 +409,7 @@ rt_status cone_table_single(rt_context* ctx, const rt_scene* sc, rt_scene::PkIma
     }
     uint32_t key[kConeKeyWords];
     size_t tiles = 0;
-    (void)cone_table_key(p, p.cam_dz, want.shadow_nl, want.cls_kind(), false, key, &tiles);
+    (void)cone_table_key(p, p.cam_dz, want.shadow_nl, want.cls_kind(), 0, key, &tiles);
     const unsigned long long* words = static_cast<const unsigned long long*>(t->buf.ptr);
     if (want.cone) p.cone_tab = words;
     if (want.shadow) p.shadow_tab = words + tiles;
@@ -453,7 +466,7 @@ rt_status packet_batch_images(rt_context* ctx, const rt_scene* sc, const rt_came
                               PkSplit* split) {
     *rec = nullptr;
     *batch_ring = -1;
-    *split = PkSplit{0u, 0u, 0u};
+    *split = PkSplit{0u, 0u, 0u, 0u};
     enum Kind { kCached, kPromote, kRing, kDup };
     Kind kind[kPkMaxBatch];
     int dup_of[kPkMaxBatch];
@@ -555,14 +568,14 @@ rt_status packet_batch_images(rt_context* ctx, const rt_scene* sc, const rt_came
     // host cannot know its counts before the launch, both grids would have to cover every tile,
     // and the surplus workgroups cost more than the split saves (moving_camera −10 %,
     // profiles/tile_split_ab.txt)
-    if (any_ring) want.lists = false;
+    if (any_ring) want.lists = want.shadowed = false;
     // The frames' cone tables, after their images on the stream: a cached or promoted camera's
     // from (or into) its entry, a ring frame's into the ring entry's table buffer up to its
     // cap, a duplicate's shared; every table that does not exist yet by ONE launch.
     uint32_t key[kConeKeyWords];
     size_t tiles = 0;
     const size_t tab_bytes =  // (the sizes only)
-        (cone_table_key(p, 0.0, want.shadow_nl, want.cls_kind(), want.lists, key, &tiles) + 255) &
+        (cone_table_key(p, 0.0, want.shadow_nl, want.cls_kind(), want.list_kind(), key, &tiles) + 255) &
         ~size_t(255);
     // (the cap counts the cone words and the class words; the shadow words come on top)
     const size_t cone_bytes =
@@ -588,7 +601,7 @@ rt_status packet_batch_images(rt_context* ctx, const rt_scene* sc, const rt_came
     std::memset(&cj, 0, sizeof cj);
     cj.shadow_nl = want.shadow_nl;
     cj.class_words = want.cls_kind();
-    cj.lists = want.lists ? 1 : 0;
+    cj.lists = want.list_kind();
     PkListCounts lc;
     std::memset(&lc, 0, sizeof lc);
     // a frame's list counts where the host has them (a cache entry's table formed earlier):
@@ -596,14 +609,17 @@ rt_status packet_batch_images(rt_context* ctx, const rt_scene* sc, const rt_came
     // its batch stays one launch
     uint32_t gx, gy, waves;
     packet_grid(p, gx, gy, waves);
-    uint32_t n_uni = 0, n_gen = 0;
+    uint32_t n_uni = 0, n_gen = 0, n_sh = 0;
     bool all_lists = want.lists;
     auto count_frame = [&](const unsigned long long* host) {
         const unsigned long long v = host ? __atomic_load_n(host, __ATOMIC_RELAXED) : 0ull;
+        const unsigned long long v2 = host ? __atomic_load_n(host + 1, __ATOMIC_RELAXED) : 0ull;
         const uint32_t u = static_cast<uint32_t>(v), g = static_cast<uint32_t>(v >> 32);
-        if (!u || !g) all_lists = false;
+        const uint32_t s = static_cast<uint32_t>(v2);
+        if (!u || !g || !s) all_lists = false;
         n_uni = std::max(n_uni, u ? u - 1u : static_cast<uint32_t>(tiles));
         n_gen = std::max(n_gen, g ? g - 1u : gx * gy);
+        n_sh = std::max(n_sh, s ? s - 1u : static_cast<uint32_t>(tiles));
     };
     p.plane_masks = want.clear ? 1u : 0u;
     // the kernel's pointers of a frame whose table is (or will be) at `words`
@@ -638,7 +654,7 @@ rt_status packet_batch_images(rt_context* ctx, const rt_scene* sc, const rt_came
             rt_scene::PkImage::ConeTab* t = nullptr;
             bool fresh = false;
             st = cone_table_entry(ctx, *ent[f], p, p.fr_dz[f][0], want.shadow_nl,
-                                  want.cls_kind(), want.lists, &t, &fresh);
+                                  want.cls_kind(), want.list_kind(), &t, &fresh);
             if (st != RT_OK || !t) all_lists = false;
             if (st != RT_OK || !t) continue;
             hand(f, static_cast<const unsigned long long*>(t->buf.ptr));
@@ -665,7 +681,7 @@ rt_status packet_batch_images(rt_context* ctx, const rt_scene* sc, const rt_came
     if (st != RT_OK)  // a table never formed must not be found by a later render
         for (int i = n_made - 1; i >= 0; --i) cone_table_drop(*made[i]);
     if (st == RT_OK && all_lists) {  // every frame has its lists: the split launch
-        *split = PkSplit{static_cast<uint32_t>(tiles), n_uni, n_gen};
+        *split = PkSplit{static_cast<uint32_t>(tiles), n_uni, n_gen, want.shadowed ? n_sh : 0u};
     }
     return st;
 }

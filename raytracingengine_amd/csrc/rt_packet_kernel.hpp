@@ -356,11 +356,22 @@ __device__ __forceinline__ void pk_light_record(const PacketScene& S, const Trac
 // it out changes neither `blocked` nor `undecided`).  A light whose mask is 0 — most of C2's:
 // the kept plane lies behind its own shadow origins, the other one beyond the light — runs no
 // classification and loads no `oth` record; all ones classifies every plane as before.
-template <int MAXC, int FEAT>
+// SPH (packet_uniform_kernel<true>: a shadowed-plane tile, tile_shadowed_mark): the camera ray's
+// claims are the same, but a shadow ray can meet a sphere.  `stab` points at the tile's shadow
+// words, one per light (one scalar load each); a non-zero word first runs the sphere block of
+// pk_occlusion_t<1, FEAT, true> over the word's bits — what pk_light runs on the general path with
+// that word as its mask: the range test on 2a, rcp_refined and the per-sphere discriminant, roots
+// and thresholds, the same expressions in the same order — with the sphere records read from the
+// global image through the scalar cache (the loop is wave-uniform; the LDS image holds these
+// values).  A 2a out of range returns "undecided" there before any plane is classified: here it
+// sets `undecided` and skips both blocks, which leaves T = 1 and queues the pixel, as there.
+// A zero word for a light is pk_occlusion_t<1, FEAT, false>: the code of the other form.
+template <int MAXC, int FEAT, bool SPH = false>
 __device__ __forceinline__ d3 pk_uniform_tile(const PacketScene& S, const TraceParams& P,
                                               const double* img, unsigned long long cls, d3 cam,
                                               d3 d, int ns, int np, int nl, double bias,
-                                              bool& fix) {
+                                              bool& fix,
+                                              const unsigned long long* stab = nullptr) {
     if (tile_class_of(cls) == kTileSky) return sky(d);
     const int k = static_cast<int>(tile_class_of(cls) - kTilePlane0);
     const pk_cdp pl = (pk_cdp)img + kPkSph * ns;
@@ -400,7 +411,56 @@ __device__ __forceinline__ d3 pk_uniform_tile(const PacketScene& S, const TraceP
         // for this light keeps (uniform: scalar branches)
         bool blocked = false, undecided = false;
         const unsigned keep = tile_plane_keep(cls, l);
-        if (keep != 0 && need) {
+        bool planes = true;  // (SPH: false for a lane whose 2a is out of range)
+        if constexpr (SPH) {
+            // pk_occlusion_t<1, FEAT, true>'s sphere block over this light's word (uniform)
+            const unsigned long long w = *(pk_culp)(stab + l);
+            if (w != 0 && need) {
+                const double max_dist = dist - bias;
+                const double a = dot(L, L);
+                const double two_a = 2.0 * a, four_a = 4.0 * a;
+                if (!(two_a >= 0x1p-100 && two_a <= 0x1p100)) {
+                    undecided = true;
+                    planes = false;
+                } else {
+                    const double inv2a = rcp_refined(two_a);
+                    uint64_t m = w;
+                    while (m) {
+                        const int i = __builtin_ctzll(m);
+                        m &= m - 1;
+                        const pk_cdp s = (pk_cdp)img + kPkSph * i;
+                        const d3 oc = so - mk(s[0], s[1], s[2]);
+                        const double b = 2.0 * dot(oc, L);
+                        const double cc = dot(oc, oc) - s[3];
+                        const double disc = b * b - four_a * cc;
+                        if (disc < 0.0) continue;
+                        if (!(disc == 0.0 || (disc > 1e-30 && disc < 1e30))) {
+                            undecided = true;
+                            continue;
+                        }
+                        const double sq = static_cast<double>(sqrt_f32(static_cast<float>(disc)));
+                        const double delta = 2e-6 * (fabs(b) + sq) * inv2a;
+                        double ts = (-b - sq) * inv2a;
+                        if (!(ts >= 1e-6 + delta)) {
+                            if (!(ts < 1e-6 - delta)) {
+                                undecided = true;
+                                continue;
+                            }
+                            ts = (-b + sq) * inv2a;
+                            if (ts < 1e-6 - delta) continue;
+                            if (!(ts >= 1e-6 + delta)) {
+                                undecided = true;
+                                continue;
+                            }
+                        }
+                        if (ts >= max_dist + delta) continue;
+                        if (ts > bias + delta && ts < max_dist - delta) blocked = true;
+                        else undecided = true;
+                    }
+                }
+            }
+        }
+        if (keep != 0 && need && planes) {
             const double max_dist = dist - bias;
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
@@ -576,7 +636,9 @@ __global__ __launch_bounds__(64 * kWgWavesX * WGY, pk_waves(MAXC, FEAT_, COUNT, 
         for (int i = tid; i < nv; i += kThreads) dst[i] = src[i];
         __syncthreads();
         if constexpr (SPLIT)
-            if (tile_class_of(cls) != kTileGeneral) return;  // packet_uniform_kernel's tile
+            // packet_uniform_kernel's tile: uniform, or marked shadowed-plane (a table formed
+            // without the third list carries no mark)
+            if (tile_class_of(cls) != kTileGeneral || (cls & kTileShadowedBit) != 0) return;
     } else if (pk_img) {
         // (a workgroup of uniform tiles: no image in LDS)
     } else if (pk_pub) {

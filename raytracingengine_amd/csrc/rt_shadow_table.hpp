@@ -339,6 +339,40 @@ RT_CT_HD inline unsigned long long tile_class_word(unsigned long long cone,
     return kTilePlane0 + static_cast<unsigned long long>((i + kIndexOff) % np);
 }
 
+// The shadowed-plane mark (packet_uniform_kernel<true>, rt_packet.hip).  A tile is *shadowed-plane
+// i* when it meets every condition of class "plane i" but "every light's shadow word is 0": its
+// cone mask is empty, the bound is ok and kept exactly plane i, which leads and has its oriented
+// unit normal in the image, 1 ≤ nl ≤ kShadowTabLights, every light has a word and some word is not
+// 0.  The geometric claims and their proof are tile_class_word's (every camera ray of the tile
+// ends on plane i with the bits of num_i / (n_i·d)); each word is a superset of the spheres a
+// shadow ray of the tile towards its light can meet (shadow_tile_word).  The tile's class byte
+// stays kTileGeneral — the single launch renders it on its general path and counts it general —
+// and the mark rides in bits the class byte and the keep masks leave free: bit 40, with the
+// plane's index in bits 41-43.  Only the table word carries it: a list entry has the tile's
+// column there (tile_shadowed_entry writes the plane's class into the class byte instead).
+// kNoWordOk and kIndexOff exist for the host test's mutants only (the mark taken on a tile with a
+// cone mask or a light without a word; the plane's index off by one).
+constexpr unsigned long long kTileShadowedBit = 1ull << 40;
+constexpr int kTileShadowedPlaneShift = 41;
+template <int kMaxPlanes, bool kNoWordOk = false, int kIndexOff = 0>
+RT_CT_HD inline unsigned long long tile_shadowed_mark(unsigned long long cone,
+                                                      const ShadowBound<kMaxPlanes>& B,
+                                                      const unsigned long long* words, int nl,
+                                                      const double* pln, int np) {
+    if ((cone != 0 && !kNoWordOk) || !B.ok || B.n != 1 || nl < 1 || nl > kShadowTabLights)
+        return 0ull;
+    bool some = false;
+    for (int l = 0; l < nl; ++l) {
+        if (words[l] == kShadowNoWord && !kNoWordOk) return 0ull;
+        some = some || words[l] != 0;
+    }
+    if (!some || !B.ball[0].lead) return 0ull;
+    const int i = B.ball[0].plane;
+    if (i < 0 || i >= np || i >= 8 || !(pln[4 * i + 3] != 0.0)) return 0ull;
+    return kTileShadowedBit |
+           (static_cast<unsigned long long>((i + kIndexOff) % np) << kTileShadowedPlaneShift);
+}
+
 // The planes a tile's shadow rays towards the light at L must still classify: bit i stands for
 // plane i of `planes`, kPlaneKeepAll says nothing is proven.  The class word carries one such
 // mask per light next to the class (tile_class_pack), and pk_uniform_tile (rt_packet_kernel.hpp)
@@ -448,6 +482,7 @@ RT_CT_HD inline unsigned tile_plane_keep(unsigned long long word, int l) {
 //   1 word    the counts: uniform tiles in the low half, general workgroups in the high half
 //   T words   the uniform tiles, one entry each (room for every tile)
 //   W/2 words the general workgroups, one 32-bit workgroup index tby · gx + tbx each
+//   1 word    the count of shadowed tiles (the third list, below)
 // for T tiles in W workgroups of `waves` tiles.  A tile is *uniform* when its class is not
 // kTileGeneral; a workgroup is *general*, and listed, when at least one of its tiles is not
 // uniform.  Every tile is therefore rendered exactly once: by the uniform kernel when it is
@@ -466,8 +501,21 @@ constexpr int kListColShift = 40, kListRowShift = 52;
 constexpr unsigned long long kListWordMask = (1ull << kListColShift) - 1ull;
 constexpr uint32_t kListCoordMask = 0xfffu;
 constexpr uint32_t kListMaxCoord = kListCoordMask + 1u;  // tile columns and rows a list can name
+// The third list: the shadowed-plane tiles (tile_shadowed_mark) of a table formed with them.  Its
+// entries have the uniform list's format and fill the T words of the uniform list from their end
+// downwards — entry j at word T − j of the lists (a tile is in one list at most, so the two never
+// meet) — and its count is one more word after the general workgroups.  A workgroup is then
+// listed only when it has a tile that is neither uniform nor shadowed.  The first two lists and
+// their count word are where they were.
 RT_CT_HD inline size_t tile_list_words(size_t tiles, size_t wgs) {
+    return 2 + tiles + (wgs + 1) / 2;
+}
+// the shadowed count's word, and the uniform array's slot of shadowed entry j
+RT_CT_HD inline size_t tile_list_shadowed_count(size_t tiles, size_t wgs) {
     return 1 + tiles + (wgs + 1) / 2;
+}
+RT_CT_HD inline uint32_t tile_list_shadowed_slot(uint32_t j, uint32_t tiles) {
+    return tiles - 1u - j;
 }
 RT_CT_HD inline uint32_t tile_list_tile(uint32_t pos, uint32_t tiles) { return tiles - 1u - pos; }
 RT_CT_HD inline bool tile_list_uniform(unsigned long long word) {
@@ -506,6 +554,44 @@ inline void tile_list_run(const unsigned long long* words, uint32_t tiles, uint3
             uni[(*n_uni)++] = tile_list_entry<kIndexOff>(words[t], x0, yl0);
         }
         if ((l & (waves - 1u)) == 0 && tile_list_wg_listed<kDropMixed>(general, l, waves))
+            gen[(*n_gen)++] = t / waves;
+    }
+}
+
+// A shadowed tile of a table word (a general class byte with the mark), and its list entry: the
+// uniform entry the tile would have with class "plane i" — the keep masks as formed, the class
+// byte written from the mark's plane index, column and row above them.
+RT_CT_HD inline bool tile_list_shadowed(unsigned long long word) {
+    return tile_class_of(word) == kTileGeneral && (word & kTileShadowedBit) != 0;
+}
+RT_CT_HD inline unsigned long long tile_shadowed_entry(unsigned long long word, uint32_t x0,
+                                                       uint32_t yl0) {
+    const unsigned long long cls = kTilePlane0 + ((word >> kTileShadowedPlaneShift) & 7ull);
+    return tile_list_entry((word & ~kTileClassBits) | cls, x0, yl0);
+}
+// tile_list_run with the third list: the run's shadowed entries go to uni[tiles − 1 − *n_sh …]
+// downwards, and a workgroup is listed when one of its tiles is neither uniform nor shadowed.
+// kDropShadowedMixed exists for the host test's mutant only (a workgroup with a shadowed wave and
+// a general wave is not listed).
+template <bool kDropShadowedMixed = false, class Origin>
+inline void tile_list_run3(const unsigned long long* words, uint32_t tiles, uint32_t waves,
+                           uint32_t pos0, Origin origin, unsigned long long* uni, uint32_t* n_uni,
+                           uint32_t* n_sh, uint32_t* gen, uint32_t* n_gen) {
+    uint64_t general = 0, shadowed = 0;
+    for (uint32_t l = 0; l < 64 && pos0 + l < tiles; ++l) {
+        const unsigned long long w = words[tile_list_tile(pos0 + l, tiles)];
+        if (tile_list_shadowed(w)) shadowed |= 1ull << l;
+        else if (!tile_list_uniform(w)) general |= 1ull << l;
+    }
+    for (uint32_t l = 0; l < 64 && pos0 + l < tiles; ++l) {
+        const uint32_t t = tile_list_tile(pos0 + l, tiles);
+        uint32_t x0, yl0;
+        origin(t, x0, yl0);
+        if (tile_list_uniform(words[t])) uni[(*n_uni)++] = tile_list_entry(words[t], x0, yl0);
+        else if (tile_list_shadowed(words[t]))
+            uni[tile_list_shadowed_slot((*n_sh)++, tiles)] = tile_shadowed_entry(words[t], x0, yl0);
+        if ((l & (waves - 1u)) == 0 && tile_list_wg_listed(general, l, waves) &&
+            !(kDropShadowedMixed && tile_list_wg_listed(shadowed, l, waves)))
             gen[(*n_gen)++] = t / waves;
     }
 }
