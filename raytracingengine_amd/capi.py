@@ -6,6 +6,7 @@ There is no CPU fallback — if the library or a gfx950 device is missing, the c
 from __future__ import annotations
 
 import ctypes
+import math
 import os
 
 import numpy as np
@@ -181,24 +182,109 @@ class ScatterPtrs(ctypes.Structure):
     _fields_ = [(name, ctypes.c_void_p) for name, *_ in SC_OUTPUTS]
 
 
-def _sc_check(outputs: int):
-    if outputs == 0 or outputs & ~SC_ALL:
-        raise ValueError("outputs: a non-empty combination of SC_* bits")
-
-
 class ClosestPtrs(ctypes.Structure):
     """struct rt_closest_out: one pointer per output, in RT_CH_* bit order."""
     _fields_ = [(name, ctypes.c_void_p) for name, *_ in CH_OUTPUTS]
 
 
-def _ch_check(outputs: int):
-    if outputs == 0 or outputs & ~CH_ALL:
-        raise ValueError("outputs: a non-empty combination of CH_* bits")
+# The records of selectable outputs by the prefix of their bits: the rows (name, bit, element
+# type, elements per item), the ctypes record and all the bits.  DL_OUTPUTS keeps its two columns
+# for its users; every direct-light output is float64 [n, 3].
+_RECORDS = {kind: (rows, record, sum(r[1] for r in rows)) for kind, rows, record in (
+    ("DL", [(name, bit, np.float64, 3) for name, bit in DL_OUTPUTS], DirectLightPtrs),
+    ("SC", SC_OUTPUTS, ScatterPtrs), ("CH", CH_OUTPUTS, ClosestPtrs))}
+
+
+_TORCH_DTYPES = {}   # numpy element type -> torch dtype, filled as _outputs meets them
+
+
+def _mask_check(kind: str, outputs: int):
+    if outputs == 0 or outputs & ~_RECORDS[kind][2]:
+        raise ValueError(f"outputs: a non-empty combination of {kind}_* bits")
 
 
 def _dl_check(outputs: int):
-    if outputs == 0 or outputs & ~DL_ALL:
-        raise ValueError("outputs: a non-empty combination of DL_* bits")
+    _mask_check("DL", outputs)
+
+
+def _sc_check(outputs: int):
+    _mask_check("SC", outputs)
+
+
+def _ch_check(outputs: int):
+    _mask_check("CH", outputs)
+
+
+def _host_rows(a, k: int):
+    """`a` as a contiguous float64 [n, k] array, and n."""
+    a = np.ascontiguousarray(a, np.float64).reshape(-1, k)
+    return a, a.shape[0]
+
+
+def _checked_input(t, dev, dtype, k: int, name: str) -> int:
+    """n of the input tensor `t` of n*k elements: contiguous, of `dtype`, on `dev`."""
+    if t.dtype != dtype or t.device != dev or not t.is_contiguous():
+        raise ValueError(f"{name}: a contiguous {str(dtype).split('.')[-1]} tensor on the "
+                         "context's device")
+    n = t.numel() // k
+    if t.numel() != k * n:
+        raise ValueError(f"{name}: n*{k} elements")
+    return n
+
+
+def _out_tensor(t, dev, dtype, shape, name: str = "out", need: str = "n"):
+    """The output tensor `t` as it is, or for None a new one of `shape`: contiguous, of `dtype`,
+    on `dev`, of at least prod(shape) elements (`need` in the message)."""
+    if t is None:
+        import torch
+        return torch.empty(shape, dtype=dtype, device=dev)
+    if (t.dtype != dtype or t.device != dev or t.numel() < math.prod(shape)
+            or not t.is_contiguous()):
+        raise ValueError(f"{name}: a contiguous {str(dtype).split('.')[-1]} tensor of at least "
+                         f"{need} elements on the device")
+    return t
+
+
+def _outputs(kind: str, outputs: int, n: int, dev=None, out=None):
+    """({name: array} of the outputs the `kind`_* bits of `outputs` request for n items, in bit
+    order; the ctypes record of their pointers).  dev None: new numpy arrays; else torch tensors
+    on `dev`, those `out` holds by name (checked as _out_tensor checks one) or new ones.  A
+    requested output's pointer is never NULL, an empty array's included."""
+    _mask_check(kind, outputs)
+    rows, record, _ = _RECORDS[kind]
+    if dev is None:
+        res = {name: np.empty((n, k) if k else (n,), dt)
+               for name, bit, dt, k in rows if outputs & bit}
+        return res, record(**{k: (v.ctypes.data or 8) for k, v in res.items()})
+    import torch
+    res, ptr = {}, {}
+    for name, bit, dt, k in rows:
+        if not outputs & bit:
+            continue
+        tdt = _TORCH_DTYPES.get(dt) or _TORCH_DTYPES.setdefault(dt, getattr(torch, dt.__name__))
+        t = None if out is None else out.get(name)
+        if t is None:
+            t = torch.empty((n, k) if k else (n,), dtype=tdt, device=dev)
+        elif (t.dtype != tdt or t.device != dev or t.numel() < max(k, 1) * n
+              or not t.is_contiguous()):
+            raise ValueError(f"out[{name!r}]: a contiguous {dt.__name__} tensor of at least "
+                             f"n*{max(k, 1)} elements on the device")
+        res[name] = t
+        ptr[name] = t.data_ptr() or 8
+    return res, record(**ptr)
+
+
+def _max_dist_tensor(max_dist, n: int, dev):
+    """max_dist of the ray queries as a float64 [n] tensor on `dev`: a scalar is expanded there."""
+    import torch
+    if not torch.is_tensor(max_dist):
+        max_dist = torch.full((n,), float(max_dist), dtype=torch.float64, device=dev)
+        # filled on torch's current stream, read on the context's
+        torch.cuda.current_stream(dev).synchronize()
+    if (max_dist.dtype != torch.float64 or max_dist.device != dev or max_dist.numel() != n
+            or not max_dist.is_contiguous()):
+        raise ValueError("max_dist: a scalar or a contiguous float64 [n] tensor on the device")
+    return max_dist
 
 
 class GatherTiming(ctypes.Structure):
@@ -354,6 +440,17 @@ def default_opts(**kw) -> RenderOpts:
     load_library().rt_render_opts_default(ctypes.byref(o))
     for k, v in kw.items():
         setattr(o, k, v)
+    return o
+
+
+def _query_opts(bias=None, no_bvh: bool = False, max_recursion=None) -> RenderOpts:
+    """The options of a batch query: the defaults, RT_FLAG_NO_BVH alone in the flags, and the
+    bias and max_recursion where the query takes them."""
+    o = default_opts(flags=RT_FLAG_NO_BVH if no_bvh else 0)
+    if bias is not None:
+        o.bias = bias
+    if max_recursion is not None:
+        o.max_recursion = max_recursion
     return o
 
 
@@ -580,14 +677,18 @@ class DeviceScene:
                                       out.ctypes.data))
         return out
 
+    def _device(self):
+        """The torch device of the context: where the tensors of the *_device methods live."""
+        import torch
+        return torch.device(f"cuda:{self.ctx.device}")
+
     def occluded(self, rays: np.ndarray, max_dist, no_bvh: bool = False) -> np.ndarray:
         """Batch IntersectAnyBefore (rt_occluded_rays): rays [n,6] and max_dist (a scalar, or
         one distance per ray) -> bool [n], True where a primitive lies at 0 < t < max_dist."""
-        rays = np.ascontiguousarray(rays, np.float64).reshape(-1, 6)
-        n = rays.shape[0]
+        rays, n = _host_rows(rays, 6)
         dist = np.ascontiguousarray(np.broadcast_to(np.asarray(max_dist, np.float64), (n,)))
         out = np.empty(n, np.uint8)
-        o = default_opts(flags=RT_FLAG_NO_BVH if no_bvh else 0)
+        o = _query_opts(no_bvh=no_bvh)
         _check(_lib.rt_occluded_rays(self.ctx.handle, self._h, ctypes.byref(o), rays.ctypes.data,
                                      dist.ctypes.data, n, out.ctypes.data))
         return out.view(np.bool_)
@@ -598,25 +699,11 @@ class DeviceScene:
         on the device), contiguous, on this context's device.  Returns `out`, a uint8 [n] tensor
         of 0 / 1 (made when None); it is written when the context's stream reaches the launch."""
         import torch
-        dev = torch.device(f"cuda:{self.ctx.device}")
-        if rays.dtype != torch.float64 or rays.device != dev or not rays.is_contiguous():
-            raise ValueError("rays: a contiguous float64 tensor on the context's device")
-        n = rays.numel() // 6
-        if rays.numel() != 6 * n:
-            raise ValueError("rays: n*6 elements")
-        if not torch.is_tensor(max_dist):
-            max_dist = torch.full((n,), float(max_dist), dtype=torch.float64, device=dev)
-            # filled on torch's current stream, read on the context's
-            torch.cuda.current_stream(dev).synchronize()
-        if (max_dist.dtype != torch.float64 or max_dist.device != dev or max_dist.numel() != n
-                or not max_dist.is_contiguous()):
-            raise ValueError("max_dist: a scalar or a contiguous float64 [n] tensor on the device")
-        if out is None:
-            out = torch.empty(n, dtype=torch.uint8, device=dev)
-        elif (out.dtype != torch.uint8 or out.device != dev or out.numel() < n
-              or not out.is_contiguous()):
-            raise ValueError("out: a contiguous uint8 tensor of at least n elements on the device")
-        o = default_opts(flags=RT_FLAG_NO_BVH if no_bvh else 0)
+        dev = self._device()
+        n = _checked_input(rays, dev, torch.float64, 6, "rays")
+        max_dist = _max_dist_tensor(max_dist, n, dev)
+        out = _out_tensor(out, dev, torch.uint8, (n,))
+        o = _query_opts(no_bvh=no_bvh)
         _check(_lib.rt_occluded_rays_device(self.ctx.handle, self._h, ctypes.byref(o),
                                             rays.data_ptr() if n else None,
                                             max_dist.data_ptr() if n else None, n,
@@ -627,11 +714,10 @@ class DeviceScene:
                       no_bvh: bool = False) -> np.ndarray:
         """Batch computeTransmittance (rt_transmittance_rays): rays [n,6] and max_dist (a scalar,
         or one distance per ray) -> float64 [n], the transmittance in [0,1] up to max_dist."""
-        rays = np.ascontiguousarray(rays, np.float64).reshape(-1, 6)
-        n = rays.shape[0]
+        rays, n = _host_rows(rays, 6)
         dist = np.ascontiguousarray(np.broadcast_to(np.asarray(max_dist, np.float64), (n,)))
         out = np.empty(n, np.float64)
-        o = default_opts(bias=bias, flags=RT_FLAG_NO_BVH if no_bvh else 0)
+        o = _query_opts(bias, no_bvh)
         _check(_lib.rt_transmittance_rays(self.ctx.handle, self._h, ctypes.byref(o),
                                           rays.ctypes.data, dist.ctypes.data, n, out.ctypes.data))
         return out
@@ -644,25 +730,11 @@ class DeviceScene:
         Returns `out`, a float64 [n] tensor (made when None); it is written when the context's
         stream reaches the launch."""
         import torch
-        dev = torch.device(f"cuda:{self.ctx.device}")
-        if rays.dtype != torch.float64 or rays.device != dev or not rays.is_contiguous():
-            raise ValueError("rays: a contiguous float64 tensor on the context's device")
-        n = rays.numel() // 6
-        if rays.numel() != 6 * n:
-            raise ValueError("rays: n*6 elements")
-        if not torch.is_tensor(max_dist):
-            max_dist = torch.full((n,), float(max_dist), dtype=torch.float64, device=dev)
-            # filled on torch's current stream, read on the context's
-            torch.cuda.current_stream(dev).synchronize()
-        if (max_dist.dtype != torch.float64 or max_dist.device != dev or max_dist.numel() != n
-                or not max_dist.is_contiguous()):
-            raise ValueError("max_dist: a scalar or a contiguous float64 [n] tensor on the device")
-        if out is None:
-            out = torch.empty(n, dtype=torch.float64, device=dev)
-        elif (out.dtype != torch.float64 or out.device != dev or out.numel() < n
-              or not out.is_contiguous()):
-            raise ValueError("out: a contiguous float64 tensor of at least n elements on the device")
-        o = default_opts(bias=bias, flags=RT_FLAG_NO_BVH if no_bvh else 0)
+        dev = self._device()
+        n = _checked_input(rays, dev, torch.float64, 6, "rays")
+        max_dist = _max_dist_tensor(max_dist, n, dev)
+        out = _out_tensor(out, dev, torch.float64, (n,))
+        o = _query_opts(bias, no_bvh)
         _check(_lib.rt_transmittance_rays_device(self.ctx.handle, self._h, ctypes.byref(o),
                                                  rays.data_ptr() if n else None,
                                                  max_dist.data_ptr() if n else None, n,
@@ -674,10 +746,9 @@ class DeviceScene:
         """directLightning's shadow rays (rt_light_transmittance): points [n,6] {p, normal}, the
         normal facing the viewer -> float64 [n, n_lights], the transmittance from each point to
         each point light (0.0 where the reference skips the light)."""
-        points = np.ascontiguousarray(points, np.float64).reshape(-1, 6)
-        n, nl = points.shape[0], len(self._arrays[3])
-        out = np.empty((n, nl), np.float64)
-        o = default_opts(bias=bias, flags=RT_FLAG_NO_BVH if no_bvh else 0)
+        points, n = _host_rows(points, 6)
+        out = np.empty((n, len(self._arrays[3])), np.float64)
+        o = _query_opts(bias, no_bvh)
         _check(_lib.rt_light_transmittance(self.ctx.handle, self._h, ctypes.byref(o),
                                            points.ctypes.data if n else None, n,
                                            out.ctypes.data if out.size else None))
@@ -689,50 +760,15 @@ class DeviceScene:
         contiguous float64 [n,6] tensor on this context's device.  Returns `out`, a float64
         [n, n_lights] tensor (made when None; a given one needs at least n*n_lights elements)."""
         import torch
-        dev = torch.device(f"cuda:{self.ctx.device}")
-        if points.dtype != torch.float64 or points.device != dev or not points.is_contiguous():
-            raise ValueError("points: a contiguous float64 tensor on the context's device")
-        n = points.numel() // 6
-        if points.numel() != 6 * n:
-            raise ValueError("points: n*6 elements")
+        dev = self._device()
+        n = _checked_input(points, dev, torch.float64, 6, "points")
         nl = len(self._arrays[3])
-        if out is None:
-            out = torch.empty((n, nl), dtype=torch.float64, device=dev)
-        elif (out.dtype != torch.float64 or out.device != dev or out.numel() < n * nl
-              or not out.is_contiguous()):
-            raise ValueError("out: a contiguous float64 tensor of at least n*n_lights elements "
-                             "on the device")
-        o = default_opts(bias=bias, flags=RT_FLAG_NO_BVH if no_bvh else 0)
+        out = _out_tensor(out, dev, torch.float64, (n, nl), need="n*n_lights")
+        o = _query_opts(bias, no_bvh)
         _check(_lib.rt_light_transmittance_device(self.ctx.handle, self._h, ctypes.byref(o),
                                                   points.data_ptr() if n else None, n,
                                                   out.data_ptr() if n * nl else None))
         return out
-
-    def _dl_host(self, n: int, outputs: int):
-        _dl_check(outputs)
-        res = {name: np.empty((n, 3), np.float64) for name, bit in DL_OUTPUTS if outputs & bit}
-        ptrs = DirectLightPtrs(**{k: v.ctypes.data for k, v in res.items()})
-        return res, ptrs
-
-    def _dl_device(self, n: int, outputs: int, out):
-        import torch
-        _dl_check(outputs)
-        dev = torch.device(f"cuda:{self.ctx.device}")
-        res = {}
-        for name, bit in DL_OUTPUTS:
-            if not outputs & bit:
-                continue
-            t = None if out is None else out.get(name)
-            if t is None:
-                t = torch.empty((n, 3), dtype=torch.float64, device=dev)
-            elif (t.dtype != torch.float64 or t.device != dev or t.numel() < 3 * n
-                  or not t.is_contiguous()):
-                raise ValueError(f"out[{name!r}]: a contiguous float64 tensor of at least n*3 "
-                                 "elements on the device")
-            res[name] = t
-        # never a NULL pointer for a requested output, an empty tensor's included
-        ptrs = DirectLightPtrs(**{k: (v.data_ptr() or 8) for k, v in res.items()})
-        return res, ptrs
 
     def direct_light(self, points: np.ndarray, materials, outputs: int = DL_RADIANCE,
                      bias: float = 1e-3, no_bvh: bool = False) -> dict:
@@ -740,11 +776,10 @@ class DeviceScene:
         view}; materials a scene.Material or seven values (shared by all points) or an [n,7]
         array -> {"radiance" | "diffuse" | "specular": float64 [n,3]} for the DL_* bits of
         `outputs`."""
-        points = np.ascontiguousarray(points, np.float64).reshape(-1, 9)
-        n = points.shape[0]
+        points, n = _host_rows(points, 9)
         m = material_rows(materials, n)
-        res, ptrs = self._dl_host(n, outputs)
-        o = default_opts(bias=bias, flags=RT_FLAG_NO_BVH if no_bvh else 0)
+        res, ptrs = _outputs("DL", outputs, n)
+        o = _query_opts(bias, no_bvh)
         _check(_lib.rt_direct_light(self.ctx.handle, self._h, ctypes.byref(o),
                                     points.ctypes.data if n else None, m.ctypes.data, m.shape[0],
                                     n, outputs, ctypes.byref(ptrs)))
@@ -754,10 +789,9 @@ class DeviceScene:
                           no_bvh: bool = False) -> dict:
         """directLightning at the first hit of every ray (rt_direct_light_rays), with the hit
         primitive's material: rays [n,6] -> the dict of direct_light; zeros where a ray misses."""
-        rays = np.ascontiguousarray(rays, np.float64).reshape(-1, 6)
-        n = rays.shape[0]
-        res, ptrs = self._dl_host(n, outputs)
-        o = default_opts(bias=bias, flags=RT_FLAG_NO_BVH if no_bvh else 0)
+        rays, n = _host_rows(rays, 6)
+        res, ptrs = _outputs("DL", outputs, n)
+        o = _query_opts(bias, no_bvh)
         _check(_lib.rt_direct_light_rays(self.ctx.handle, self._h, ctypes.byref(o),
                                          rays.ctypes.data if n else None, n, outputs,
                                          ctypes.byref(ptrs)))
@@ -771,15 +805,10 @@ class DeviceScene:
         in the kernel arguments).  Returns a dict of float64 [n,3] tensors; `out` may hold a
         tensor per requested name to write into."""
         import torch
-        dev = torch.device(f"cuda:{self.ctx.device}")
-        if points.dtype != torch.float64 or points.device != dev or not points.is_contiguous():
-            raise ValueError("points: a contiguous float64 tensor on the context's device")
-        n = points.numel() // 9
-        if points.numel() != 9 * n:
-            raise ValueError("points: n*9 elements")
+        dev = self._device()
+        n = _checked_input(points, dev, torch.float64, 9, "points")
         if torch.is_tensor(materials) and materials.numel() != 7:
-            if (materials.dtype != torch.float64 or materials.device != dev
-                    or materials.numel() != 7 * n or not materials.is_contiguous()):
+            if _checked_input(materials, dev, torch.float64, 7, "materials") != n:
                 raise ValueError("materials: a contiguous float64 [n,7] tensor on the device")
             m_ptr, n_m = materials.data_ptr(), n
         else:   # one material: a host record, read by the call before it returns
@@ -787,8 +816,8 @@ class DeviceScene:
                 materials = materials.detach().cpu().numpy().reshape(7)
             host = material_rows(materials, 1)
             m_ptr, n_m = host.ctypes.data, 1
-        res, ptrs = self._dl_device(n, outputs, out)
-        o = default_opts(bias=bias, flags=RT_FLAG_NO_BVH if no_bvh else 0)
+        res, ptrs = _outputs("DL", outputs, n, dev, out)
+        o = _query_opts(bias, no_bvh)
         _check(_lib.rt_direct_light_device(self.ctx.handle, self._h, ctypes.byref(o),
                                            points.data_ptr() if n else None, m_ptr, n_m, n,
                                            outputs, ctypes.byref(ptrs)))
@@ -800,14 +829,10 @@ class DeviceScene:
         float64 [n,6] tensor on this context's device.  Returns a dict of float64 [n,3] tensors;
         `out` may hold a tensor per requested name to write into."""
         import torch
-        dev = torch.device(f"cuda:{self.ctx.device}")
-        if rays.dtype != torch.float64 or rays.device != dev or not rays.is_contiguous():
-            raise ValueError("rays: a contiguous float64 tensor on the context's device")
-        n = rays.numel() // 6
-        if rays.numel() != 6 * n:
-            raise ValueError("rays: n*6 elements")
-        res, ptrs = self._dl_device(n, outputs, out)
-        o = default_opts(bias=bias, flags=RT_FLAG_NO_BVH if no_bvh else 0)
+        dev = self._device()
+        n = _checked_input(rays, dev, torch.float64, 6, "rays")
+        res, ptrs = _outputs("DL", outputs, n, dev, out)
+        o = _query_opts(bias, no_bvh)
         _check(_lib.rt_direct_light_rays_device(self.ctx.handle, self._h, ctypes.byref(o),
                                                 rays.data_ptr() if n else None, n, outputs,
                                                 ctypes.byref(ptrs)))
@@ -820,14 +845,9 @@ class DeviceScene:
         rw}: float64; "flags" [n] uint8: bit 0 hit, bit 1 refraction ray, bit 2 reflection ray}
         for the SC_* bits of `outputs`.  An absent child is zeros.  terminal: every ray is at the
         recursion limit (max_recursion = 0): sky, no intersection, no children."""
-        rays = np.ascontiguousarray(rays, np.float64).reshape(-1, 6)
-        n = rays.shape[0]
-        _sc_check(outputs)
-        res = {name: np.empty((n, k) if k else (n,), dt)
-               for name, bit, dt, k in SC_OUTPUTS if outputs & bit}
-        ptrs = ScatterPtrs(**{k: v.ctypes.data for k, v in res.items()})
-        o = default_opts(bias=bias, flags=RT_FLAG_NO_BVH if no_bvh else 0,
-                         max_recursion=0 if terminal else 1)
+        rays, n = _host_rows(rays, 6)
+        res, ptrs = _outputs("SC", outputs, n)
+        o = _query_opts(bias, no_bvh, 0 if terminal else 1)
         _check(_lib.rt_scatter_rays(self.ctx.handle, self._h, ctypes.byref(o),
                                     rays.ctypes.data if n else None, n, outputs,
                                     ctypes.byref(ptrs)))
@@ -839,30 +859,10 @@ class DeviceScene:
         [n,6] tensor on this context's device.  Returns the dict of scatter() as torch tensors;
         `out` may hold a tensor per requested name to write into."""
         import torch
-        dev = torch.device(f"cuda:{self.ctx.device}")
-        if rays.dtype != torch.float64 or rays.device != dev or not rays.is_contiguous():
-            raise ValueError("rays: a contiguous float64 tensor on the context's device")
-        n = rays.numel() // 6
-        if rays.numel() != 6 * n:
-            raise ValueError("rays: n*6 elements")
-        _sc_check(outputs)
-        res = {}
-        for name, bit, dt, k in SC_OUTPUTS:
-            if not outputs & bit:
-                continue
-            tdt = torch.uint8 if dt is np.uint8 else torch.float64
-            t = None if out is None else out.get(name)
-            if t is None:
-                t = torch.empty((n, k) if k else (n,), dtype=tdt, device=dev)
-            elif (t.dtype != tdt or t.device != dev or t.numel() < max(k, 1) * n
-                  or not t.is_contiguous()):
-                raise ValueError(f"out[{name!r}]: a contiguous {tdt} tensor of at least "
-                                 f"n*{max(k, 1)} elements on the device")
-            res[name] = t
-        # never a NULL pointer for a requested output, an empty tensor's included
-        ptrs = ScatterPtrs(**{k: (v.data_ptr() or 8) for k, v in res.items()})
-        o = default_opts(bias=bias, flags=RT_FLAG_NO_BVH if no_bvh else 0,
-                         max_recursion=0 if terminal else 1)
+        dev = self._device()
+        n = _checked_input(rays, dev, torch.float64, 6, "rays")
+        res, ptrs = _outputs("SC", outputs, n, dev, out)
+        o = _query_opts(bias, no_bvh, 0 if terminal else 1)
         _check(_lib.rt_scatter_rays_device(self.ctx.handle, self._h, ctypes.byref(o),
                                            rays.data_ptr() if n else None, n, outputs,
                                            ctypes.byref(ptrs)))
@@ -890,16 +890,10 @@ class DeviceScene:
         as a float64 [rows*W, 6] torch tensor on the context's device (`out`: a contiguous float64
         tensor of at least rows*W*6 elements to write into, returned as it is)."""
         import torch
-        dev = torch.device(f"cuda:{self.ctx.device}")
         rec, w, h = self._camera_record(cam)
         o = default_opts(**opts)
-        n = rendered_rows(o, h) * w
-        if out is None:
-            out = torch.empty((n, 6), dtype=torch.float64, device=dev)
-        elif (out.dtype != torch.float64 or out.device != dev or out.numel() < 6 * n
-              or not out.is_contiguous()):
-            raise ValueError("out: a contiguous float64 tensor of at least rows*W*6 elements on "
-                             "the device")
+        out = _out_tensor(out, self._device(), torch.float64, (rendered_rows(o, h) * w, 6),
+                          need="rows*W*6")
         _check(_lib.rt_camera_rays_device(self.ctx.handle, rec.ctypes.data, ctypes.byref(o),
                                           sample, out.data_ptr() or 8))
         return out
@@ -909,13 +903,9 @@ class DeviceScene:
         {"t" [n] float64, "prim" [n,2] int32 {type, index}, "normal" [n,3], "point" [n,3],
         "material" [n,7] float64} for the CH_* bits of `outputs`.  A miss: t = +inf, prim =
         {0, -1}, zeros elsewhere."""
-        rays = np.ascontiguousarray(rays, np.float64).reshape(-1, 6)
-        n = rays.shape[0]
-        _ch_check(outputs)
-        res = {name: np.empty((n, k) if k else (n,), dt)
-               for name, bit, dt, k in CH_OUTPUTS if outputs & bit}
-        ptrs = ClosestPtrs(**{k: (v.ctypes.data or 8) for k, v in res.items()})
-        o = default_opts(flags=RT_FLAG_NO_BVH if no_bvh else 0)
+        rays, n = _host_rows(rays, 6)
+        res, ptrs = _outputs("CH", outputs, n)
+        o = _query_opts(no_bvh=no_bvh)
         _check(_lib.rt_closest_rays(self.ctx.handle, self._h, ctypes.byref(o),
                                     rays.ctypes.data if n else None, n, outputs,
                                     ctypes.byref(ptrs)))
@@ -926,29 +916,10 @@ class DeviceScene:
         [n,6] tensor on this context's device.  Returns the dict of closest() as torch tensors;
         `out` may hold a tensor per requested name to write into."""
         import torch
-        dev = torch.device(f"cuda:{self.ctx.device}")
-        if rays.dtype != torch.float64 or rays.device != dev or not rays.is_contiguous():
-            raise ValueError("rays: a contiguous float64 tensor on the context's device")
-        n = rays.numel() // 6
-        if rays.numel() != 6 * n:
-            raise ValueError("rays: n*6 elements")
-        _ch_check(outputs)
-        res = {}
-        for name, bit, dt, k in CH_OUTPUTS:
-            if not outputs & bit:
-                continue
-            tdt = torch.int32 if dt is np.int32 else torch.float64
-            t = None if out is None else out.get(name)
-            if t is None:
-                t = torch.empty((n, k) if k else (n,), dtype=tdt, device=dev)
-            elif (t.dtype != tdt or t.device != dev or t.numel() < max(k, 1) * n
-                  or not t.is_contiguous()):
-                raise ValueError(f"out[{name!r}]: a contiguous {tdt} tensor of at least "
-                                 f"n*{max(k, 1)} elements on the device")
-            res[name] = t
-        # never a NULL pointer for a requested output, an empty tensor's included
-        ptrs = ClosestPtrs(**{k: (v.data_ptr() or 8) for k, v in res.items()})
-        o = default_opts(flags=RT_FLAG_NO_BVH if no_bvh else 0)
+        dev = self._device()
+        n = _checked_input(rays, dev, torch.float64, 6, "rays")
+        res, ptrs = _outputs("CH", outputs, n, dev, out)
+        o = _query_opts(no_bvh=no_bvh)
         _check(_lib.rt_closest_rays_device(self.ctx.handle, self._h, ctypes.byref(o),
                                            rays.data_ptr() if n else None, n, outputs,
                                            ctypes.byref(ptrs)))
@@ -960,18 +931,9 @@ class DeviceScene:
         contiguous float64 tensor of at least n*3 elements to write into, returned as it is).
         opts as trace_rays (max_recursion, bias, seed, flags)."""
         import torch
-        dev = torch.device(f"cuda:{self.ctx.device}")
-        if rays.dtype != torch.float64 or rays.device != dev or not rays.is_contiguous():
-            raise ValueError("rays: a contiguous float64 tensor on the context's device")
-        n = rays.numel() // 6
-        if rays.numel() != 6 * n:
-            raise ValueError("rays: n*6 elements")
-        if out is None:
-            out = torch.empty((n, 3), dtype=torch.float64, device=dev)
-        elif (out.dtype != torch.float64 or out.device != dev or out.numel() < 3 * n
-              or not out.is_contiguous()):
-            raise ValueError("out: a contiguous float64 tensor of at least n*3 elements on the "
-                             "device")
+        dev = self._device()
+        n = _checked_input(rays, dev, torch.float64, 6, "rays")
+        out = _out_tensor(out, dev, torch.float64, (n, 3), need="n*3")
         o = default_opts(**opts)
         _check(_lib.rt_trace_rays_device(self.ctx.handle, self._h, ctypes.byref(o),
                                          rays.data_ptr() if n else None, n,
@@ -1006,18 +968,12 @@ class DeviceScene:
         tensor to add to (contiguous float64, at least rows*W*3 elements, returned as it is),
         required when sample_begin > 0; with sample_begin == 0 it need not be initialised."""
         import torch
-        dev = torch.device(f"cuda:{self.ctx.device}")
         rec, w, h = self._camera_record(cam)
         o = default_opts(**opts)
-        n = rendered_rows(o, h) * w
-        if sum is None:
-            if sample_begin > 0:
-                raise ValueError("sum: required when sample_begin > 0")
-            sum = torch.empty((n, 3), dtype=torch.float64, device=dev)
-        elif (sum.dtype != torch.float64 or sum.device != dev or sum.numel() < 3 * n
-              or not sum.is_contiguous()):
-            raise ValueError("sum: a contiguous float64 tensor of at least rows*W*3 elements on "
-                             "the device")
+        if sum is None and sample_begin > 0:
+            raise ValueError("sum: required when sample_begin > 0")
+        sum = _out_tensor(sum, self._device(), torch.float64, (rendered_rows(o, h) * w, 3), "sum",
+                          "rows*W*3")
         _check(_lib.rt_accumulate_samples_device(self.ctx.handle, self._h, rec.ctypes.data,
                                                  ctypes.byref(o), sample_begin, sample_end,
                                                  sum.data_ptr() or 8))
@@ -1028,8 +984,7 @@ class DeviceScene:
         """sum / samples as render's outputs (rt_resolve): {"hdr64" float64 [n,3], "hdr32" float32
         [n,3], "ldr" uint8 [n,3] — [7,n,3] for TONEMAP_ALL — when tonemap is not TONEMAP_NONE}
         from a float64 [n,3] host sum.  With samples = 1 the bytes are Context.tonemap's."""
-        sum = np.ascontiguousarray(sum, np.float64).reshape(-1, 3)
-        n = sum.shape[0]
+        sum, n = _host_rows(sum, 3)
         out = {}
         if hdr64:
             out["hdr64"] = np.empty((n, 3), np.float64)
@@ -1049,12 +1004,8 @@ class DeviceScene:
         hold a tensor per requested name to write into).  No host synchronisation: after
         accumulate_device on the same context the sum is read in stream order."""
         import torch
-        dev = torch.device(f"cuda:{self.ctx.device}")
-        if sum.dtype != torch.float64 or sum.device != dev or not sum.is_contiguous():
-            raise ValueError("sum: a contiguous float64 tensor on the context's device")
-        n = sum.numel() // 3
-        if sum.numel() != 3 * n:
-            raise ValueError("sum: n*3 elements")
+        dev = self._device()
+        n = _checked_input(sum, dev, torch.float64, 3, "sum")
         want = []
         if hdr64:
             want.append(("hdr64", torch.float64, (n, 3)))
@@ -1062,18 +1013,11 @@ class DeviceScene:
             want.append(("hdr32", torch.float32, (n, 3)))
         if tonemap != TONEMAP_NONE:
             want.append(("ldr", torch.uint8, (7, n, 3) if tonemap == TONEMAP_ALL else (n, 3)))
-        res = {}
-        for name, tdt, shape in want:
-            t = None if out is None else out.get(name)
-            if t is None:
-                t = torch.empty(shape, dtype=tdt, device=dev)
-            elif (t.dtype != tdt or t.device != dev or t.numel() < int(np.prod(shape))
-                  or not t.is_contiguous()):
-                raise ValueError(f"out[{name!r}]: a contiguous {tdt} tensor of at least "
-                                 f"{int(np.prod(shape))} elements on the device")
-            res[name] = t
-        ptr = {k: (v.data_ptr() or 8) for k, v in res.items()}
+        res = {name: _out_tensor(None if out is None else out.get(name), dev, tdt, shape,
+                                 f"out[{name!r}]", str(math.prod(shape)))
+               for name, tdt, shape in want}
         # never a NULL pointer for a requested output or the sum, an empty tensor's included
+        ptr = {k: (v.data_ptr() or 8) for k, v in res.items()}
         _check(_lib.rt_resolve_device(self.ctx.handle, sum.data_ptr() or 8, n, samples, tonemap,
                                       ptr.get("hdr64"), ptr.get("hdr32"), ptr.get("ldr")))
         return res

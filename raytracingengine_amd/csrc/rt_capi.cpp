@@ -1,4 +1,5 @@
-// rt_capi.cpp — implementation of include/rt_capi.h on HIP (gfx950).
+// rt_capi.cpp — implementation of include/rt_capi.h on HIP (gfx950): contexts, scenes, render,
+// G-buffer, statistics and the rt_debug_* entries (the batch queries: rt_capi_queries.cpp).
 //
 // The context owns a device, a stream and growable device staging buffers; a scene is one
 // HBM allocation of packed records (rt_internal.hpp).  No exception crosses the C boundary.
@@ -997,832 +998,6 @@ rt_status rt_stats_reset(rt_context* ctx) {
     ctx->timed_ms = 0.0;
     ctx->launches = 0;
     RT_HIP(hipMemset(ctx->counters.ptr, 0, 2 * sizeof(unsigned long long)));
-    return RT_OK;
-}
-
-// A 1×1 camera: the batch entry points reuse build_params for the scene/opts part only.
-static rt_camera batch_camera() {
-    rt_camera c;
-    std::memset(&c, 0, sizeof c);
-    c.width = 1;
-    c.height = 1;
-    c.aa_samples = 1;
-    return c;
-}
-
-rt_status rt_trace_rays(rt_context* ctx, const rt_scene* sc, const rt_render_opts* opts,
-                        const double* rays, size_t n, double* rgb, rt_stats* stats) {
-    if (!ctx || (n && (!rays || !rgb))) return fail(RT_ERR_INVALID_ARG, "NULL argument to rt_trace_rays");
-    DeviceGuard g(ctx->device);
-    const rt_camera cam = batch_camera();
-    rt_render_opts o;
-    if (opts) o = *opts;
-    else rt_render_opts_default(&o);
-    o.row_begin = 0;
-    o.row_end = 0;
-    TraceParams p;
-    int path;
-    bool lds;
-    size_t lds_bytes;
-    uint32_t rows;
-    rt_status st = build_params(ctx, sc, &cam, &o, p, path, lds, lds_bytes, rows);
-    if (st != RT_OK) return st;
-    if (stats) std::memset(stats, 0, sizeof *stats);
-    if (n == 0) return RT_OK;
-    RT_HIP(ctx->rays.ensure(n * 9 * sizeof(double)));
-    double* d_rays = static_cast<double*>(ctx->rays.ptr);
-    double* d_out = d_rays + 6 * n;
-    RT_HIP(hipMemcpyAsync(d_rays, rays, n * 6 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    RT_HIP(launch_trace_rays(p, path, false, d_rays, n, d_out, ctx->stream));
-    RT_HIP(hipMemcpyAsync(rgb, d_out, n * 3 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (stats) {
-        p.counters = static_cast<unsigned long long*>(ctx->counters.ptr);
-        st = scratch_wait(ctx);
-        if (st != RT_OK) return st;
-        RT_HIP(hipMemsetAsync(p.counters, 0, 2 * sizeof(unsigned long long), ctx->stream));
-        RT_HIP(launch_trace_rays(p, path, true, d_rays, n, d_out, ctx->stream));
-        unsigned long long c[2] = {0, 0};
-        RT_HIP(hipMemcpyAsync(c, p.counters, sizeof c, hipMemcpyDeviceToHost, ctx->stream));
-        st = scratch_done(ctx);  // the counters' last user is this read-back
-        if (st != RT_OK) return st;
-        RT_HIP(hipStreamSynchronize(ctx->stream));
-        stats->trace_rays = c[0];
-        stats->shadow_rays = c[1];
-        return RT_OK;
-    }
-    RT_HIP(hipStreamSynchronize(ctx->stream));
-    return RT_OK;
-}
-
-// rt_trace_rays on device pointers: the same parameters and kernel selection, no staging copy,
-// no counting pass, no synchronisation.
-rt_status rt_trace_rays_device(rt_context* ctx, const rt_scene* sc, const rt_render_opts* opts,
-                               const void* d_rays, size_t n, void* d_rgb) {
-    if (!ctx || (n && (!d_rays || !d_rgb)))
-        return fail(RT_ERR_INVALID_ARG, "NULL argument to rt_trace_rays_device");
-    DeviceGuard g(ctx->device);
-    const rt_camera cam = batch_camera();
-    rt_render_opts o;
-    if (opts) o = *opts;
-    else rt_render_opts_default(&o);
-    o.row_begin = 0;
-    o.row_end = 0;
-    TraceParams p;
-    int path;
-    bool lds;
-    size_t lds_bytes;
-    uint32_t rows;
-    rt_status st = build_params(ctx, sc, &cam, &o, p, path, lds, lds_bytes, rows);
-    if (st != RT_OK) return st;
-    if (n == 0) return RT_OK;
-    RT_HIP(launch_trace_rays(p, path, false, static_cast<const double*>(d_rays), n,
-                             static_cast<double*>(d_rgb), ctx->stream));
-    return RT_OK;
-}
-
-rt_status rt_intersect_rays(rt_context* ctx, const rt_scene* sc, const double* rays, size_t n,
-                            double* hits) {
-    if (!ctx || (n && (!rays || !hits)))
-        return fail(RT_ERR_INVALID_ARG, "NULL argument to rt_intersect_rays");
-    DeviceGuard g(ctx->device);
-    const rt_camera cam = batch_camera();
-    TraceParams p;
-    int path;
-    bool lds;
-    size_t lds_bytes;
-    uint32_t rows;
-    rt_status st = build_params(ctx, sc, &cam, nullptr, p, path, lds, lds_bytes, rows);
-    if (st != RT_OK) return st;
-    if (n == 0) return RT_OK;
-    RT_HIP(ctx->rays.ensure(n * 15 * sizeof(double)));
-    double* d_rays = static_cast<double*>(ctx->rays.ptr);
-    double* d_out = d_rays + 6 * n;
-    RT_HIP(hipMemcpyAsync(d_rays, rays, n * 6 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    RT_HIP(launch_intersect_rays(p, d_rays, n, d_out, ctx->stream));
-    RT_HIP(hipMemcpyAsync(hits, d_out, n * 9 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    RT_HIP(hipStreamSynchronize(ctx->stream));
-    return RT_OK;
-}
-
-// The launch parameters of the any-hit query: the scene part of build_params; of opts only
-// RT_FLAG_NO_BVH is read (whatever else the caller left there must neither fail nor steer it).
-static rt_status occluded_params(rt_context* ctx, const rt_scene* sc, const rt_render_opts* opts,
-                                 TraceParams& p) {
-    const rt_camera cam = batch_camera();
-    rt_render_opts o;
-    rt_render_opts_default(&o);
-    if (opts) o.flags = opts->flags & RT_FLAG_NO_BVH;
-    int path;
-    bool lds;
-    size_t lds_bytes;
-    uint32_t rows;
-    return build_params(ctx, sc, &cam, &o, p, path, lds, lds_bytes, rows);
-}
-
-rt_status rt_occluded_rays_device(rt_context* ctx, const rt_scene* sc, const rt_render_opts* opts,
-                                  const void* d_rays, const void* d_max_dist, size_t n,
-                                  void* d_occluded) {
-    if (!ctx || (n && (!d_rays || !d_max_dist || !d_occluded)))
-        return fail(RT_ERR_INVALID_ARG, "NULL argument to rt_occluded_rays_device");
-    DeviceGuard g(ctx->device);
-    TraceParams p;
-    rt_status st = occluded_params(ctx, sc, opts, p);
-    if (st != RT_OK) return st;
-    if (n == 0) return RT_OK;
-    RT_HIP(launch_occluded_rays(p, static_cast<const double*>(d_rays),
-                                static_cast<const double*>(d_max_dist), n,
-                                static_cast<uint8_t*>(d_occluded), ctx->stream));
-    return RT_OK;
-}
-
-rt_status rt_occluded_rays(rt_context* ctx, const rt_scene* sc, const rt_render_opts* opts,
-                           const double* rays, const double* max_dist, size_t n,
-                           uint8_t* occluded_out) {
-    if (!ctx || (n && (!rays || !max_dist || !occluded_out)))
-        return fail(RT_ERR_INVALID_ARG, "NULL argument to rt_occluded_rays");
-    DeviceGuard g(ctx->device);
-    TraceParams p;
-    rt_status st = occluded_params(ctx, sc, opts, p);
-    if (st != RT_OK) return st;
-    if (n == 0) return RT_OK;
-    // ctx->rays: n rays (6 doubles), n distances, n answer bytes
-    RT_HIP(ctx->rays.ensure(n * 7 * sizeof(double) + n));
-    double* d_rays = static_cast<double*>(ctx->rays.ptr);
-    double* d_dist = d_rays + 6 * n;
-    uint8_t* d_out = reinterpret_cast<uint8_t*>(d_dist + n);
-    RT_HIP(hipMemcpyAsync(d_rays, rays, n * 6 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    RT_HIP(hipMemcpyAsync(d_dist, max_dist, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    RT_HIP(launch_occluded_rays(p, d_rays, d_dist, n, d_out, ctx->stream));
-    RT_HIP(hipMemcpyAsync(occluded_out, d_out, n, hipMemcpyDeviceToHost, ctx->stream));
-    RT_HIP(hipStreamSynchronize(ctx->stream));
-    return RT_OK;
-}
-
-// The launch parameters of the transmittance queries: the scene part of build_params; of opts
-// only bias and RT_FLAG_NO_BVH are read, as occluded_params reads its flag.  opaque: no material
-// is transparent — what selects the tree path — so the kernels' occlusion_opaque variant serves
-// the scene; RTAMD_TX_OPAQUE=0 (read per launch) sends it through the march alone (A/B, tests).
-static rt_status transmit_params(rt_context* ctx, const rt_scene* sc, const rt_render_opts* opts,
-                                 TraceParams& p, bool& opaque) {
-    const rt_camera cam = batch_camera();
-    rt_render_opts o;
-    rt_render_opts_default(&o);
-    if (opts) {
-        o.flags = opts->flags & RT_FLAG_NO_BVH;
-        o.bias = opts->bias;
-    }
-    int path;
-    bool lds;
-    size_t lds_bytes;
-    uint32_t rows;
-    rt_status st = build_params(ctx, sc, &cam, &o, p, path, lds, lds_bytes, rows);
-    if (st != RT_OK) return st;
-    const char* e = std::getenv("RTAMD_TX_OPAQUE");
-    opaque = !sc->any_transparent && !(e && std::atoi(e) == 0);
-    return RT_OK;
-}
-
-rt_status rt_transmittance_rays_device(rt_context* ctx, const rt_scene* sc,
-                                       const rt_render_opts* opts, const void* d_rays,
-                                       const void* d_max_dist, size_t n, void* d_T) {
-    if (!ctx || (n && (!d_rays || !d_max_dist || !d_T)))
-        return fail(RT_ERR_INVALID_ARG, "NULL argument to rt_transmittance_rays_device");
-    DeviceGuard g(ctx->device);
-    TraceParams p;
-    bool opaque;
-    rt_status st = transmit_params(ctx, sc, opts, p, opaque);
-    if (st != RT_OK) return st;
-    if (n == 0) return RT_OK;
-    RT_HIP(launch_transmittance_rays(p, opaque, static_cast<const double*>(d_rays),
-                                     static_cast<const double*>(d_max_dist), n,
-                                     static_cast<double*>(d_T), ctx->stream));
-    return RT_OK;
-}
-
-rt_status rt_transmittance_rays(rt_context* ctx, const rt_scene* sc, const rt_render_opts* opts,
-                                const double* rays, const double* max_dist, size_t n,
-                                double* T_out) {
-    if (!ctx || (n && (!rays || !max_dist || !T_out)))
-        return fail(RT_ERR_INVALID_ARG, "NULL argument to rt_transmittance_rays");
-    DeviceGuard g(ctx->device);
-    TraceParams p;
-    bool opaque;
-    rt_status st = transmit_params(ctx, sc, opts, p, opaque);
-    if (st != RT_OK) return st;
-    if (n == 0) return RT_OK;
-    // ctx->rays: n rays (6 doubles), n distances, n answers
-    RT_HIP(ctx->rays.ensure(n * 8 * sizeof(double)));
-    double* d_rays = static_cast<double*>(ctx->rays.ptr);
-    double* d_dist = d_rays + 6 * n;
-    double* d_out = d_dist + n;
-    RT_HIP(hipMemcpyAsync(d_rays, rays, n * 6 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    RT_HIP(hipMemcpyAsync(d_dist, max_dist, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    RT_HIP(launch_transmittance_rays(p, opaque, d_rays, d_dist, n, d_out, ctx->stream));
-    RT_HIP(hipMemcpyAsync(T_out, d_out, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    RT_HIP(hipStreamSynchronize(ctx->stream));
-    return RT_OK;
-}
-
-rt_status rt_light_transmittance_device(rt_context* ctx, const rt_scene* sc,
-                                        const rt_render_opts* opts, const void* d_points, size_t n,
-                                        void* d_T) {
-    if (!ctx || (n && !d_points))
-        return fail(RT_ERR_INVALID_ARG, "NULL argument to rt_light_transmittance_device");
-    DeviceGuard g(ctx->device);
-    TraceParams p;
-    bool opaque;
-    rt_status st = transmit_params(ctx, sc, opts, p, opaque);
-    if (st != RT_OK) return st;
-    if (n == 0 || p.nl == 0) return RT_OK;  // no lights: nothing is written
-    if (!d_T)  // with no lights there is no output to point to
-        return fail(RT_ERR_INVALID_ARG, "NULL argument to rt_light_transmittance_device");
-    RT_HIP(launch_light_transmittance(p, opaque, static_cast<const double*>(d_points), n,
-                                      static_cast<double*>(d_T), ctx->stream));
-    return RT_OK;
-}
-
-rt_status rt_light_transmittance(rt_context* ctx, const rt_scene* sc, const rt_render_opts* opts,
-                                 const double* points, size_t n, double* T_out) {
-    if (!ctx || (n && !points))
-        return fail(RT_ERR_INVALID_ARG, "NULL argument to rt_light_transmittance");
-    DeviceGuard g(ctx->device);
-    TraceParams p;
-    bool opaque;
-    rt_status st = transmit_params(ctx, sc, opts, p, opaque);
-    if (st != RT_OK) return st;
-    if (n == 0 || p.nl == 0) return RT_OK;  // no lights: nothing is written
-    if (!T_out)  // with no lights there is no output to point to
-        return fail(RT_ERR_INVALID_ARG, "NULL argument to rt_light_transmittance");
-    // ctx->rays: n points (6 doubles), n * nl answers
-    const size_t nl = static_cast<size_t>(p.nl);
-    RT_HIP(ctx->rays.ensure(n * (6 + nl) * sizeof(double)));
-    double* d_pts = static_cast<double*>(ctx->rays.ptr);
-    double* d_out = d_pts + 6 * n;
-    RT_HIP(hipMemcpyAsync(d_pts, points, n * 6 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    RT_HIP(launch_light_transmittance(p, opaque, d_pts, n, d_out, ctx->stream));
-    RT_HIP(hipMemcpyAsync(T_out, d_out, n * nl * sizeof(double), hipMemcpyDeviceToHost,
-                          ctx->stream));
-    RT_HIP(hipStreamSynchronize(ctx->stream));
-    return RT_OK;
-}
-
-// ---- direct lighting (rt_direct.hip) -------------------------------------------------------
-static_assert(sizeof(rt_material) == 7 * sizeof(double), "rt_material is not seven packed doubles");
-
-// The argument checks the four direct-light entries share, made before anything touches a
-// device; `entry` ends every message.  inputs_ok: no input pointer is NULL, or n == 0.
-static rt_status check_direct_light_args(const rt_context* ctx, int outputs,
-                                         const rt_direct_light_out* out, bool inputs_ok,
-                                         size_t n_materials, size_t n, const char* entry) {
-    const std::string name(entry);
-    if (outputs == 0) return fail(RT_ERR_INVALID_ARG, "no output requested from " + name);
-    if (outputs & ~RT_DL_ALL) return fail(RT_ERR_INVALID_ARG, "unknown output bit passed to " + name);
-    if (!out) return fail(RT_ERR_INVALID_ARG, "NULL output record passed to " + name);
-    const void* ptr[3] = {out->radiance, out->diffuse, out->specular};
-    for (int k = 0; k < 3; ++k)
-        if ((outputs & (1 << k)) && !ptr[k])
-            return fail(RT_ERR_INVALID_ARG, "NULL pointer of a requested output passed to " + name);
-    if (!inputs_ok) return fail(RT_ERR_INVALID_ARG, "NULL argument to " + name);
-    if (n && n_materials != n && n_materials != 1)
-        return fail(RT_ERR_INVALID_ARG, "n_materials must be n or 1 in " + name);
-    if (!ctx) return fail(RT_ERR_INVALID_ARG, "NULL context passed to " + name);
-    return RT_OK;
-}
-
-// The requested outputs of `o` as the kernels take them (a pointer that was not requested is
-// not passed on).
-static DlOut direct_light_outputs(int outputs, const rt_direct_light_out& o) {
-    return DlOut{(outputs & RT_DL_RADIANCE) ? static_cast<double*>(o.radiance) : nullptr,
-                 (outputs & RT_DL_DIFFUSE) ? static_cast<double*>(o.diffuse) : nullptr,
-                 (outputs & RT_DL_SPECULAR) ? static_cast<double*>(o.specular) : nullptr};
-}
-
-static DlMaterial shared_material(const void* m) {
-    DlMaterial s;
-    std::memcpy(s.v, m, 7 * sizeof(double));
-    s.v[7] = 0.0;
-    return s;
-}
-
-// n*3 doubles per requested output after `used` doubles of ctx->rays (already ensured).
-static rt_direct_light_out direct_light_staging(rt_context* ctx, size_t used, size_t n,
-                                                int outputs) {
-    double* at = static_cast<double*>(ctx->rays.ptr) + used;
-    rt_direct_light_out d{nullptr, nullptr, nullptr};
-    void** slot[3] = {&d.radiance, &d.diffuse, &d.specular};
-    for (int k = 0; k < 3; ++k)
-        if (outputs & (1 << k)) {
-            *slot[k] = at;
-            at += 3 * n;
-        }
-    return d;
-}
-
-static rt_status direct_light_download(rt_context* ctx, const rt_direct_light_out& d,
-                                       const rt_direct_light_out& h, size_t n, int outputs) {
-    void* const dev[3] = {d.radiance, d.diffuse, d.specular};
-    void* const host[3] = {h.radiance, h.diffuse, h.specular};
-    for (int k = 0; k < 3; ++k)
-        if (outputs & (1 << k))
-            RT_HIP(hipMemcpyAsync(host[k], dev[k], n * 3 * sizeof(double), hipMemcpyDeviceToHost,
-                                  ctx->stream));
-    RT_HIP(hipStreamSynchronize(ctx->stream));
-    return RT_OK;
-}
-
-static size_t popcount3(int outputs) {
-    return static_cast<size_t>((outputs & 1) + ((outputs >> 1) & 1) + ((outputs >> 2) & 1));
-}
-
-rt_status rt_direct_light_device(rt_context* ctx, const rt_scene* sc, const rt_render_opts* opts,
-                                 const void* d_points, const void* d_materials, size_t n_materials,
-                                 size_t n, int outputs, const struct rt_direct_light_out* d_out) {
-    const char* entry = "rt_direct_light_device";
-    rt_status st = check_direct_light_args(ctx, outputs, d_out, !n || (d_points && d_materials),
-                                           n_materials, n, entry);
-    if (st != RT_OK) return st;
-    if (n == 0) return RT_OK;
-    DeviceGuard g(ctx->device);
-    TraceParams p;
-    bool opaque;
-    st = transmit_params(ctx, sc, opts, p, opaque);
-    if (st != RT_OK) return st;
-    // one material for all points: d_materials is a host pointer, read now (rt_capi.h)
-    const bool shared = n_materials == 1;
-    RT_HIP(launch_direct_light_points(p, opaque, static_cast<const double*>(d_points),
-                                      shared ? nullptr : static_cast<const double*>(d_materials),
-                                      shared ? shared_material(d_materials) : DlMaterial{}, n,
-                                      direct_light_outputs(outputs, *d_out), ctx->stream));
-    return RT_OK;
-}
-
-rt_status rt_direct_light(rt_context* ctx, const rt_scene* sc, const rt_render_opts* opts,
-                          const double* points, const rt_material* materials, size_t n_materials,
-                          size_t n, int outputs, const struct rt_direct_light_out* out) {
-    const char* entry = "rt_direct_light";
-    rt_status st = check_direct_light_args(ctx, outputs, out, !n || (points && materials),
-                                           n_materials, n, entry);
-    if (st != RT_OK) return st;
-    if (n == 0) return RT_OK;
-    DeviceGuard g(ctx->device);
-    TraceParams p;
-    bool opaque;
-    st = transmit_params(ctx, sc, opts, p, opaque);
-    if (st != RT_OK) return st;
-    // ctx->rays: n points (9 doubles), n materials (7 doubles) unless one is shared, and n * 3
-    // doubles per requested output
-    const bool shared = n_materials == 1;
-    const size_t in = n * (shared ? 9 : 16);
-    RT_HIP(ctx->rays.ensure((in + 3 * n * popcount3(outputs)) * sizeof(double)));
-    double* d_pts = static_cast<double*>(ctx->rays.ptr);
-    double* d_mat = d_pts + 9 * n;
-    RT_HIP(hipMemcpyAsync(d_pts, points, n * 9 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    if (!shared)
-        RT_HIP(hipMemcpyAsync(d_mat, materials, n * 7 * sizeof(double), hipMemcpyHostToDevice,
-                              ctx->stream));
-    const rt_direct_light_out d = direct_light_staging(ctx, in, n, outputs);
-    RT_HIP(launch_direct_light_points(p, opaque, d_pts, shared ? nullptr : d_mat,
-                                      shared ? shared_material(materials) : DlMaterial{}, n,
-                                      direct_light_outputs(outputs, d), ctx->stream));
-    return direct_light_download(ctx, d, *out, n, outputs);
-}
-
-rt_status rt_direct_light_rays_device(rt_context* ctx, const rt_scene* sc,
-                                      const rt_render_opts* opts, const void* d_rays, size_t n,
-                                      int outputs, const struct rt_direct_light_out* d_out) {
-    const char* entry = "rt_direct_light_rays_device";
-    rt_status st = check_direct_light_args(ctx, outputs, d_out, !n || d_rays, 1, n, entry);
-    if (st != RT_OK) return st;
-    if (n == 0) return RT_OK;
-    DeviceGuard g(ctx->device);
-    TraceParams p;
-    bool opaque;
-    st = transmit_params(ctx, sc, opts, p, opaque);
-    if (st != RT_OK) return st;
-    RT_HIP(launch_direct_light_rays(p, opaque, static_cast<const double*>(d_rays), n,
-                                    direct_light_outputs(outputs, *d_out), ctx->stream));
-    return RT_OK;
-}
-
-rt_status rt_direct_light_rays(rt_context* ctx, const rt_scene* sc, const rt_render_opts* opts,
-                               const double* rays, size_t n, int outputs,
-                               const struct rt_direct_light_out* out) {
-    const char* entry = "rt_direct_light_rays";
-    rt_status st = check_direct_light_args(ctx, outputs, out, !n || rays, 1, n, entry);
-    if (st != RT_OK) return st;
-    if (n == 0) return RT_OK;
-    DeviceGuard g(ctx->device);
-    TraceParams p;
-    bool opaque;
-    st = transmit_params(ctx, sc, opts, p, opaque);
-    if (st != RT_OK) return st;
-    // ctx->rays: n rays (6 doubles) and n * 3 doubles per requested output
-    RT_HIP(ctx->rays.ensure(n * (6 + 3 * popcount3(outputs)) * sizeof(double)));
-    double* d_rays = static_cast<double*>(ctx->rays.ptr);
-    RT_HIP(hipMemcpyAsync(d_rays, rays, n * 6 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    const rt_direct_light_out d = direct_light_staging(ctx, 6 * n, n, outputs);
-    RT_HIP(launch_direct_light_rays(p, opaque, d_rays, n, direct_light_outputs(outputs, d),
-                                    ctx->stream));
-    return direct_light_download(ctx, d, *out, n, outputs);
-}
-
-// ---- scatter (rt_scatter.hip) ---------------------------------------------------------------
-// Bytes per ray of each output, in RT_SC_* bit order.
-static constexpr size_t kScBytes[5] = {24, 48, 48, 16, 1};
-
-// The argument checks of the two scatter entries, in rt_direct_light_rays' order, made before
-// anything touches a device; `entry` ends every message.
-static rt_status check_scatter_args(const rt_context* ctx, int outputs, const rt_scatter_out* out,
-                                    bool inputs_ok, const char* entry) {
-    const std::string name(entry);
-    if (outputs == 0) return fail(RT_ERR_INVALID_ARG, "no output requested from " + name);
-    if (outputs & ~RT_SC_ALL) return fail(RT_ERR_INVALID_ARG, "unknown output bit passed to " + name);
-    if (!out) return fail(RT_ERR_INVALID_ARG, "NULL output record passed to " + name);
-    const void* ptr[5] = {out->value, out->refract_rays, out->reflect_rays, out->weights, out->flags};
-    for (int k = 0; k < 5; ++k)
-        if ((outputs & (1 << k)) && !ptr[k])
-            return fail(RT_ERR_INVALID_ARG, "NULL pointer of a requested output passed to " + name);
-    if (!inputs_ok) return fail(RT_ERR_INVALID_ARG, "NULL argument to " + name);
-    if (!ctx) return fail(RT_ERR_INVALID_ARG, "NULL context passed to " + name);
-    return RT_OK;
-}
-
-static ScOut scatter_outputs(int outputs, const rt_scatter_out& o) {
-    return ScOut{(outputs & RT_SC_VALUE) ? static_cast<double*>(o.value) : nullptr,
-                 (outputs & RT_SC_REFRACT) ? static_cast<double*>(o.refract_rays) : nullptr,
-                 (outputs & RT_SC_REFLECT) ? static_cast<double*>(o.reflect_rays) : nullptr,
-                 (outputs & RT_SC_WEIGHTS) ? static_cast<double*>(o.weights) : nullptr,
-                 (outputs & RT_SC_FLAGS) ? static_cast<uint8_t*>(o.flags) : nullptr};
-}
-
-// transmit_params, and of opts->max_recursion its sign: 0 is "at the recursion limit".
-static rt_status scatter_params(rt_context* ctx, const rt_scene* sc, const rt_render_opts* opts,
-                                TraceParams& p, bool& opaque) {
-    rt_status st = transmit_params(ctx, sc, opts, p, opaque);
-    if (st != RT_OK) return st;
-    p.max_rec = (opts && opts->max_recursion <= 0) ? 0 : 1;
-    return RT_OK;
-}
-
-rt_status rt_scatter_rays_device(rt_context* ctx, const rt_scene* sc, const rt_render_opts* opts,
-                                 const void* d_rays, size_t n, int outputs,
-                                 const struct rt_scatter_out* d_out) {
-    rt_status st = check_scatter_args(ctx, outputs, d_out, !n || d_rays, "rt_scatter_rays_device");
-    if (st != RT_OK) return st;
-    if (n == 0) return RT_OK;
-    DeviceGuard g(ctx->device);
-    TraceParams p;
-    bool opaque;
-    st = scatter_params(ctx, sc, opts, p, opaque);
-    if (st != RT_OK) return st;
-    RT_HIP(launch_scatter_rays(p, opaque, static_cast<const double*>(d_rays), n,
-                               scatter_outputs(outputs, *d_out), ctx->stream));
-    return RT_OK;
-}
-
-rt_status rt_scatter_rays(rt_context* ctx, const rt_scene* sc, const rt_render_opts* opts,
-                          const double* rays, size_t n, int outputs,
-                          const struct rt_scatter_out* out) {
-    rt_status st = check_scatter_args(ctx, outputs, out, !n || rays, "rt_scatter_rays");
-    if (st != RT_OK) return st;
-    if (n == 0) return RT_OK;
-    DeviceGuard g(ctx->device);
-    TraceParams p;
-    bool opaque;
-    st = scatter_params(ctx, sc, opts, p, opaque);
-    if (st != RT_OK) return st;
-    // ctx->rays: n rays (6 doubles), then each requested output in bit order; the doubles first,
-    // so the flag bytes, the last, leave every other output 8-byte aligned
-    size_t bytes = n * 6 * sizeof(double);
-    for (int k = 0; k < 5; ++k)
-        if (outputs & (1 << k)) bytes += n * kScBytes[k];
-    RT_HIP(ctx->rays.ensure(bytes));
-    char* at = static_cast<char*>(ctx->rays.ptr);
-    double* d_rays = reinterpret_cast<double*>(at);
-    at += n * 6 * sizeof(double);
-    rt_scatter_out d{nullptr, nullptr, nullptr, nullptr, nullptr};
-    void** slot[5] = {&d.value, &d.refract_rays, &d.reflect_rays, &d.weights, &d.flags};
-    void* const host[5] = {out->value, out->refract_rays, out->reflect_rays, out->weights, out->flags};
-    for (int k = 0; k < 5; ++k)
-        if (outputs & (1 << k)) {
-            *slot[k] = at;
-            at += n * kScBytes[k];
-        }
-    RT_HIP(hipMemcpyAsync(d_rays, rays, n * 6 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    RT_HIP(launch_scatter_rays(p, opaque, d_rays, n, scatter_outputs(outputs, d), ctx->stream));
-    for (int k = 0; k < 5; ++k)
-        if (outputs & (1 << k))
-            RT_HIP(hipMemcpyAsync(host[k], *slot[k], n * kScBytes[k], hipMemcpyDeviceToHost,
-                                  ctx->stream));
-    RT_HIP(hipStreamSynchronize(ctx->stream));
-    return RT_OK;
-}
-
-// ---- camera rays (rt_camera_rays.hip) -------------------------------------------------------
-// The argument checks of the two camera-ray entries and the camera part of build_params: no scene
-// is involved, and of opts only the row set and the seed are read.
-static rt_status camera_rays_params(const rt_context* ctx, const rt_camera* cam,
-                                    const rt_render_opts* opts, int sample, const void* out,
-                                    const char* entry, TraceParams& p) {
-    const std::string name(entry);
-    if (!ctx || !cam || !out) return fail(RT_ERR_INVALID_ARG, "NULL argument to " + name);
-    if (cam->width == 0 || cam->height == 0)
-        return fail(RT_ERR_INVALID_ARG, "zero camera width or height passed to " + name);
-    if (static_cast<uint64_t>(cam->width) * cam->height > (1ull << 31))
-        return fail(RT_ERR_UNSUPPORTED, "image larger than 2^31 pixels passed to " + name);
-    if (sample < 0 || sample >= std::max(1, cam->aa_samples))
-        return fail(RT_ERR_INVALID_ARG, "sample " + std::to_string(sample) +
-                                            " outside [0, max(1, aa_samples)) passed to " + name);
-    rt_render_opts o;
-    rt_render_opts_default(&o);
-    if (opts) {
-        o.seed = opts->seed;
-        o.row_begin = opts->row_begin;
-        o.row_end = opts->row_end;
-        o.row_block = opts->row_block;
-        o.row_cycle = opts->row_cycle;
-    }
-    const uint32_t r1 = o.row_end ? o.row_end : cam->height;
-    if (r1 > cam->height || o.row_begin >= r1)
-        return fail(RT_ERR_INVALID_ARG, "row range [" + std::to_string(o.row_begin) + "," +
-                                            std::to_string(r1) + ") invalid for height " +
-                                            std::to_string(cam->height) + " passed to " + name);
-    if (o.row_cycle > 1 && o.row_block == 0)
-        return fail(RT_ERR_INVALID_ARG, "row_cycle > 1 without row_block >= 1 passed to " + name);
-    std::memset(&p, 0, sizeof p);
-    for (int i = 0; i < 3; ++i) p.cam_pos[i] = cam->position[i];
-    p.focal = cam->focal;
-    p.width = cam->width;
-    p.height = cam->height;
-    p.aa = cam->aa_samples;
-    p.seed = o.seed;
-    p.row0 = o.row_begin;
-    if (o.row_cycle > 1) {
-        p.row_block = o.row_block;
-        p.row_stride = static_cast<uint32_t>(o.row_block) * o.row_cycle;
-    }
-    p.rows = rendered_rows(o, cam->height);
-    return RT_OK;
-}
-
-rt_status rt_camera_rays_device(rt_context* ctx, const rt_camera* cam, const rt_render_opts* opts,
-                                int sample, void* d_rays) {
-    TraceParams p;
-    rt_status st = camera_rays_params(ctx, cam, opts, sample, d_rays, "rt_camera_rays_device", p);
-    if (st != RT_OK) return st;
-    DeviceGuard g(ctx->device);
-    RT_HIP(launch_camera_rays(p, sample, static_cast<double*>(d_rays), ctx->stream));
-    return RT_OK;
-}
-
-rt_status rt_camera_rays(rt_context* ctx, const rt_camera* cam, const rt_render_opts* opts,
-                         int sample, double* rays_out) {
-    TraceParams p;
-    rt_status st = camera_rays_params(ctx, cam, opts, sample, rays_out, "rt_camera_rays", p);
-    if (st != RT_OK) return st;
-    DeviceGuard g(ctx->device);
-    const size_t bytes = static_cast<size_t>(p.rows) * p.width * 6 * sizeof(double);
-    RT_HIP(ctx->rays.ensure(bytes));
-    double* d_rays = static_cast<double*>(ctx->rays.ptr);
-    RT_HIP(launch_camera_rays(p, sample, d_rays, ctx->stream));
-    RT_HIP(hipMemcpyAsync(rays_out, d_rays, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    RT_HIP(hipStreamSynchronize(ctx->stream));
-    return RT_OK;
-}
-
-// ---- closest hit with selectable outputs (rt_closest.hip) -----------------------------------
-// Bytes per ray of each output, in RT_CH_* bit order (every one a multiple of 8).
-static constexpr size_t kChBytes[5] = {8, 8, 24, 24, 56};
-
-// rt_scatter_rays' checks in its order, made before anything touches a device.
-static rt_status check_closest_args(const rt_context* ctx, int outputs, const rt_closest_out* out,
-                                    bool inputs_ok, const char* entry) {
-    const std::string name(entry);
-    if (outputs == 0) return fail(RT_ERR_INVALID_ARG, "no output requested from " + name);
-    if (outputs & ~RT_CH_ALL) return fail(RT_ERR_INVALID_ARG, "unknown output bit passed to " + name);
-    if (!out) return fail(RT_ERR_INVALID_ARG, "NULL output record passed to " + name);
-    const void* ptr[5] = {out->t, out->prim, out->normal, out->point, out->material};
-    for (int k = 0; k < 5; ++k)
-        if ((outputs & (1 << k)) && !ptr[k])
-            return fail(RT_ERR_INVALID_ARG, "NULL pointer of a requested output passed to " + name);
-    if (!inputs_ok) return fail(RT_ERR_INVALID_ARG, "NULL argument to " + name);
-    if (!ctx) return fail(RT_ERR_INVALID_ARG, "NULL context passed to " + name);
-    return RT_OK;
-}
-
-static ChOut closest_outputs(int outputs, const rt_closest_out& o) {
-    return ChOut{(outputs & RT_CH_T) ? static_cast<double*>(o.t) : nullptr,
-                 (outputs & RT_CH_PRIM) ? static_cast<int32_t*>(o.prim) : nullptr,
-                 (outputs & RT_CH_NORMAL) ? static_cast<double*>(o.normal) : nullptr,
-                 (outputs & RT_CH_POINT) ? static_cast<double*>(o.point) : nullptr,
-                 (outputs & RT_CH_MATERIAL) ? static_cast<double*>(o.material) : nullptr};
-}
-
-rt_status rt_closest_rays_device(rt_context* ctx, const rt_scene* sc, const rt_render_opts* opts,
-                                 const void* d_rays, size_t n, int outputs,
-                                 const struct rt_closest_out* d_out) {
-    rt_status st = check_closest_args(ctx, outputs, d_out, !n || d_rays, "rt_closest_rays_device");
-    if (st != RT_OK) return st;
-    if (n == 0) return RT_OK;
-    DeviceGuard g(ctx->device);
-    TraceParams p;
-    st = occluded_params(ctx, sc, opts, p);  // of opts only RT_FLAG_NO_BVH
-    if (st != RT_OK) return st;
-    RT_HIP(launch_closest_rays(p, static_cast<const double*>(d_rays), n,
-                               closest_outputs(outputs, *d_out), ctx->stream));
-    return RT_OK;
-}
-
-rt_status rt_closest_rays(rt_context* ctx, const rt_scene* sc, const rt_render_opts* opts,
-                          const double* rays, size_t n, int outputs,
-                          const struct rt_closest_out* out) {
-    rt_status st = check_closest_args(ctx, outputs, out, !n || rays, "rt_closest_rays");
-    if (st != RT_OK) return st;
-    if (n == 0) return RT_OK;
-    DeviceGuard g(ctx->device);
-    TraceParams p;
-    st = occluded_params(ctx, sc, opts, p);
-    if (st != RT_OK) return st;
-    // ctx->rays: n rays (6 doubles), then each requested output in bit order
-    size_t bytes = n * 6 * sizeof(double);
-    for (int k = 0; k < 5; ++k)
-        if (outputs & (1 << k)) bytes += n * kChBytes[k];
-    RT_HIP(ctx->rays.ensure(bytes));
-    char* at = static_cast<char*>(ctx->rays.ptr);
-    double* d_rays = reinterpret_cast<double*>(at);
-    at += n * 6 * sizeof(double);
-    rt_closest_out d{nullptr, nullptr, nullptr, nullptr, nullptr};
-    void** slot[5] = {&d.t, &d.prim, &d.normal, &d.point, &d.material};
-    void* const host[5] = {out->t, out->prim, out->normal, out->point, out->material};
-    for (int k = 0; k < 5; ++k)
-        if (outputs & (1 << k)) {
-            *slot[k] = at;
-            at += n * kChBytes[k];
-        }
-    RT_HIP(hipMemcpyAsync(d_rays, rays, n * 6 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    RT_HIP(launch_closest_rays(p, d_rays, n, closest_outputs(outputs, d), ctx->stream));
-    for (int k = 0; k < 5; ++k)
-        if (outputs & (1 << k))
-            RT_HIP(hipMemcpyAsync(host[k], *slot[k], n * kChBytes[k], hipMemcpyDeviceToHost,
-                                  ctx->stream));
-    RT_HIP(hipStreamSynchronize(ctx->stream));
-    return RT_OK;
-}
-
-// ---- progressive frames (rt_accumulate.hip) -------------------------------------------------
-// The argument checks of the two accumulate entries, made before the context or the scene is
-// dereferenced, then build_params with the members of opts the call reads: the kernel selection
-// (path) and the RT_ERR_UNSUPPORTED of rt_trace_rays for the scene and opts.
-static rt_status accumulate_params(rt_context* ctx, const rt_scene* sc, const rt_camera* cam,
-                                   const rt_render_opts* opts, int s0, int s1, const void* sum,
-                                   const char* entry, TraceParams& p, int& path) {
-    const std::string name(entry);
-    if (!ctx || !sc || !cam || !sum) return fail(RT_ERR_INVALID_ARG, "NULL argument to " + name);
-    if (cam->width == 0 || cam->height == 0)
-        return fail(RT_ERR_INVALID_ARG, "zero camera width or height passed to " + name);
-    if (s0 < 0 || s0 >= s1 || s1 > std::max(1, cam->aa_samples))
-        return fail(RT_ERR_INVALID_ARG, "sample range [" + std::to_string(s0) + "," +
-                                            std::to_string(s1) +
-                                            ") empty or outside [0, max(1, aa_samples)] passed to " +
-                                            name);
-    rt_render_opts o;
-    rt_render_opts_default(&o);
-    if (opts) {
-        o.max_recursion = opts->max_recursion;
-        o.bias = opts->bias;
-        o.seed = opts->seed;
-        o.row_begin = opts->row_begin;
-        o.row_end = opts->row_end;
-        o.row_block = opts->row_block;
-        o.row_cycle = opts->row_cycle;
-        o.flags = opts->flags & RT_FLAG_NO_BVH;
-    }
-    o.tonemap = RT_TONEMAP_NONE;
-    const uint32_t r1 = o.row_end ? o.row_end : cam->height;
-    if (r1 > cam->height || o.row_begin >= r1)
-        return fail(RT_ERR_INVALID_ARG, "row range [" + std::to_string(o.row_begin) + "," +
-                                            std::to_string(r1) + ") invalid for height " +
-                                            std::to_string(cam->height) + " passed to " + name);
-    if (o.row_cycle > 1 && o.row_block == 0)
-        return fail(RT_ERR_INVALID_ARG, "row_cycle > 1 without row_block >= 1 passed to " + name);
-    bool lds;
-    size_t lds_bytes;
-    uint32_t rows;
-    const rt_status st = build_params(ctx, sc, cam, &o, p, path, lds, lds_bytes, rows);
-    if (st != RT_OK) return fail(st, g_last_error + ", passed to " + name);
-    return RT_OK;
-}
-
-rt_status rt_accumulate_samples_device(rt_context* ctx, const rt_scene* sc, const rt_camera* cam,
-                                       const rt_render_opts* opts, int sample_begin,
-                                       int sample_end, void* d_sum) {
-    TraceParams p;
-    int path;
-    rt_status st = accumulate_params(ctx, sc, cam, opts, sample_begin, sample_end, d_sum,
-                                     "rt_accumulate_samples_device", p, path);
-    if (st != RT_OK) return st;
-    DeviceGuard g(ctx->device);
-    RT_HIP(launch_accumulate_samples(p, path, sample_begin, sample_end,
-                                     static_cast<double*>(d_sum), ctx->stream));
-    return RT_OK;
-}
-
-rt_status rt_accumulate_samples(rt_context* ctx, const rt_scene* sc, const rt_camera* cam,
-                                const rt_render_opts* opts, int sample_begin, int sample_end,
-                                double* sum) {
-    TraceParams p;
-    int path;
-    rt_status st = accumulate_params(ctx, sc, cam, opts, sample_begin, sample_end, sum,
-                                     "rt_accumulate_samples", p, path);
-    if (st != RT_OK) return st;
-    DeviceGuard g(ctx->device);
-    const size_t bytes = static_cast<size_t>(p.rows) * p.width * 3 * sizeof(double);
-    RT_HIP(ctx->out64.ensure(bytes));
-    double* d_sum = static_cast<double*>(ctx->out64.ptr);
-    if (sample_begin > 0)  // the sum so far; with sample_begin == 0 nothing of it is read
-        RT_HIP(hipMemcpyAsync(d_sum, sum, bytes, hipMemcpyHostToDevice, ctx->stream));
-    RT_HIP(launch_accumulate_samples(p, path, sample_begin, sample_end, d_sum, ctx->stream));
-    RT_HIP(hipMemcpyAsync(sum, d_sum, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    RT_HIP(hipStreamSynchronize(ctx->stream));
-    return RT_OK;
-}
-
-// The checks of the two resolve entries, before the context is dereferenced.
-static rt_status check_resolve_args(const rt_context* ctx, const void* sum, size_t n, int samples,
-                                    int tonemap, const void* hdr64, const void* hdr32,
-                                    const void* ldr, const char* entry) {
-    const std::string name(entry);
-    if (samples < 1)
-        return fail(RT_ERR_INVALID_ARG, "samples " + std::to_string(samples) + " < 1 passed to " + name);
-    if (tonemap < RT_TONEMAP_NONE || tonemap > RT_TONEMAP_COUNT)
-        return fail(RT_ERR_INVALID_ARG, "unknown tonemap operator passed to " + name);
-    if (!hdr64 && !hdr32 && !ldr) return fail(RT_ERR_INVALID_ARG, "no output passed to " + name);
-    if (ldr && tonemap == RT_TONEMAP_NONE)
-        return fail(RT_ERR_INVALID_ARG, "bytes requested with RT_TONEMAP_NONE from " + name);
-    if (!sum && n > 0) return fail(RT_ERR_INVALID_ARG, "NULL sum passed to " + name);
-    if (!ctx) return fail(RT_ERR_INVALID_ARG, "NULL context passed to " + name);
-    return RT_OK;
-}
-
-rt_status rt_resolve_device(rt_context* ctx, const void* d_sum, size_t n, int samples, int tonemap,
-                            void* d_hdr64, void* d_hdr32, void* d_ldr) {
-    rt_status st = check_resolve_args(ctx, d_sum, n, samples, tonemap, d_hdr64, d_hdr32, d_ldr,
-                                      "rt_resolve_device");
-    if (st != RT_OK) return st;
-    if (n == 0) return RT_OK;
-    DeviceGuard g(ctx->device);
-    RT_HIP(launch_resolve(static_cast<const double*>(d_sum), n, samples, tonemap,
-                          static_cast<double*>(d_hdr64), static_cast<float*>(d_hdr32),
-                          static_cast<uint8_t*>(d_ldr), ctx->stream));
-    return RT_OK;
-}
-
-rt_status rt_resolve(rt_context* ctx, const double* sum, size_t n, int samples, int tonemap,
-                     double* hdr64, float* hdr32, uint8_t* ldr) {
-    rt_status st = check_resolve_args(ctx, sum, n, samples, tonemap, hdr64, hdr32, ldr, "rt_resolve");
-    if (st != RT_OK) return st;
-    if (n == 0) return RT_OK;
-    DeviceGuard g(ctx->device);
-    const size_t planes = tonemap == RT_TONEMAP_COUNT ? RT_TONEMAP_COUNT : 1;
-    RT_HIP(ctx->tm_in.ensure(n * 3 * sizeof(double)));
-    if (hdr64) RT_HIP(ctx->out64.ensure(n * 3 * sizeof(double)));
-    if (hdr32) RT_HIP(ctx->out32.ensure(n * 3 * sizeof(float)));
-    if (ldr) RT_HIP(ctx->tm_out.ensure(planes * n * 3));
-    RT_HIP(hipMemcpyAsync(ctx->tm_in.ptr, sum, n * 3 * sizeof(double), hipMemcpyHostToDevice,
-                          ctx->stream));
-    RT_HIP(launch_resolve(static_cast<const double*>(ctx->tm_in.ptr), n, samples, tonemap,
-                          hdr64 ? static_cast<double*>(ctx->out64.ptr) : nullptr,
-                          hdr32 ? static_cast<float*>(ctx->out32.ptr) : nullptr,
-                          ldr ? static_cast<uint8_t*>(ctx->tm_out.ptr) : nullptr, ctx->stream));
-    if (hdr64)
-        RT_HIP(hipMemcpyAsync(hdr64, ctx->out64.ptr, n * 3 * sizeof(double), hipMemcpyDeviceToHost,
-                              ctx->stream));
-    if (hdr32)
-        RT_HIP(hipMemcpyAsync(hdr32, ctx->out32.ptr, n * 3 * sizeof(float), hipMemcpyDeviceToHost,
-                              ctx->stream));
-    if (ldr)
-        RT_HIP(hipMemcpyAsync(ldr, ctx->tm_out.ptr, planes * n * 3, hipMemcpyDeviceToHost,
-                              ctx->stream));
-    RT_HIP(hipStreamSynchronize(ctx->stream));
-    return RT_OK;
-}
-
-rt_status rt_tonemap(rt_context* ctx, const double* hdr, size_t n, int op, uint8_t* out) {
-    if (!ctx || (!hdr && n) || (!out && n))
-        return fail(RT_ERR_INVALID_ARG, "NULL argument to rt_tonemap");
-    if (op < 0 || op > RT_TONEMAP_COUNT) return fail(RT_ERR_INVALID_ARG, "tonemap op out of range");
-    if (n == 0) return RT_OK;
-    DeviceGuard g(ctx->device);
-    const size_t planes = op == RT_TONEMAP_COUNT ? RT_TONEMAP_COUNT : 1;
-    RT_HIP(ctx->tm_in.ensure(n * 3 * sizeof(double)));
-    RT_HIP(ctx->tm_out.ensure(planes * n * 3));
-    RT_HIP(hipMemcpyAsync(ctx->tm_in.ptr, hdr, n * 3 * sizeof(double), hipMemcpyHostToDevice,
-                          ctx->stream));
-    RT_HIP(launch_tonemap(static_cast<const double*>(ctx->tm_in.ptr), n, op,
-                          static_cast<uint8_t*>(ctx->tm_out.ptr), ctx->stream));
-    RT_HIP(hipMemcpyAsync(out, ctx->tm_out.ptr, planes * n * 3, hipMemcpyDeviceToHost,
-                          ctx->stream));
-    RT_HIP(hipStreamSynchronize(ctx->stream));
     return RT_OK;
 }
 

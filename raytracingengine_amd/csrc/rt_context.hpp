@@ -1,5 +1,6 @@
 // rt_context.hpp — the C-ABI objects (rt_context, rt_scene) and the helpers the C-ABI
-// translation units share (rt_capi.cpp: single device; rt_multi.cpp: RCCL multi-GPU frames).
+// translation units share (rt_capi.cpp: single device; rt_capi_queries.cpp: the batch queries;
+// rt_multi.cpp: RCCL multi-GPU frames).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -22,6 +23,13 @@ rt_status hip_fail(hipError_t e, const char* what);
     do {                                                \
         hipError_t e_ = (call);                         \
         if (e_ != hipSuccess) return rtamd::hip_fail(e_, #call); \
+    } while (0)
+
+// Returns a failed rt_status of `call` to the caller (its message is already set).
+#define RT_TRY(call)                    \
+    do {                                \
+        rt_status s_ = (call);          \
+        if (s_ != RT_OK) return s_;     \
     } while (0)
 
 struct DeviceBuffer {
@@ -203,6 +211,13 @@ rt_status enqueue_frames(rt_context* ctx, const rt_scene* sc, const rt_camera* c
                          const rt_render_opts* opts, double* d64, float* d32, uint8_t* dldr,
                          uint32_t frame_rows = 0);
 rt_status check_batch(const rt_camera* cams, int nframes);
+// The launch parameters of a render or a query (rt_capi_queries.cpp) of `sc` from `cam` with opts
+// (NULL: the defaults), after checking all three: p, the TraceRay shape the scene can produce
+// (path: kPathDirect / kPathChain / kPathTree), whether the scene's records fit the context's LDS
+// budget and their bytes, and the rows the row set of opts selects.
+rt_status build_params(rt_context* ctx, const rt_scene* sc, const rt_camera* cam,
+                       const rt_render_opts* opts_in, TraceParams& p, int& path, bool& lds,
+                       size_t& lds_bytes, uint32_t& rows);
 // rt_packet_host.cpp, for enqueue_frames before a packet launch.  One frame: p.pk_image from the
 // scene's cache of camera images, a setup launch on a camera's second sighting, or a publish
 // slot (p.pk_pub); a batch: p.fr[f] for every frame and *batch_ring = the ring entry its formed
