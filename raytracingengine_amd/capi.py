@@ -540,41 +540,34 @@ class Context:
                                            max_rows, out.ctypes.data))
         return out
 
+    def _debug_counter(self, entry) -> tuple[int, int]:
+        a, b = ctypes.c_uint64(), ctypes.c_uint64()
+        _check(entry(self._h, ctypes.byref(a), ctypes.byref(b)))
+        return a.value, b.value
+
     def debug_cone_table(self) -> tuple[int, int]:
         """Packet-kernel frames enqueued so far (with, without) a camera-cone table."""
-        a, b = ctypes.c_uint64(), ctypes.c_uint64()
-        _check(_lib.rt_debug_cone_table(self._h, ctypes.byref(a), ctypes.byref(b)))
-        return a.value, b.value
+        return self._debug_counter(_lib.rt_debug_cone_table)
 
     def debug_shadow_table(self) -> tuple[int, int]:
         """Packet-kernel frames enqueued so far (with, without) a shadow-cull table."""
-        a, b = ctypes.c_uint64(), ctypes.c_uint64()
-        _check(_lib.rt_debug_shadow_table(self._h, ctypes.byref(a), ctypes.byref(b)))
-        return a.value, b.value
+        return self._debug_counter(_lib.rt_debug_shadow_table)
 
     def debug_tile_class(self) -> tuple[int, int]:
         """Packet-kernel frames enqueued so far (with, without) tile class words."""
-        a, b = ctypes.c_uint64(), ctypes.c_uint64()
-        _check(_lib.rt_debug_tile_class(self._h, ctypes.byref(a), ctypes.byref(b)))
-        return a.value, b.value
+        return self._debug_counter(_lib.rt_debug_tile_class)
 
     def debug_plane_clear(self) -> tuple[int, int]:
         """Packet-kernel frames enqueued so far (with, without) shadow-plane keep masks."""
-        a, b = ctypes.c_uint64(), ctypes.c_uint64()
-        _check(_lib.rt_debug_plane_clear(self._h, ctypes.byref(a), ctypes.byref(b)))
-        return a.value, b.value
+        return self._debug_counter(_lib.rt_debug_plane_clear)
 
     def debug_tile_split(self) -> tuple[int, int]:
         """Fix-up variant frames enqueued so far (as a split launch, as a single launch)."""
-        a, b = ctypes.c_uint64(), ctypes.c_uint64()
-        _check(_lib.rt_debug_tile_split(self._h, ctypes.byref(a), ctypes.byref(b)))
-        return a.value, b.value
+        return self._debug_counter(_lib.rt_debug_tile_split)
 
     def debug_tile_shadowed(self) -> tuple[int, int]:
         """Fix-up variant frames enqueued so far (with, without) a launch over shadowed tiles."""
-        a, b = ctypes.c_uint64(), ctypes.c_uint64()
-        _check(_lib.rt_debug_tile_shadowed(self._h, ctypes.byref(a), ctypes.byref(b)))
-        return a.value, b.value
+        return self._debug_counter(_lib.rt_debug_tile_shadowed)
 
     def debug_fixup_count(self) -> int:
         """Pixels the last fix-up variant launch of this context queued for its fix-up launch."""

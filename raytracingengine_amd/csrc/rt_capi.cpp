@@ -273,6 +273,27 @@ rt_status enqueue_render(rt_context* ctx, const rt_scene* sc, const rt_camera* c
     return enqueue_frames(ctx, sc, cam, 1, opts, d64, d32, dldr);
 }
 
+// The rt_debug_* frame counters of one packet launch: what each of its frames was handed (its
+// table pointers; one frame: the launch's own) and, for the fix-up variant, how it is launched.
+static void count_packet_frames(rt_context* ctx, const TraceParams& p, int nframes, bool fixup,
+                                const PkSplit& split) {
+    auto count = [&](rt_context::PkCounter c, bool with, uint64_t n) {
+        ctx->pk_frames[c][with ? 0 : 1] += n;
+    };
+    for (int f = 0; f < nframes; ++f) {
+        const bool cone = (nframes > 1 ? p.fr_tab[f] : p.cone_tab) != nullptr;
+        const bool shadow = (nframes > 1 ? p.fr_stab[f] : p.shadow_tab) != nullptr;
+        const bool cls = (nframes > 1 ? p.fr_ctab[f] : p.class_tab) != nullptr;
+        count(rt_context::kCntConeTable, cone, 1);
+        count(rt_context::kCntShadowTable, shadow, 1);
+        count(rt_context::kCntTileClass, cls, 1);
+        count(rt_context::kCntPlaneClear, cls && p.plane_masks, 1);
+    }
+    if (!fixup) return;
+    count(rt_context::kCntTileSplit, split.tiles != 0, static_cast<uint64_t>(nframes));
+    count(rt_context::kCntTileShadowed, split.tiles && split.sh_n, static_cast<uint64_t>(nframes));
+}
+
 rt_status enqueue_frames(rt_context* ctx, const rt_scene* sc, const rt_camera* cams, int nframes,
                          const rt_render_opts* opts, double* d64, float* d32, uint8_t* dldr,
                          uint32_t frame_rows) {
@@ -342,21 +363,6 @@ rt_status enqueue_frames(rt_context* ctx, const rt_scene* sc, const rt_camera* c
         st = packet_image(ctx, sc, p, flags, &rec);
         if (st != RT_OK) return st;
     }
-    if (packet) {  // rt_debug_cone_table: which frames read their camera-cone mask from a table
-        for (int f = 0; f < nframes; ++f)
-            ++((nframes > 1 ? p.fr_tab[f] : p.cone_tab) ? ctx->cone_tab_frames
-                                                         : ctx->cone_notab_frames);
-        for (int f = 0; f < nframes; ++f)  // rt_debug_shadow_table
-            ++((nframes > 1 ? p.fr_stab[f] : p.shadow_tab) ? ctx->shadow_tab_frames
-                                                            : ctx->shadow_notab_frames);
-        for (int f = 0; f < nframes; ++f)  // rt_debug_tile_class
-            ++((nframes > 1 ? p.fr_ctab[f] : p.class_tab) ? ctx->tile_class_frames
-                                                          : ctx->tile_noclass_frames);
-        for (int f = 0; f < nframes; ++f)  // rt_debug_plane_clear
-            ++(((nframes > 1 ? p.fr_ctab[f] : p.class_tab) && p.plane_masks)
-                   ? ctx->plane_mask_frames
-                   : ctx->plane_nomask_frames);
-    }
     // the fix-up variant of the packet kernel (undecided shadow rays re-rendered per pixel after
     // the launch) uses the context's fix-up list: ordered across streams like the counters
     const bool fixup = packet && packet_uses_fixup(p, false, sc->max_specular > 0.0);
@@ -374,11 +380,7 @@ rt_status enqueue_frames(rt_context* ctx, const rt_scene* sc, const rt_camera* c
     // batch has its tile lists (packet_batch_images formed none under a tile order), and the two
     // launches go onto the render's stream one after the other
     if (!fixup || p.tile_order) pk_split.tiles = 0;
-    if (packet && fixup)
-        (pk_split.tiles ? ctx->tile_split_frames : ctx->tile_nosplit_frames) += nframes;
-    if (packet && fixup)  // rt_debug_tile_shadowed: the split launch's third kernel
-        ((pk_split.tiles && pk_split.sh_n) ? ctx->tile_shadowed_frames
-                                           : ctx->tile_noshadowed_frames) += nframes;
+    if (packet) count_packet_frames(ctx, p, nframes, fixup, pk_split);
     // generic kernels without triangle / area-light code for scenes that use neither
     const bool lean_generic = p.nt == 0 && p.al_samples == 0;
     // reflection chains of scenes made of planes (and up to kBoxMaxSpheres spheres) take the
@@ -1049,52 +1051,37 @@ rt_status rt_debug_tile_order(rt_context* ctx, const rt_scene* sc, const rt_came
     return RT_OK;
 }
 
-rt_status rt_debug_cone_table(rt_context* ctx, uint64_t* with_table, uint64_t* without_table) {
-    if (!ctx || !with_table || !without_table)
-        return fail(RT_ERR_INVALID_ARG, "NULL argument to rt_debug_cone_table");
-    *with_table = ctx->cone_tab_frames;
-    *without_table = ctx->cone_notab_frames;
+static rt_status debug_counter(rt_context* ctx, rt_context::PkCounter c, uint64_t* with,
+                               uint64_t* without, const char* entry) {
+    if (!ctx || !with || !without)
+        return fail(RT_ERR_INVALID_ARG, std::string("NULL argument to ") + entry);
+    *with = ctx->pk_frames[c][0];
+    *without = ctx->pk_frames[c][1];
     return RT_OK;
+}
+
+rt_status rt_debug_cone_table(rt_context* ctx, uint64_t* with_table, uint64_t* without_table) {
+    return debug_counter(ctx, rt_context::kCntConeTable, with_table, without_table, __func__);
 }
 
 rt_status rt_debug_shadow_table(rt_context* ctx, uint64_t* with_table, uint64_t* without_table) {
-    if (!ctx || !with_table || !without_table)
-        return fail(RT_ERR_INVALID_ARG, "NULL argument to rt_debug_shadow_table");
-    *with_table = ctx->shadow_tab_frames;
-    *without_table = ctx->shadow_notab_frames;
-    return RT_OK;
+    return debug_counter(ctx, rt_context::kCntShadowTable, with_table, without_table, __func__);
 }
 
 rt_status rt_debug_tile_class(rt_context* ctx, uint64_t* with_words, uint64_t* without_words) {
-    if (!ctx || !with_words || !without_words)
-        return fail(RT_ERR_INVALID_ARG, "NULL argument to rt_debug_tile_class");
-    *with_words = ctx->tile_class_frames;
-    *without_words = ctx->tile_noclass_frames;
-    return RT_OK;
+    return debug_counter(ctx, rt_context::kCntTileClass, with_words, without_words, __func__);
 }
 
 rt_status rt_debug_plane_clear(rt_context* ctx, uint64_t* with_masks, uint64_t* without_masks) {
-    if (!ctx || !with_masks || !without_masks)
-        return fail(RT_ERR_INVALID_ARG, "NULL argument to rt_debug_plane_clear");
-    *with_masks = ctx->plane_mask_frames;
-    *without_masks = ctx->plane_nomask_frames;
-    return RT_OK;
+    return debug_counter(ctx, rt_context::kCntPlaneClear, with_masks, without_masks, __func__);
 }
 
 rt_status rt_debug_tile_split(rt_context* ctx, uint64_t* split, uint64_t* single) {
-    if (!ctx || !split || !single)
-        return fail(RT_ERR_INVALID_ARG, "NULL argument to rt_debug_tile_split");
-    *split = ctx->tile_split_frames;
-    *single = ctx->tile_nosplit_frames;
-    return RT_OK;
+    return debug_counter(ctx, rt_context::kCntTileSplit, split, single, __func__);
 }
 
 rt_status rt_debug_tile_shadowed(rt_context* ctx, uint64_t* with, uint64_t* without) {
-    if (!ctx || !with || !without)
-        return fail(RT_ERR_INVALID_ARG, "NULL argument to rt_debug_tile_shadowed");
-    *with = ctx->tile_shadowed_frames;
-    *without = ctx->tile_noshadowed_frames;
-    return RT_OK;
+    return debug_counter(ctx, rt_context::kCntTileShadowed, with, without, __func__);
 }
 
 rt_status rt_debug_fixup_count(rt_context* ctx, uint32_t* pixels) {

@@ -88,18 +88,18 @@ struct rt_context {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> free_events;
     double timed_ms = 0.0;
     uint64_t launches = 0;
-    // packet-kernel frames enqueued with / without a camera-cone table (rt_debug_cone_table)
-    uint64_t cone_tab_frames = 0, cone_notab_frames = 0;
-    // ... and with / without a shadow-cull table (rt_debug_shadow_table)
-    uint64_t shadow_tab_frames = 0, shadow_notab_frames = 0;
-    // ... and with / without tile class words (rt_debug_tile_class)
-    uint64_t tile_class_frames = 0, tile_noclass_frames = 0;
-    // ... and with class words that carry shadow-plane keep masks / without (rt_debug_plane_clear)
-    uint64_t plane_mask_frames = 0, plane_nomask_frames = 0;
-    // ... and through the fix-up variant's split launch / its single launch (rt_debug_tile_split)
-    uint64_t tile_split_frames = 0, tile_nosplit_frames = 0;
-    // ... and with / without a launch over a list of shadowed-plane tiles (rt_debug_tile_shadowed)
-    uint64_t tile_shadowed_frames = 0, tile_noshadowed_frames = 0;
+    // packet-kernel frames enqueued {with, without} each thing the rt_debug_* entry of the same
+    // name reports (rt_capi.cpp count_packet_frames)
+    enum PkCounter {
+        kCntConeTable,     // a camera-cone table
+        kCntShadowTable,   // a shadow-cull table
+        kCntTileClass,     // tile class words
+        kCntPlaneClear,    // class words that carry shadow-plane keep masks
+        kCntTileSplit,     // fix-up variant frames: the split launch / its single launch
+        kCntTileShadowed,  // ... with / without a launch over a list of shadowed-plane tiles
+        kPkCounters
+    };
+    uint64_t pk_frames[kPkCounters][2] = {};
     // rt_render_multi: RCCL communicators over the devices of the last context list this
     // context led (rt_multi.cpp); destroyed with the context
     std::vector<rt_context*> group_ctxs;
@@ -156,8 +156,8 @@ struct rt_scene {
         // packet_cone_table_kernel on the stream of the render that created it, never rewritten;
         // renders on other streams wait for `ready` until it has completed.  Dropped with the
         // image entry.  The buffer also holds the shadow-cull words formed from the cone masks
-        // (rt_shadow_table.hpp), after them: nl per tile when the scene gets any, and then the
-        // tile class words, one per tile, when the key says so.
+        // (rt_shadow_table.hpp) and whatever else the key's contents word names: the layout is
+        // rt_tile_table.hpp's.
         struct ConeTab {
             static constexpr size_t kKeyWords = 20;
             uint32_t key[kKeyWords] = {};
@@ -166,9 +166,7 @@ struct rt_scene {
             hipStream_t stream = nullptr;
             bool done = false;
             // with tile lists (the key says so): two pinned host words the launch that forms the
-            // table fills with the lists' counts, each plus one — uniform tiles in the first
-            // word's low half, general workgroups in its high half, shadowed-plane tiles in the
-            // second word; 0: not formed yet
+            // table fills with the lists' counts (tile_list_counts_encode; 0: not formed yet)
             unsigned long long* counts = nullptr;
         };
         std::vector<ConeTab> tabs;

@@ -5,7 +5,10 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <cstdlib>
 #include <vector>
+
+#include "rt_tile_table.hpp"
 
 namespace rtamd {
 
@@ -135,19 +138,20 @@ struct TraceParams {
     // packet kernel, single-sample variants of up to 64 spheres: the camera-cone candidate mask
     // of every wave tile (rt_cone_table.hpp), one 64-bit word per tile at
     // (tby · gx + tbx) · waves + wave, formed by packet_cone_table_kernel before the launch; null:
-    // the wave forms its own.  fr_tab[f]: frame f's of a batch (after fr_dz, as fr_dz after fr[])
+    // the wave forms its own.  fr_tab[f]: frame f's of a batch (after fr_dz, as fr_dz after fr[]).
+    // These three pointer sets point into one tile table each: rt_tile_table.hpp has its layout
     const unsigned long long* cone_tab;
     const unsigned long long* fr_tab[kPkMaxBatch];
     // the same variants: the shadow-cull candidate masks of every wave tile (rt_shadow_table.hpp),
-    // nl 64-bit words per tile at ((tby · gx + tbx) · waves + wave) · nl + light, formed by the
-    // same launch into the same buffer after the cone table's words; a word of all ones or a null
-    // pointer: the wave forms its own mask (origin_ball + cull_capsule).  fr_stab[f]: frame f's
+    // nl 64-bit words per tile at ((tby · gx + tbx) · waves + wave) · nl + light; a word of all
+    // ones or a null pointer: the wave forms its own mask (origin_ball + cull_capsule).
+    // fr_stab[f]: frame f's
     const unsigned long long* shadow_tab;
     const unsigned long long* fr_stab[kPkMaxBatch];
     // the fix-up variant of those: the class word of every wave tile (tile_class_word,
-    // rt_shadow_table.hpp), one per tile at (tby · gx + tbx) · waves + wave in the same buffer
-    // after the shadow words — 0: the general path, else the tile sees only sky or only one
-    // plane and casts no shadow ray a sphere can meet (pk_uniform_tile).  The class is the
+    // rt_shadow_table.hpp), one per tile at (tby · gx + tbx) · waves + wave — 0: the general
+    // path, else the tile sees only sky or only one plane and casts no shadow ray a sphere can
+    // meet (pk_uniform_tile).  The class is the
     // word's bits 0-7; bits 8 + 8·l … 15 + 8·l hold light l's shadow-plane keep mask
     // (shadow_plane_keep; all ones: every plane is classified), on general tiles too, so readers
     // test tile_class_of(word).  Null: no tile is classified.  fr_ctab[f]: frame f's
@@ -156,7 +160,7 @@ struct TraceParams {
 };
 // The fix-up variant's split launch of a frame batch (packet_uniform_kernel and
 // packet_direct_kernel's kFeatSplit twin, rt_packet.hip): every frame's class words are followed
-// by its tile lists (rt_shadow_table.hpp), at fr_ctab[f] + tiles; tiles == 0: no lists, one
+// by its tile lists (rt_tile_table.hpp, TileTabLayout::Lists); tiles == 0: no lists, one
 // launch as before.  uni_n and gen_n: the uniform tiles and general workgroups the two launches
 // cover per frame — the largest count of the batch's frames where the host knows them, every
 // tile or workgroup where it does not.  sh_n: the same for the shadowed-plane tiles
@@ -230,33 +234,29 @@ struct PkImageJobs {
 };
 hipError_t launch_packet_image_batch(const TraceParams& p, const PkImageJobs& jobs,
                                      hipStream_t stream);
-// The camera-cone tables (TraceParams.cone_tab / fr_tab) one launch forms: job j writes the
-// table of frame frame[j] (-1: the one-frame launch's camera, p.cam_pos / p.pk_image) to dst[j],
-// reading the frame's packet image, formed earlier on the stream.
+// The tile tables (rt_tile_table.hpp) one launch forms: job j writes the table of frame frame[j]
+// (-1: the one-frame launch's camera, p.cam_pos / p.pk_image) to dst[j], reading the frame's
+// packet image, formed earlier on the stream; every job's table holds `contents`.
 struct PkConeJobs {
     unsigned long long* dst[kPkMaxBatch];
     int32_t frame[kPkMaxBatch];
     int32_t n;
-    // > 0: the shadow-cull words too (rt_shadow_table.hpp), shadow_nl per tile, written after
-    // the job's cone words: dst[j] + tiles
-    int32_t shadow_nl;
-    // != 0 (with shadow_nl > 0 only): the tile class words too, one per tile after the shadow
-    // words: dst[j] + tiles · (1 + shadow_nl); 2: with the shadow-plane keep masks formed
-    // (shadow_plane_keep), 1: with all-ones masks
-    int32_t class_words;
-    // != 0 (with class_words only): the tile lists too, after the class words:
-    // dst[j] + tiles · (2 + shadow_nl), tile_list_words(tiles, workgroups) words; 2: with the
-    // shadowed-plane tiles marked in their class words and filed in the third list
-    int32_t lists;
+    TileTabContents contents;
 };
-// host[j], when set, points at two pinned host words that receive job j's three list counts once
-// the table is formed: uniform tiles in the first word's low half, general workgroups in its high
-// half, shadowed tiles in the second word, each plus one (0: not yet)
+// host[j], when set, points at the two pinned host words that receive job j's list counts once
+// the table is formed (tile_list_counts_encode)
 struct PkListCounts {
     unsigned long long* host[kPkMaxBatch];
 };
 hipError_t launch_packet_cone_tables(const TraceParams& p, const PkConeJobs& jobs,
                                      hipStream_t stream, const PkListCounts* counts = nullptr);
+// An RTAMD_PK_* switch as set now (-1: unset), and whether it is set to 0 — "off"; read per
+// launch: the tests flip the switches between launches.
+inline int packet_switch(const char* name) {
+    const char* e = std::getenv(name);
+    return e ? std::atoi(e) : -1;
+}
+inline bool packet_switch_off(const char* name) { return packet_switch(name) == 0; }
 // Whether a launch of p may take the split launch at all (RTAMD_PK_TILE_SPLIT, read per launch,
 // a tile grid whose columns and rows a list entry can name, one wave row per workgroup and no
 // tile order: an order names dispatch positions, a list tiles), and the two launches

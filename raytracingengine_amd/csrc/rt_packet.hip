@@ -46,23 +46,17 @@ hipError_t launch_packet_image_batch(const TraceParams& p, const PkImageJobs& jo
     return hipGetLastError();
 }
 
-// The camera-cone candidate masks of a launch's wave tiles (rt_cone_table.hpp), one lane per
-// tile and one grid row per job: a one-frame launch's camera, or every frame of a batch that
-// has no cached table.  The per-sphere terms are the packet image's (cone_terms), formed
-// earlier on the stream.  Tables are indexed by tile — (tby · gx + tbx) · waves + wave — not by
-// dispatch position: the tile order permutes dispatch, not tiles.
-// With J.shadow_nl > 0 the same lane goes on to the tile's shadow-cull words
-// (rt_shadow_table.hpp), which depend on the cone mask it just formed: nl words per tile after
-// the job's cone words, so a batch of new cameras pays no launch of its own for them.
-// With J.class_words the lane closes with the tile's class word (tile_class_word), one per tile
-// after the shadow words: which tiles the fix-up variant renders on its uniform path, and which
-// planes each light's shadow rays of the tile must still classify (bits 8 and up).
-// With J.lists the lane also files its tile in the frame's tile lists (rt_shadow_table.hpp), after
-// the class words: a wavefront is one run of list positions (position i stands for tile
-// tiles − 1 − i), compacted with three ballots (uniform tiles, general tiles, listed workgroups'
-// first lanes) and given its place in each list by one atomic add per wavefront — tile_list_run
-// is the same run in plain C++, and the helpers that decide are shared with it;
-// the counts were zeroed by packet_list_zero_kernel before this launch.
+// The tile tables (rt_tile_table.hpp: the sections, their order and what each is formed from) of
+// a launch's wave tiles, one lane per tile and one grid row per job: a one-frame launch's camera,
+// or every frame of a batch that has no cached table, so a batch of new cameras pays one launch.
+// The per-sphere terms are the packet image's (cone_terms), formed earlier on the stream.  The
+// lane writes the sections J.contents names, in their order, and returns after the last.
+// Tables are indexed by tile — (tby · gx + tbx) · waves + wave — not by dispatch position: the
+// tile order permutes dispatch, not tiles.  With lists the lanes take the tiles from the last one
+// down, and a wavefront is one run of list positions (tile_list_run, rt_shadow_table.hpp, is the
+// same run in plain C++ and shares the helpers that decide): compacted with three ballots
+// (uniform tiles, shadowed tiles, listed workgroups' first lanes) and given its place in each
+// list by one atomic add per wavefront on the counts packet_list_zero_kernel zeroed before.
 // The kernel waits more than it issues (dependent FP64 chains, one lane per tile), so it is
 // built for 5 waves per SIMD (96 VGPRs, 104 B of scratch; by itself it compiles to 3): the
 // measured times are in DESIGN §4 and profiles/shadow_table_pmc.txt.
@@ -80,14 +74,15 @@ __global__ __launch_bounds__(kConeThreads, 5) void packet_cone_table_kernel(Trac
     const int ns = P.ns < 64 ? P.ns : 64;  // (the launcher checked P.ns <= 64)
     for (int i = threadIdx.x; i < 8 * ns; i += kConeThreads)
         s_terms[i] = reinterpret_cast<const float*>(img + kPkSph * (i >> 3) + 4)[i & 7];
-    if (J.shadow_nl > 0)
+    const TileTabContents C = J.contents;
+    if (C.has_shadow())
         for (int i = threadIdx.x; i < 3 * ns; i += kConeThreads)
             s_ctr[i] = img[kPkSph * (i / 3) + i % 3];
     __syncthreads();
     const uint32_t pos = blockIdx.x * kConeThreads + threadIdx.x;
     if (pos >= gx * gy * waves) return;
     // (every tile has one lane; with lists the lanes take the tiles from the last one down)
-    const uint32_t t = J.lists ? tile_list_tile(pos, gx * gy * waves) : pos;
+    const uint32_t t = C.has_lists() ? tile_list_tile(pos, gx * gy * waves) : pos;
     const uint32_t wave = t % waves, wg = t / waves, tbx = wg % gx, tby = wg / gx;
     const uint32_t x0 = tbx * (kPkW * kWgWavesX) + (wave % kWgWavesX) * kPkW;
     const uint32_t yl0 = tby * (kPkH * (waves / kWgWavesX)) + (wave / kWgWavesX) * kPkH;
@@ -95,48 +90,49 @@ __global__ __launch_bounds__(kConeThreads, 5) void packet_cone_table_kernel(Trac
     const ConeRect q = cone_tile_rect(x0, yl0, P.width, rp);
     const ConeBound B = cone_tile_bound(q, P.half_w, P.half_h, camp[0], camp[1], dz);
     const uint64_t cone = cone_tile_mask(B, s_terms, 8, ns);
-    J.dst[blockIdx.y][t] = cone;
-    if (J.shadow_nl <= 0) return;
+    const TileTabLayout L{static_cast<size_t>(gx) * gy * waves, static_cast<size_t>(gx) * gy, C};
+    unsigned long long* tab = J.dst[blockIdx.y];
+    tab[L.cone(t)] = cone;
+    if (!C.has_shadow()) return;
     // (the launcher checked shadow_nl == P.nl <= kShadowTabLights, P.np <= 2 and ns <= 63: no
     // chunk bounds, so the image's planes follow its ns sphere records)
-    unsigned long long* sw = J.dst[blockIdx.y] + static_cast<size_t>(gx) * gy * waves +
-                             static_cast<size_t>(t) * J.shadow_nl;
+    unsigned long long* sw = tab + L.shadow(t, 0);
     // (two planes at most: scenes of three or more take the plane-culling variant, no table)
     ShadowBound<2> SB;
     SB.n = 0;
     SB.ok = false;
     if (cone == 0)
         SB = shadow_tile_bound<2>(q, P.half_w, P.half_h, camp, dz, img + kPkSph * ns, P.np, P.bias);
-    // (with J.class_words == 2 each light's shadow-plane keep mask too, shadow_plane_keep: it
-    // rides in the class word, tile_class_pack; 1: all ones, nothing is taken as proven)
+    // (each light's shadow-plane keep mask too when the class words carry them, shadow_plane_keep:
+    // it rides in the class word, tile_class_pack; else all ones, nothing is taken as proven)
     unsigned long long any = 0, keep = 0;
-    for (int l = 0; l < J.shadow_nl; ++l) {
+    for (int l = 0; l < C.shadow_nl; ++l) {
         sw[l] = shadow_tile_word(SB, P.lt + kLtStride * l, P.bias, s_ctr, 3, s_terms + 7, 8, ns);
         any |= sw[l];
-        const unsigned k = J.class_words == 2
+        const unsigned k = C.forms_keep()
                                ? shadow_plane_keep<2>(SB, P.lt + kLtStride * l, img + kPkSph * ns,
                                                       P.np, camp, P.bias)
                                : kPlaneKeepAll;
         keep |= static_cast<unsigned long long>(k) << (8 + 8 * l);
     }
-    if (J.class_words == 0) return;
+    if (!C.has_class()) return;
     // the tile's class word (tile_class_word), after every tile's shadow words; s_pln of the
     // image follows its planes and lights (pk_build_image).  The OR of the tile's shadow words
     // stands for them (zero iff every one is; the launcher checked shadow_nl <= kShadowTabLights)
     const double* pln = img + kPkSph * ns + kPlStride * P.np + kLtStride * P.nl;
-    // (J.lists == 2: the shadowed-plane mark too, tile_shadowed_mark.  `any` stands for the words
-    // here as well: a real word has no bit 63, so their OR is all ones iff one of them is)
+    // (with the third list: the shadowed-plane mark too, tile_shadowed_mark.  `any` stands for
+    // the words here as well: a real word has no bit 63, so their OR is all ones iff one is)
     const unsigned long long mark =
-        J.lists == 2 ? tile_shadowed_mark(cone, SB, &any, 1, pln, P.np) : 0ull;
+        C.forms_mark() ? tile_shadowed_mark(cone, SB, &any, 1, pln, P.np) : 0ull;
     const unsigned long long cw = tile_class_word(cone, SB, &any, 1, pln, P.np) | keep | mark;
-    J.dst[blockIdx.y][static_cast<size_t>(gx) * gy * waves * (1 + J.shadow_nl) + t] = cw;
-    if (!J.lists) return;
+    tab[L.cls(t)] = cw;
+    if (!C.has_lists()) return;
     // the tile lists: the active lanes of this wavefront are a run's first lanes (lane 0 among
     // them), and a workgroup's tiles are `waves` adjacent lanes
-    const size_t tiles = static_cast<size_t>(gx) * gy * waves;
-    unsigned long long* hdr = J.dst[blockIdx.y] + tiles * (2 + J.shadow_nl);
-    unsigned long long* uni = hdr + 1;
-    uint32_t* gen = reinterpret_cast<uint32_t*>(hdr + 1 + tiles);
+    // (the counts word's halves: TileListCounts)
+    uint32_t* n_ug = reinterpret_cast<uint32_t*>(tab + L.list_counts());
+    unsigned long long* uni = tab + L.uniform(0);
+    uint32_t* gen = reinterpret_cast<uint32_t*>(tab + L.general_base());
     const uint32_t lane = threadIdx.x & 63u;
     const bool is_uni = tile_list_uniform(cw), is_sh = tile_list_shadowed(cw);
     const uint64_t bu = __ballot(is_uni), bs = __ballot(is_sh), bg = __ballot(!is_uni && !is_sh);
@@ -144,13 +140,10 @@ __global__ __launch_bounds__(kConeThreads, 5) void packet_cone_table_kernel(Trac
     const uint64_t bl = __ballot(lead);
     uint32_t base_u = 0, base_g = 0, base_s = 0;
     if (lane == 0) {
-        if (bu) base_u = atomicAdd(reinterpret_cast<uint32_t*>(hdr),
-                                   static_cast<uint32_t>(__builtin_popcountll(bu)));
-        if (bl) base_g = atomicAdd(reinterpret_cast<uint32_t*>(hdr) + 1,
-                                   static_cast<uint32_t>(__builtin_popcountll(bl)));
+        if (bu) base_u = atomicAdd(n_ug, static_cast<uint32_t>(__builtin_popcountll(bu)));
+        if (bl) base_g = atomicAdd(n_ug + 1, static_cast<uint32_t>(__builtin_popcountll(bl)));
         if (bs)
-            base_s = atomicAdd(reinterpret_cast<uint32_t*>(
-                                   hdr + tile_list_shadowed_count(tiles, static_cast<size_t>(gx) * gy)),
+            base_s = atomicAdd(reinterpret_cast<uint32_t*>(tab + L.shadowed_count()),
                                static_cast<uint32_t>(__builtin_popcountll(bs)));
     }
     base_u = __shfl(base_u, 0, 64);
@@ -159,30 +152,27 @@ __global__ __launch_bounds__(kConeThreads, 5) void packet_cone_table_kernel(Trac
     const uint64_t below = (1ull << lane) - 1ull;
     if (is_uni) uni[base_u + __builtin_popcountll(bu & below)] = tile_list_entry(cw, x0, yl0);
     if (is_sh)
-        uni[tile_list_shadowed_slot(base_s + __builtin_popcountll(bs & below),
-                                    static_cast<uint32_t>(tiles))] = tile_shadowed_entry(cw, x0, yl0);
+        uni[TileTabLayout::shadowed_slot(base_s + __builtin_popcountll(bs & below),
+                                         static_cast<uint32_t>(L.tiles))] =
+            tile_shadowed_entry(cw, x0, yl0);
     if (lead) gen[base_g + __builtin_popcountll(bl & below)] = wg;
 }
 
 // The list counts of a table launch's jobs: zeroed before it, and handed to the host after it
-// (each plus one in a pinned word, so 0 says "not yet") where the table has a cache entry.
-// (hdr: the word of the uniform and general counts, hdr_s: the shadowed count's; the host's second
-// word receives that count plus one)
-__global__ __launch_bounds__(64) void packet_list_zero_kernel(PkConeJobs J, size_t hdr,
-                                                              size_t hdr_s) {
+// (tile_list_counts_encode, into two pinned words) where the table has a cache entry.
+__global__ __launch_bounds__(64) void packet_list_zero_kernel(PkConeJobs J, TileTabLayout L) {
     if (static_cast<int>(threadIdx.x) >= J.n) return;
-    J.dst[threadIdx.x][hdr] = 0ull;
-    J.dst[threadIdx.x][hdr_s] = 0ull;
+    J.dst[threadIdx.x][L.list_counts()] = 0ull;
+    J.dst[threadIdx.x][L.shadowed_count()] = 0ull;
 }
 __global__ __launch_bounds__(64) void packet_list_counts_kernel(PkConeJobs J, PkListCounts C,
-                                                                size_t hdr, size_t hdr_s) {
+                                                                TileTabLayout L) {
     if (static_cast<int>(threadIdx.x) >= J.n || !C.host[threadIdx.x]) return;
-    const unsigned long long v = J.dst[threadIdx.x][hdr];
-    const unsigned long long s = J.dst[threadIdx.x][hdr_s];
-    __hip_atomic_store(C.host[threadIdx.x],
-                       (((v >> 32) + 1ull) << 32) | ((v & 0xffffffffull) + 1ull), __ATOMIC_RELAXED,
-                       __HIP_MEMORY_SCOPE_SYSTEM);
-    __hip_atomic_store(C.host[threadIdx.x] + 1, (s & 0xffffffffull) + 1ull, __ATOMIC_RELAXED,
+    unsigned long long w[2];
+    tile_list_counts_encode(tile_list_counts(J.dst[threadIdx.x][L.list_counts()],
+                                             J.dst[threadIdx.x][L.shadowed_count()]), w);
+    __hip_atomic_store(C.host[threadIdx.x], w[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __hip_atomic_store(C.host[threadIdx.x] + 1, w[1], __ATOMIC_RELAXED,
                        __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
@@ -191,12 +181,9 @@ hipError_t launch_packet_cone_tables(const TraceParams& p, const PkConeJobs& job
     if (jobs.n <= 0) return hipSuccess;
     if (jobs.n > kPkMaxBatch || p.ns > 64 || p.width == 0 || p.rows == 0)
         return hipErrorInvalidValue;
-    if (jobs.shadow_nl != 0 && jobs.shadow_nl != packet_shadow_table_lights(p))
+    const TileTabContents C = jobs.contents;
+    if (!C.valid() || (C.has_shadow() && C.shadow_nl != packet_shadow_table_lights(p)))
         return hipErrorInvalidValue;
-    if (jobs.class_words != 0 && jobs.shadow_nl <= 0) return hipErrorInvalidValue;
-    if (jobs.class_words < 0 || jobs.class_words > 2) return hipErrorInvalidValue;
-    if (jobs.lists != 0 && jobs.class_words == 0) return hipErrorInvalidValue;
-    if (jobs.lists < 0 || jobs.lists > 2) return hipErrorInvalidValue;
     for (int j = 0; j < jobs.n; ++j) {
         const int f = jobs.frame[j];
         if (!jobs.dst[j] || f < -1 || f >= static_cast<int>(p.nframes) ||
@@ -206,22 +193,20 @@ hipError_t launch_packet_cone_tables(const TraceParams& p, const PkConeJobs& job
     uint32_t gx, gy, waves;
     packet_grid(p, gx, gy, waves);
     const uint32_t tiles = gx * gy * waves;
-    const size_t hdr = static_cast<size_t>(tiles) * (2 + jobs.shadow_nl);
-    const size_t hdr_s = hdr + tile_list_shadowed_count(tiles, static_cast<size_t>(gx) * gy);
-    if (jobs.lists) {
+    const TileTabLayout L{tiles, static_cast<size_t>(gx) * gy, C};
+    if (C.has_lists()) {
         // (a list entry names a tile by 12-bit column and row: packet_split_wanted)
         if (gx * kWgWavesX > kListMaxCoord || gy * (waves / kWgWavesX) > kListMaxCoord)
             return hipErrorInvalidValue;
-        hipLaunchKernelGGL(packet_list_zero_kernel, dim3(1), dim3(64), 0, stream, jobs, hdr,
-                           hdr_s);
+        hipLaunchKernelGGL(packet_list_zero_kernel, dim3(1), dim3(64), 0, stream, jobs, L);
     }
     hipLaunchKernelGGL(packet_cone_table_kernel,
                        dim3((tiles + kConeThreads - 1) / kConeThreads,
                             static_cast<unsigned>(jobs.n)),
                        dim3(kConeThreads), 0, stream, p, jobs, gx, gy, waves);
-    if (jobs.lists && counts)
+    if (C.has_lists() && counts)
         hipLaunchKernelGGL(packet_list_counts_kernel, dim3(1), dim3(64), 0, stream, jobs, *counts,
-                           hdr, hdr_s);
+                           L);
     return hipGetLastError();
 }
 
@@ -438,8 +423,7 @@ int packet_shadow_table_lights(const TraceParams& p) {
 // marching variant everywhere, =1: the fix-up variant for every eligible batch (tests, A/B).
 constexpr uint64_t kPkFixMinPixels = 32ull << 20;
 bool packet_uses_fixup(const TraceParams& p, bool count, bool any_specular) {
-    const char* e = std::getenv("RTAMD_PK_FIX");  // read per launch (tests switch it)
-    const int mode = e ? std::atoi(e) : -1;
+    const int mode = packet_switch("RTAMD_PK_FIX");
     if (mode == 0) return false;
     const bool eligible = !count && p.aa == 1 && !p.tile_cost && p.nframes >= 1 &&
                           (p.ns + 63) / 64 <= 1 && packet_features(p, any_specular) == 0;
@@ -462,22 +446,24 @@ bool packet_uses_fixup(const TraceParams& p, bool count, bool any_specular) {
 #define RT_PACKET_UNI_WAVES 8
 #endif
 // SPH = true: the same kernel over the frame's list of shadowed-plane tiles (tile_shadowed_mark,
-// rt_shadow_table.hpp: entries of the same format from the end of the uniform list's words
-// downwards, their count after the general list), which also hands pk_uniform_tile the tile's
-// shadow words — P.fr_stab of the frame at the tile the entry's column and row name, nl words —
-// for the sphere block of the shadow classification.  SPH = false is the kernel as it was.
+// rt_shadow_table.hpp; entries of the same format, TileTabLayout::Lists), which also hands
+// pk_uniform_tile the tile's shadow words — P.fr_stab of the frame at the tile the entry's column
+// and row name, nl words — for the sphere block of the shadow classification.
 constexpr int kUniThreads = RT_PACKET_UNI_THREADS;
 template <bool SPH>
 __global__ __launch_bounds__(kUniThreads, RT_PACKET_UNI_WAVES) void packet_uniform_kernel(TraceParams P, uint32_t tiles) {
     constexpr int FEAT = kFeatFix;
     const PkFrame& F = P.fr[blockIdx.z];  // (split launches are frame batches: P.nframes >= 1)
-    const pk_culp hdr = (pk_culp)P.fr_ctab[blockIdx.z] + tiles;
+    // (one wave row per workgroup, packet_split_wanted: tiles / kWgWavesX workgroups)
+    const pk_culp ctab = (pk_culp)P.fr_ctab[blockIdx.z];
+    const TileTabLayout::Lists L{tiles, tiles / kWgWavesX};
+    const pk_culp hdr = ctab + L.after_cls();
     const uint32_t i = blockIdx.x * (kUniThreads / 64) +
                        __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(threadIdx.x) >> 6);
-    // (one wave row per workgroup, packet_split_wanted: tiles / kWgWavesX workgroups)
-    if (i >= static_cast<uint32_t>(hdr[SPH ? tile_list_shadowed_count(tiles, tiles / kWgWavesX) : 0]))
-        return;
-    const unsigned long long e = hdr[1 + (SPH ? tile_list_shadowed_slot(i, tiles) : i)];
+    const TileListCounts n = tile_list_counts(SPH ? 0ull : hdr[L.counts()],
+                                              SPH ? hdr[L.shadowed_count()] : 0ull);
+    if (i >= (SPH ? n.shadowed : n.uniform)) return;
+    const unsigned long long e = hdr[SPH ? L.shadowed(i) : L.uniform(i)];
     const unsigned long long cls = e & kListWordMask;
     const uint32_t col = static_cast<uint32_t>(e >> kListColShift) & kListCoordMask;
     const uint32_t row = static_cast<uint32_t>(e >> kListRowShift) & kListCoordMask;
@@ -516,8 +502,7 @@ __global__ __launch_bounds__(kUniThreads, RT_PACKET_UNI_WAVES) void packet_unifo
 // RTAMD_PK_TILE_SPLIT=0 (read per launch): the fix-up variant's single launch, no lists formed
 // (a table formed that way is one of its own).
 bool packet_split_wanted(const TraceParams& p) {
-    const char* e = std::getenv("RTAMD_PK_TILE_SPLIT");
-    if (e && std::atoi(e) == 0) return false;
+    if (packet_switch_off("RTAMD_PK_TILE_SPLIT")) return false;
     uint32_t gx, gy, waves;
     packet_grid(p, gx, gy, waves);
     // (one wave row per workgroup: a scene with class words has at most 63 spheres, an image far

@@ -43,10 +43,8 @@ constexpr size_t kPkPubMaxWords = 1024;
 std::atomic<uint32_t> g_pk_epoch{0};
 rt_status packet_publish_slot(rt_context* ctx, const rt_scene* sc, TraceParams& p) {
     const size_t words = packet_lds_bytes(p.ns, p.np, p.nl) / 4;
-    static const bool off = [] {  // RTAMD_PK_PUB=0: every workgroup forms it (A/B runs)
-        const char* e = std::getenv("RTAMD_PK_PUB");
-        return e && std::atoi(e) == 0;
-    }();
+    // RTAMD_PK_PUB=0: every workgroup forms it (A/B runs; read once)
+    static const bool off = packet_switch_off("RTAMD_PK_PUB");
     if (off || words > kPkPubMaxWords) return RT_OK;
     const size_t slot = kPkPubMaxWords * sizeof(unsigned long long);
     if (!sc->pk_pub.ptr) {
@@ -208,49 +206,28 @@ rt_status packet_image_entry(rt_context* ctx, const rt_scene* sc, const double* 
     return RT_OK;
 }
 
-// Camera-cone tables (rt_cone_table.hpp; TraceParams.cone_tab / fr_tab).  A table belongs to a
-// camera, its ray constants and a launch shape (cone_table_key): a cached camera keeps up to
-// kMaxConeTabs of them next to its image (later shapes or focal lengths go without), each
-// formed once by a small launch on the stream that first needs it and guarded by an event for
-// the others; a batch frame without a cached image gets one in the
-// batch's ring entry, formed by one launch per batch.  A one-frame launch of a camera seen for
-// the first time (the publish-slot path) gets none: a setup launch per frame costs more than
-// the frame saves.  RTAMD_PK_CONE_TAB=0 (read per launch): no tables (A/B runs, tests).
-// The shadow-cull words (rt_shadow_table.hpp; TraceParams.shadow_tab / fr_stab) live and die
-// with the cone table they are formed from: the same launch writes them into the same buffer
-// after the cone words (nl per tile, for the scenes packet_shadow_table_lights accepts), under
-// the same key, cache entry, ring entry and caps.  Unlike the cone masks they depend on the
-// render call's bias (it enters every ball's radius), so the key of a table that holds them
-// carries the bias bit for bit and how many words per tile it holds: one position rendered at
-// two biases has two tables, as at two focal lengths.  RTAMD_PK_SHADOW_TAB=0 (read per launch):
-// no shadow words are formed or handed to the kernel (the table kernel does the cone table's
-// work only, and a cached table formed that way is one of its own, whatever the bias).  With
-// The tile lists (rt_shadow_table.hpp) follow the class words in the same buffer, formed by the
-// same launch for the frame batches that take the fix-up variant: same key (the word that says
-// what follows the shadow words has one more bit), cache entry, ring entry and caps; like the
-// shadow words they come on top of the ring's accounting (9/8 of the class words at most).  A
-// cache entry's table also has a pinned host word that receives the lists' two counts once the
-// table is formed, which sizes the split launch's grids; a batch with a ring frame (a camera
-// seen for the first time) forms no lists and stays one launch, as does the batch whose launch
-// forms a table.  RTAMD_PK_TILE_SPLIT=0 (read per launch): no lists.
-// The shadowed-plane tiles (tile_shadowed_mark) are marked in the class words and filed in a third
-// list by the same launch, in the same words (the list fills the uniform list's free end, its
-// count is one word more, and the pinned host words are two: three counts); the key word has one
-// more bit for them.  RTAMD_PK_TILE_SHADOWED=0 (read per launch): no mark and no third list, and a
-// cached table formed that way is one of its own.
-// RTAMD_PK_CONE_TAB=0 alone the cone words are still formed — the shadow words depend on them —
-// but only the shadow pointers reach the kernel.
-// The tile class words (tile_class_word, rt_shadow_table.hpp; TraceParams.class_tab / fr_ctab)
-// follow the shadow words in the same buffer, one per tile: formed by the same launch only when
-// both the cone and the shadow words are formed and passed, under the same key (one more word
-// says whether the buffer holds them), cache entry, ring entry and caps, and counted in the
-// ring's accounting.  RTAMD_PK_TILE_CLASS=0 (read per launch): none are formed or passed, and a
-// cached table formed that way is one of its own.
-// The shadow-plane keep masks (shadow_plane_keep) ride in the class words' bits 8 and up, so they
-// share the class words' buffer, cache entry, ring entry and accounting; the key word that says
-// the buffer holds class words also says whether their masks were formed.  RTAMD_PK_PLANE_CLEAR=0
-// (read per launch): the class words carry all-ones masks — every plane is classified — and a
-// cached table formed that way is one of its own.
+// Tile tables (rt_tile_table.hpp says what one holds and where; the kernel's pointers into one
+// are TraceParams.cone_tab / shadow_tab / class_tab and fr_tab / fr_stab / fr_ctab).  A table
+// belongs to a camera, its ray constants, a launch shape and its contents (cone_table_key): a
+// cached camera keeps up to kMaxConeTabs of them next to its image (later shapes or focal lengths
+// go without), each formed once by a small launch on the stream that first needs it and guarded
+// by an event for the others; a batch frame without a cached image gets one in the batch's ring
+// entry, formed by one launch per batch.  A one-frame launch of a camera seen for the first time
+// (the publish-slot path) gets none: a setup launch per frame costs more than the frame saves.
+// What a launch's tables hold, and which sections reach the kernel, is tables_wanted's answer:
+// the scene, the launch and the RTAMD_PK_* switches (each read per launch, 0 = off) decide, and
+// a table formed with other contents is one of its own in the cache.
+//   RTAMD_PK_CONE_TAB      the cone pointer (the words are still formed: the others need them)
+//   RTAMD_PK_SHADOW_TAB    the shadow words and their pointer; they depend on the render call's
+//                          bias, so a table that holds them is keyed by it
+//   RTAMD_PK_TILE_CLASS    the class words (only with both of the above)
+//   RTAMD_PK_PLANE_CLEAR   their shadow-plane keep masks (else all ones: every plane classified)
+//   RTAMD_PK_TILE_SPLIT    the lists, for the frame batches that take the fix-up variant
+//   RTAMD_PK_TILE_SHADOWED the shadowed-plane mark and the third list
+// A cache entry's table with lists also has two pinned host words that receive the lists' counts
+// once the table is formed (TileListCounts), which size the split launch's grids; a batch with a
+// ring frame (a camera seen for the first time) forms no lists and stays one launch, as does the
+// batch whose launch forms a table.
 constexpr size_t kMaxConeTabs = 8;
 // The ring's table memory per entry (kPkBatchRing entries), counted in cone words: a 32-frame
 // 1080p batch takes 8.3 MB (259 KB a frame), a 4K frame 1 MB; frames past the cap go without a
@@ -259,84 +236,68 @@ constexpr size_t kMaxConeTabs = 8;
 constexpr size_t kConeRingBytes = size_t(16) << 20;
 
 struct TabsWanted {
-    bool cone, shadow;
-    int shadow_nl;  // shadow words per tile this launch's tables hold (0: cone masks only)
-    bool cls;       // the tile class words too, one per tile after the shadow words
-    bool clear;     // ... with their shadow-plane keep masks formed (else all ones)
-    bool lists;     // ... and the tile lists after them (the fix-up variant's split launch)
-    bool shadowed;  // ... with the shadowed-plane tiles marked and in a third list
-    int list_kind() const { return lists ? (shadowed ? 2 : 1) : 0; }  // PkConeJobs.lists
-    int cls_kind() const { return cls ? (clear ? 2 : 1) : 0; }  // PkConeJobs.class_words
+    bool cone, shadow;  // which of the cone and shadow pointers the kernel gets
+    TileTabContents c;  // what the launch's tables hold (the class pointer: c.has_class())
     bool any() const { return cone || shadow; }
 };
 TabsWanted tables_wanted(const rt_scene* sc, const TraceParams& p) {
-    TabsWanted w{false, false, 0, false, false, false, false};
+    TabsWanted w{false, false, {0, 0, 0}};
     if (!packet_reads_cone_table(p, sc->max_specular > 0.0)) return w;
-    const char* e = std::getenv("RTAMD_PK_CONE_TAB");
-    w.cone = !(e && std::atoi(e) == 0);
-    e = std::getenv("RTAMD_PK_SHADOW_TAB");
-    w.shadow = packet_shadow_table_lights(p) > 0 && !(e && std::atoi(e) == 0);
-    w.shadow_nl = w.shadow ? packet_shadow_table_lights(p) : 0;
-    e = std::getenv("RTAMD_PK_TILE_CLASS");
-    w.cls = w.cone && w.shadow && !(e && std::atoi(e) == 0);
-    e = std::getenv("RTAMD_PK_PLANE_CLEAR");
-    w.clear = w.cls && !(e && std::atoi(e) == 0);
+    auto on = [](const char* name) { return !packet_switch_off(name); };
+    w.cone = on("RTAMD_PK_CONE_TAB");
+    w.shadow = packet_shadow_table_lights(p) > 0 && on("RTAMD_PK_SHADOW_TAB");
+    w.c.shadow_nl = w.shadow ? packet_shadow_table_lights(p) : 0;
+    if (w.cone && w.shadow && on("RTAMD_PK_TILE_CLASS"))
+        w.c.class_words = on("RTAMD_PK_PLANE_CLEAR") ? 2 : 1;
     // the tile lists serve frame batches that take the fix-up variant, and only those
-    w.lists = w.cls && p.nframes >= 1 && packet_uses_fixup(p, false, sc->max_specular > 0.0) &&
-              packet_split_wanted(p);
-    e = std::getenv("RTAMD_PK_TILE_SHADOWED");
-    w.shadowed = w.lists && !(e && std::atoi(e) == 0);
+    if (w.c.has_class() && p.nframes >= 1 &&
+        packet_uses_fixup(p, false, sc->max_specular > 0.0) && packet_split_wanted(p))
+        w.c.lists = on("RTAMD_PK_TILE_SHADOWED") ? 2 : 1;
     return w;
 }
 
-// A table's key: everything its masks depend on besides the scene and the camera position (the
+// p's launch shape as a table's layout
+TileTabLayout table_layout(const TraceParams& p, const TileTabContents& c) {
+    uint32_t gx, gy, waves;
+    packet_grid(p, gx, gy, waves);
+    return TileTabLayout{static_cast<size_t>(gx) * gy * waves, static_cast<size_t>(gx) * gy, c};
+}
+
+// A table's key: everything its words depend on besides the scene and the camera position (the
 // cache entry's) — the launch shape (tile_order's fields, the row plan's block and stride as
-// words of their own: a collision here would be wrong masks, not another permutation) and the
-// camera-ray constants dz = (cam.z + focal) − cam.z, W/2 and H/2 bit for bit: the focal length
-// is the render call's, not the scene's, so one position may be rendered at several.  A table
-// with shadow words (shadow_nl > 0 per tile) also carries that count and the render call's
-// bias bit for bit: the words formed at one bias are wrong masks at a larger one.  Returns the
-// table's size.
+// words of their own: a collision here would be wrong masks, not another permutation), the
+// camera-ray constants dz = (cam.z + focal) − cam.z, W/2 and H/2 bit for bit (the focal length
+// is the render call's, not the scene's, so one position may be rendered at several), the
+// contents, and for a table with shadow words the render call's bias bit for bit: the words formed
+// at one bias are wrong masks at a larger one.
 constexpr size_t kConeKeyWords = rt_scene::PkImage::ConeTab::kKeyWords;
-size_t cone_table_key(const TraceParams& p, double dz, int shadow_nl, int cls, int lists,
-                      uint32_t (&key)[kConeKeyWords], size_t* tiles = nullptr) {
+void cone_table_key(const TraceParams& p, double dz, const TileTabContents& c,
+                    uint32_t (&key)[kConeKeyWords]) {
     uint32_t gx, gy, waves;
     packet_grid(p, gx, gy, waves);
     const uint32_t k[9] = {gx, gy, waves, p.width, p.height, p.rows, p.row0, p.row_block,
                            p.row_stride};
-    const double c[3] = {dz, p.half_w, p.half_h};
+    const double d[3] = {dz, p.half_w, p.half_h};
     std::memset(key, 0, sizeof key);
     std::memcpy(key, k, sizeof k);
-    std::memcpy(key + 9, c, sizeof c);
-    static_assert(sizeof k + sizeof c + 2 * sizeof(uint32_t) + sizeof(double) <=
+    std::memcpy(key + 9, d, sizeof d);
+    static_assert(sizeof k + sizeof d + sizeof(uint32_t) + sizeof(double) <=
                       sizeof(uint32_t) * kConeKeyWords, "cone table key");
     // (lights and planes are the scene's, like the spheres: not part of the key)
-    if (shadow_nl > 0) {
-        key[15] = static_cast<uint32_t>(shadow_nl);
-        std::memcpy(key + 16, &p.bias, sizeof p.bias);
-        // the class words follow the shadow words (1), with their keep masks formed (3)
-        // ... and the tile lists follow the class words (4), the shadowed-plane tiles marked
-        // and listed (8)
-        key[18] = (cls == 2 ? 3u : (cls ? 1u : 0u)) | (cls && lists ? 4u : 0u) |
-                  (cls && lists == 2 ? 8u : 0u);
-    }
-    const size_t n = static_cast<size_t>(gx) * gy * waves;
-    if (tiles) *tiles = n;
-    return sizeof(unsigned long long) *
-           (n * (1 + static_cast<size_t>(shadow_nl > 0 ? shadow_nl + (cls ? 1 : 0) : 0)) +
-            (shadow_nl > 0 && cls && lists ? tile_list_words(n, static_cast<size_t>(gx) * gy) : 0));
+    key[15] = c.key_word();
+    if (c.has_shadow()) std::memcpy(key + 16, &p.bias, sizeof p.bias);
 }
 
 // The cached camera's table for p's launch shape: *tab = the existing one (this stream ordered
 // after the launch that formed it), or a new entry whose table the caller forms (*fresh) and
 // whose event it records; null when the camera's table list is full.
 rt_status cone_table_entry(rt_context* ctx, rt_scene::PkImage& im, const TraceParams& p,
-                           double dz, int shadow_nl, int cls, int lists,
+                           double dz, const TileTabContents& c,
                            rt_scene::PkImage::ConeTab** tab, bool* fresh) {
     *tab = nullptr;
     *fresh = false;
     uint32_t key[kConeKeyWords];
-    const size_t bytes = cone_table_key(p, dz, shadow_nl, cls, lists, key);
+    cone_table_key(p, dz, c, key);
     for (auto& t : im.tabs) {
         if (std::memcmp(t.key, key, sizeof key) != 0) continue;
         if (!t.done && t.stream != ctx->stream) {
@@ -355,10 +316,10 @@ rt_status cone_table_entry(rt_context* ctx, rt_scene::PkImage& im, const TracePa
     auto& t = im.tabs.back();
     std::memcpy(t.key, key, sizeof key);
     t.stream = ctx->stream;
-    hipError_t e = t.buf.ensure(bytes);
+    hipError_t e = t.buf.ensure(table_layout(p, c).bytes());
     if (e == hipSuccess) e = hipEventCreateWithFlags(&t.ready, hipEventDisableTiming);
-    if (e == hipSuccess && lists) {
-        // (two words: {uniform, general} and the shadowed count, PkListCounts)
+    if (e == hipSuccess && c.has_lists()) {
+        // (the two words of tile_list_counts_encode)
         e = hipHostMalloc(reinterpret_cast<void**>(&t.counts), 2 * sizeof(unsigned long long));
         if (e == hipSuccess) __atomic_store_n(t.counts, 0ull, __ATOMIC_RELAXED);
         if (e == hipSuccess) __atomic_store_n(t.counts + 1, 0ull, __ATOMIC_RELAXED);
@@ -382,6 +343,15 @@ void cone_table_drop(rt_scene::PkImage& im) {  // the entry cone_table_entry jus
     im.tabs.pop_back();
 }
 
+// The kernel's three pointers into a table at `words` (null: none is handed over).
+void hand_table(const TabsWanted& want, const TileTabLayout& L, const unsigned long long* words,
+                const unsigned long long** cone, const unsigned long long** shadow,
+                const unsigned long long** cls) {
+    *cone = words && want.cone ? words + L.cone(0) : nullptr;
+    *shadow = words && want.shadow ? words + L.shadow(0, 0) : nullptr;
+    *cls = words && want.c.has_class() ? words + L.cls(0) : nullptr;
+}
+
 // One-frame launches with an image entry (p.pk_image set, formed earlier on the stream).
 rt_status cone_table_single(rt_context* ctx, const rt_scene* sc, rt_scene::PkImage& im,
                             TraceParams& p) {
@@ -389,8 +359,7 @@ rt_status cone_table_single(rt_context* ctx, const rt_scene* sc, rt_scene::PkIma
     if (!want.any()) return RT_OK;
     rt_scene::PkImage::ConeTab* t = nullptr;
     bool fresh = false;
-    const rt_status st = cone_table_entry(ctx, im, p, p.cam_dz, want.shadow_nl, want.cls_kind(),
-                                          0, &t, &fresh);
+    const rt_status st = cone_table_entry(ctx, im, p, p.cam_dz, want.c, &t, &fresh);
     if (st != RT_OK || !t) return st;
     if (fresh) {
         PkConeJobs jobs;
@@ -398,8 +367,7 @@ rt_status cone_table_single(rt_context* ctx, const rt_scene* sc, rt_scene::PkIma
         jobs.dst[0] = static_cast<unsigned long long*>(t->buf.ptr);
         jobs.frame[0] = -1;
         jobs.n = 1;
-        jobs.shadow_nl = want.shadow_nl;
-        jobs.class_words = want.cls_kind();
+        jobs.contents = want.c;
         hipError_t e = launch_packet_cone_tables(p, jobs, ctx->stream);
         if (e == hipSuccess) e = hipEventRecord(t->ready, ctx->stream);
         if (e != hipSuccess) {
@@ -407,14 +375,9 @@ rt_status cone_table_single(rt_context* ctx, const rt_scene* sc, rt_scene::PkIma
             return hip_fail(e, "cone table setup");
         }
     }
-    uint32_t key[kConeKeyWords];
-    size_t tiles = 0;
-    (void)cone_table_key(p, p.cam_dz, want.shadow_nl, want.cls_kind(), 0, key, &tiles);
-    const unsigned long long* words = static_cast<const unsigned long long*>(t->buf.ptr);
-    if (want.cone) p.cone_tab = words;
-    if (want.shadow) p.shadow_tab = words + tiles;
-    if (want.cls) p.class_tab = words + tiles * (1 + static_cast<size_t>(want.shadow_nl));
-    p.plane_masks = want.clear ? 1u : 0u;
+    hand_table(want, table_layout(p, want.c), static_cast<const unsigned long long*>(t->buf.ptr),
+               &p.cone_tab, &p.shadow_tab, &p.class_tab);
+    p.plane_masks = want.c.forms_keep() ? 1u : 0u;
     return RT_OK;
 }
 
@@ -568,18 +531,16 @@ rt_status packet_batch_images(rt_context* ctx, const rt_scene* sc, const rt_came
     // host cannot know its counts before the launch, both grids would have to cover every tile,
     // and the surplus workgroups cost more than the split saves (moving_camera −10 %,
     // profiles/tile_split_ab.txt)
-    if (any_ring) want.lists = want.shadowed = false;
+    if (any_ring) want.c.lists = 0;
     // The frames' cone tables, after their images on the stream: a cached or promoted camera's
     // from (or into) its entry, a ring frame's into the ring entry's table buffer up to its
     // cap, a duplicate's shared; every table that does not exist yet by ONE launch.
-    uint32_t key[kConeKeyWords];
-    size_t tiles = 0;
-    const size_t tab_bytes =  // (the sizes only)
-        (cone_table_key(p, 0.0, want.shadow_nl, want.cls_kind(), want.list_kind(), key, &tiles) + 255) &
-        ~size_t(255);
-    // (the cap counts the cone words and the class words; the shadow words come on top)
+    const TileTabLayout L = table_layout(p, want.c);
+    const uint32_t tiles = static_cast<uint32_t>(L.tiles);
+    const size_t tab_bytes = (L.bytes() + 255) & ~size_t(255);
+    // (the cap counts the cone words and the class words; the others come on top)
     const size_t cone_bytes =
-        (sizeof(unsigned long long) * tiles * (want.cls ? 2 : 1) + 255) & ~size_t(255);
+        (sizeof(unsigned long long) * L.capped_words() + 255) & ~size_t(255);
     char* ring_tab = nullptr;
     size_t ring_room = 0;
     if (any_ring) {
@@ -599,44 +560,33 @@ rt_status packet_batch_images(rt_context* ctx, const rt_scene* sc, const rt_came
     }
     PkConeJobs cj;
     std::memset(&cj, 0, sizeof cj);
-    cj.shadow_nl = want.shadow_nl;
-    cj.class_words = want.cls_kind();
-    cj.lists = want.list_kind();
+    cj.contents = want.c;
     PkListCounts lc;
     std::memset(&lc, 0, sizeof lc);
-    // a frame's list counts where the host has them (a cache entry's table formed earlier):
-    // {uniform tiles, general workgroups}; a table formed by this call's launch has none yet, and
-    // its batch stays one launch
-    uint32_t gx, gy, waves;
-    packet_grid(p, gx, gy, waves);
-    uint32_t n_uni = 0, n_gen = 0, n_sh = 0;
-    bool all_lists = want.lists;
+    // a frame's list counts where the host has them (a cache entry's table formed earlier); a
+    // table formed by this call's launch has none yet, and its batch stays one launch
+    TileListCounts most{0u, 0u, 0u};
+    bool all_lists = want.c.has_lists();
     auto count_frame = [&](const unsigned long long* host) {
-        const unsigned long long v = host ? __atomic_load_n(host, __ATOMIC_RELAXED) : 0ull;
-        const unsigned long long v2 = host ? __atomic_load_n(host + 1, __ATOMIC_RELAXED) : 0ull;
-        const uint32_t u = static_cast<uint32_t>(v), g = static_cast<uint32_t>(v >> 32);
-        const uint32_t s = static_cast<uint32_t>(v2);
-        if (!u || !g || !s) all_lists = false;
-        n_uni = std::max(n_uni, u ? u - 1u : static_cast<uint32_t>(tiles));
-        n_gen = std::max(n_gen, g ? g - 1u : gx * gy);
-        n_sh = std::max(n_sh, s ? s - 1u : static_cast<uint32_t>(tiles));
+        const unsigned long long v[2] = {host ? __atomic_load_n(host, __ATOMIC_RELAXED) : 0ull,
+                                         host ? __atomic_load_n(host + 1, __ATOMIC_RELAXED) : 0ull};
+        TileListCounts n;
+        if (!tile_list_counts_decode(v, &n)) all_lists = false;
+        else most = TileListCounts{std::max(most.uniform, n.uniform),
+                                   std::max(most.general, n.general),
+                                   std::max(most.shadowed, n.shadowed)};
     };
-    p.plane_masks = want.clear ? 1u : 0u;
+    p.plane_masks = want.c.forms_keep() ? 1u : 0u;
     // the kernel's pointers of a frame whose table is (or will be) at `words`
     auto hand = [&](int f, const unsigned long long* words) {
-        p.fr_tab[f] = want.cone ? words : nullptr;
-        p.fr_stab[f] = want.shadow ? words + tiles : nullptr;
-        p.fr_ctab[f] =
-            want.cls ? words + tiles * (1 + static_cast<size_t>(want.shadow_nl)) : nullptr;
+        hand_table(want, L, words, &p.fr_tab[f], &p.fr_stab[f], &p.fr_ctab[f]);
     };
     rt_scene::PkImage* made[kPkMaxBatch];  // entries that got a fresh table (newest last)
     rt_scene::PkImage::ConeTab* made_tab[kPkMaxBatch];
     int n_made = 0;
     rt_status st = RT_OK;
     for (int f = 0; f < nframes && st == RT_OK; ++f) {
-        p.fr_tab[f] = nullptr;
-        p.fr_stab[f] = nullptr;
-        p.fr_ctab[f] = nullptr;
+        hand(f, nullptr);
         unsigned long long* dst = nullptr;
         if (kind[f] == kDup) {
             p.fr_tab[f] = p.fr_tab[dup_of[f]];
@@ -653,8 +603,7 @@ rt_status packet_batch_images(rt_context* ctx, const rt_scene* sc, const rt_came
         } else {
             rt_scene::PkImage::ConeTab* t = nullptr;
             bool fresh = false;
-            st = cone_table_entry(ctx, *ent[f], p, p.fr_dz[f][0], want.shadow_nl,
-                                  want.cls_kind(), want.list_kind(), &t, &fresh);
+            st = cone_table_entry(ctx, *ent[f], p, p.fr_dz[f][0], want.c, &t, &fresh);
             if (st != RT_OK || !t) all_lists = false;
             if (st != RT_OK || !t) continue;
             hand(f, static_cast<const unsigned long long*>(t->buf.ptr));
@@ -681,7 +630,8 @@ rt_status packet_batch_images(rt_context* ctx, const rt_scene* sc, const rt_came
     if (st != RT_OK)  // a table never formed must not be found by a later render
         for (int i = n_made - 1; i >= 0; --i) cone_table_drop(*made[i]);
     if (st == RT_OK && all_lists) {  // every frame has its lists: the split launch
-        *split = PkSplit{static_cast<uint32_t>(tiles), n_uni, n_gen, want.shadowed ? n_sh : 0u};
+        *split = PkSplit{tiles, most.uniform, most.general,
+                         want.c.forms_mark() ? most.shadowed : 0u};
     }
     return st;
 }

@@ -591,11 +591,11 @@ __global__ __launch_bounds__(64 * kWgWavesX * WGY, pk_waves(MAXC, FEAT_, COUNT, 
     if constexpr (SPLIT) {
         // this workgroup's entry of the frame's general list (the launcher checked that every
         // frame has class words and lists); past the count: nothing to render (uniform)
-        const uint32_t split_tiles =
-            gxw * ((P.rows + kPkH * WGY - 1) / (kPkH * WGY)) * (kWgWavesX * WGY);
-        const pk_culp hdr = (pk_culp)class_tab + split_tiles;
-        if (lin >= static_cast<uint32_t>(hdr[0] >> 32)) return;
-        const uint32_t t = ((pk_cip)(hdr + 1 + split_tiles))[lin];
+        const uint32_t split_wgs = gxw * ((P.rows + kPkH * WGY - 1) / (kPkH * WGY));
+        const TileTabLayout::Lists L{split_wgs * (kWgWavesX * WGY), split_wgs};
+        const pk_culp hdr = (pk_culp)class_tab + L.after_cls();
+        if (lin >= tile_list_counts(hdr[L.counts()], 0ull).general) return;
+        const uint32_t t = ((pk_cip)(hdr + L.general_base()))[lin];
         tbx = t % gxw;
         tby = t / gxw;
     }

@@ -60,6 +60,7 @@
 #include <stdint.h>
 
 #include "rt_cone_table.hpp"
+#include "rt_tile_table.hpp"
 
 #if defined(__clang__)
 #define RT_ST_UNROLL _Pragma("unroll")
@@ -69,7 +70,7 @@
 
 namespace rtamd {
 
-constexpr int kShadowTabLights = 4;
+// (kShadowTabLights, the lights a table has words for: rt_tile_table.hpp)
 constexpr int kShadowTabPlanes = 8;
 constexpr unsigned long long kShadowNoWord = ~0ull;
 // The tile class (tile_class_word, below): the relative margin of its plane ordering, and its
@@ -477,16 +478,12 @@ RT_CT_HD inline unsigned tile_plane_keep(unsigned long long word, int l) {
 }
 
 // The tile lists of a frame (packet_uniform_kernel and the split launch of packet_direct_kernel,
-// rt_packet_kernel.hpp): formed from the class words by the lane that forms them, they follow the
-// class words in the table's buffer —
-//   1 word    the counts: uniform tiles in the low half, general workgroups in the high half
-//   T words   the uniform tiles, one entry each (room for every tile)
-//   W/2 words the general workgroups, one 32-bit workgroup index tby · gx + tbx each
-//   1 word    the count of shadowed tiles (the third list, below)
-// for T tiles in W workgroups of `waves` tiles.  A tile is *uniform* when its class is not
-// kTileGeneral; a workgroup is *general*, and listed, when at least one of its tiles is not
-// uniform.  Every tile is therefore rendered exactly once: by the uniform kernel when it is
-// uniform, else by its wave of the listed workgroup (whose uniform waves return).
+// rt_packet_kernel.hpp): formed from the class words by the lane that forms them, where
+// rt_tile_table.hpp says.  A tile is *uniform* when its class is not kTileGeneral, and *shadowed*
+// when it is general and carries the shadowed-plane mark (tile_shadowed_mark: only a table with the
+// third list forms marks); a workgroup is listed when at least one of its tiles is neither.  Every
+// tile is therefore rendered exactly once: by a list kernel when it is uniform or shadowed, else by
+// its wave of the listed workgroup (whose other waves return).
 // A uniform entry is the tile's class word (bits 0-39: the class and up to four keep masks) with
 // the tile's column and row in 8-pixel units above it (12 bits each), so the kernel that reads
 // the list needs no second lookup and no division.
@@ -495,28 +492,10 @@ RT_CT_HD inline unsigned tile_plane_keep(unsigned long long word, int l) {
 // kernel's default dispatch has.  `waves` (2 or 4) divides 64 and T, so the tiles of a workgroup
 // are `waves` adjacent, aligned lanes of one run.  The order of the runs in a list is whatever
 // the runs' atomic adds make it; a list's order only permutes which workgroup renders which tile.
-// kIndexOff and kDropMixed exist for the host test's mutants only (an entry's column off by one;
-// a workgroup listed only when all of its tiles are general).
 constexpr int kListColShift = 40, kListRowShift = 52;
 constexpr unsigned long long kListWordMask = (1ull << kListColShift) - 1ull;
 constexpr uint32_t kListCoordMask = 0xfffu;
 constexpr uint32_t kListMaxCoord = kListCoordMask + 1u;  // tile columns and rows a list can name
-// The third list: the shadowed-plane tiles (tile_shadowed_mark) of a table formed with them.  Its
-// entries have the uniform list's format and fill the T words of the uniform list from their end
-// downwards — entry j at word T − j of the lists (a tile is in one list at most, so the two never
-// meet) — and its count is one more word after the general workgroups.  A workgroup is then
-// listed only when it has a tile that is neither uniform nor shadowed.  The first two lists and
-// their count word are where they were.
-RT_CT_HD inline size_t tile_list_words(size_t tiles, size_t wgs) {
-    return 2 + tiles + (wgs + 1) / 2;
-}
-// the shadowed count's word, and the uniform array's slot of shadowed entry j
-RT_CT_HD inline size_t tile_list_shadowed_count(size_t tiles, size_t wgs) {
-    return 1 + tiles + (wgs + 1) / 2;
-}
-RT_CT_HD inline uint32_t tile_list_shadowed_slot(uint32_t j, uint32_t tiles) {
-    return tiles - 1u - j;
-}
 RT_CT_HD inline uint32_t tile_list_tile(uint32_t pos, uint32_t tiles) { return tiles - 1u - pos; }
 RT_CT_HD inline bool tile_list_uniform(unsigned long long word) {
     return tile_class_of(word) != kTileGeneral;
@@ -535,29 +514,6 @@ RT_CT_HD inline bool tile_list_wg_listed(uint64_t general, unsigned lane, unsign
     const uint64_t g = (general >> (lane & ~(waves - 1u))) & group;
     return kDropMixed ? g == group : g != 0;
 }
-// One run of up to 64 list positions from `pos0` on, as one wavefront of the table kernel forms
-// it: words[] are the frame's class words by tile; the run's uniform entries go to uni[*n_uni …]
-// and its listed workgroups to gen[*n_gen …] (the kernel takes the two bases with one atomic add
-// each).  x0_of / yl0_of give a tile's pixel origin.
-template <int kIndexOff = 0, bool kDropMixed = false, class Origin>
-inline void tile_list_run(const unsigned long long* words, uint32_t tiles, uint32_t waves,
-                          uint32_t pos0, Origin origin, unsigned long long* uni, uint32_t* n_uni,
-                          uint32_t* gen, uint32_t* n_gen) {
-    uint64_t general = 0;
-    for (uint32_t l = 0; l < 64 && pos0 + l < tiles; ++l)
-        if (!tile_list_uniform(words[tile_list_tile(pos0 + l, tiles)])) general |= 1ull << l;
-    for (uint32_t l = 0; l < 64 && pos0 + l < tiles; ++l) {
-        const uint32_t t = tile_list_tile(pos0 + l, tiles);
-        if (tile_list_uniform(words[t])) {
-            uint32_t x0, yl0;
-            origin(t, x0, yl0);
-            uni[(*n_uni)++] = tile_list_entry<kIndexOff>(words[t], x0, yl0);
-        }
-        if ((l & (waves - 1u)) == 0 && tile_list_wg_listed<kDropMixed>(general, l, waves))
-            gen[(*n_gen)++] = t / waves;
-    }
-}
-
 // A shadowed tile of a table word (a general class byte with the mark), and its list entry: the
 // uniform entry the tile would have with class "plane i" — the keep masks as formed, the class
 // byte written from the mark's plane index, column and row above them.
@@ -569,28 +525,36 @@ RT_CT_HD inline unsigned long long tile_shadowed_entry(unsigned long long word, 
     const unsigned long long cls = kTilePlane0 + ((word >> kTileShadowedPlaneShift) & 7ull);
     return tile_list_entry((word & ~kTileClassBits) | cls, x0, yl0);
 }
-// tile_list_run with the third list: the run's shadowed entries go to uni[tiles − 1 − *n_sh …]
-// downwards, and a workgroup is listed when one of its tiles is neither uniform nor shadowed.
-// kDropShadowedMixed exists for the host test's mutant only (a workgroup with a shadowed wave and
-// a general wave is not listed).
-template <bool kDropShadowedMixed = false, class Origin>
-inline void tile_list_run3(const unsigned long long* words, uint32_t tiles, uint32_t waves,
-                           uint32_t pos0, Origin origin, unsigned long long* uni, uint32_t* n_uni,
-                           uint32_t* n_sh, uint32_t* gen, uint32_t* n_gen) {
-    uint64_t general = 0, shadowed = 0;
+// One run of up to 64 list positions from `pos0` on, as one wavefront of the table kernel forms
+// it: words[] are the frame's class words by tile.  Three masks over the run's lanes (the kernel's
+// three ballots) — uniform, shadowed and general tiles.  n_sh is the third list's switch: null
+// for a table without it, where no tile counts as shadowed.  The run's uniform entries go to
+// uni[*n_uni …], its shadowed entries to uni[shadowed_slot(*n_sh …)] downwards and its listed
+// workgroups to gen[*n_gen …] (the kernel takes the three bases with one atomic add each).
+// origin gives a tile's pixel origin.  The template parameters exist for the host tests' mutants
+// only: an entry's column off by one, a workgroup listed only when all of its tiles are general,
+// and a workgroup with a shadowed and a general wave not listed.
+template <int kIndexOff = 0, bool kDropMixed = false, bool kDropShadowedMixed = false,
+          class Origin>
+inline void tile_list_run(const unsigned long long* words, uint32_t tiles, uint32_t waves,
+                          uint32_t pos0, Origin origin, unsigned long long* uni, uint32_t* n_uni,
+                          uint32_t* gen, uint32_t* n_gen, uint32_t* n_sh = nullptr) {
+    uint64_t uniform = 0, shadowed = 0, general = 0;
     for (uint32_t l = 0; l < 64 && pos0 + l < tiles; ++l) {
         const unsigned long long w = words[tile_list_tile(pos0 + l, tiles)];
-        if (tile_list_shadowed(w)) shadowed |= 1ull << l;
-        else if (!tile_list_uniform(w)) general |= 1ull << l;
+        if (tile_list_uniform(w)) uniform |= 1ull << l;
+        else if (n_sh && tile_list_shadowed(w)) shadowed |= 1ull << l;
+        else general |= 1ull << l;
     }
     for (uint32_t l = 0; l < 64 && pos0 + l < tiles; ++l) {
         const uint32_t t = tile_list_tile(pos0 + l, tiles);
         uint32_t x0, yl0;
         origin(t, x0, yl0);
-        if (tile_list_uniform(words[t])) uni[(*n_uni)++] = tile_list_entry(words[t], x0, yl0);
-        else if (tile_list_shadowed(words[t]))
-            uni[tile_list_shadowed_slot((*n_sh)++, tiles)] = tile_shadowed_entry(words[t], x0, yl0);
-        if ((l & (waves - 1u)) == 0 && tile_list_wg_listed(general, l, waves) &&
+        if ((uniform >> l) & 1ull) uni[(*n_uni)++] = tile_list_entry<kIndexOff>(words[t], x0, yl0);
+        if ((shadowed >> l) & 1ull)
+            uni[TileTabLayout::shadowed_slot((*n_sh)++, tiles)] =
+                tile_shadowed_entry(words[t], x0, yl0);
+        if ((l & (waves - 1u)) == 0 && tile_list_wg_listed<kDropMixed>(general, l, waves) &&
             !(kDropShadowedMixed && tile_list_wg_listed(shadowed, l, waves)))
             gen[(*n_gen)++] = t / waves;
     }

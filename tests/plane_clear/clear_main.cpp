@@ -1,7 +1,7 @@
 // clear_main.cpp — stand-alone host check of the shadow-plane keep masks (shadow_plane_keep,
 // csrc/rt_shadow_table.hpp), built and run by tests/test_plane_clear_host.py against the C oracle
 // (oracle/rt_oracle.c).  The random frames, the frame file and the oracle's shadow rays are
-// tests/shadow_table/shadow_main.cpp's, included below with its main renamed.
+// tests/host_frame.hpp's.
 //
 //   clear_main prop SEED CASES [MUTANT]
 //       For every tile with an entry (empty cone mask, every plane decided), every lane pixel of
@@ -21,9 +21,7 @@
 // dropped over all tiles with an entry, `rays` the shadow rays checked against a dropped plane.
 // Exit status 0 only when every property holds (mutants: always 0, the caller reads
 // `violations`).
-#define main shadow_table_main
-#include "../shadow_table/shadow_main.cpp"
-#undef main
+#include "../host_frame.hpp"
 
 enum ClearMutant { kClrNone, kClrLight };
 
@@ -60,12 +58,7 @@ static ClearTile clear_tile(const Frame& F, uint32_t x0, uint32_t yl0, ClearMuta
             T.keep[l] = shadow_plane_keep(B, L, pl, np, F.cam.position, F.bias);
         }
     }
-    std::vector<double> pln(4 * static_cast<size_t>(np), 0.0);
-    for (int i = 0; i < np; ++i) {
-        const double* o = &F.planes[8 * static_cast<size_t>(i)];
-        const double n1 = std::fabs(o[3]) + std::fabs(o[4]) + std::fabs(o[5]);
-        pln[4 * static_cast<size_t>(i) + 3] = o[7] != 0.0 && n1 <= 2.0 ? 1.0 : 0.0;
-    }
+    const std::vector<double> pln = plane_flags(F);
     T.cls = tile_class_word<kShadowTabPlanes>(cone, B, words, nl, pln.data(), np);
     // the packed word gives back what went in
     const unsigned long long w = tile_class_pack(T.cls, T.keep, nl);
@@ -180,37 +173,8 @@ static int run_clear_prop(uint64_t seed, int cases, ClearMutant mut) {
 }
 
 static int run_clear_frame(const char* path) {
-    std::FILE* f = std::fopen(path, "r");
-    if (!f) return 4;
     Frame F{};
-    unsigned W = 0, H = 0, ns = 0, np = 0, nl = 0;
-    if (std::fscanf(f, "%u %u %la %la %la %la %la %u %u %u", &W, &H, &F.cam.position[0],
-                    &F.cam.position[1], &F.cam.position[2], &F.cam.focal, &F.bias, &ns, &np,
-                    &nl) != 10)
-        return 4;
-    if (W == 0 || H == 0 || ns < 1 || ns > 63 || np < 1 || np > unsigned(kShadowTabPlanes) ||
-        nl < 1 || nl > unsigned(kShadowTabLights))
-        return 4;
-    F.cam.width = W;
-    F.cam.height = H;
-    F.cam.aa_samples = 1;
-    F.sph.resize(ns);
-    F.pl.resize(np);
-    F.lt.resize(nl);
-    for (auto& s : F.sph)
-        if (std::fscanf(f, "%la %la %la %la", &s.center[0], &s.center[1], &s.center[2],
-                        &s.radius) != 4)
-            return 4;
-    for (auto& p : F.pl)
-        if (std::fscanf(f, "%la %la %la %la %la %la", &p.point[0], &p.point[1], &p.point[2],
-                        &p.normal[0], &p.normal[1], &p.normal[2]) != 6)
-            return 4;
-    for (auto& l : F.lt)
-        if (std::fscanf(f, "%la %la %la", &l.position[0], &l.position[1], &l.position[2]) != 3)
-            return 4;
-    std::fclose(f);
-    set_rows(F, 0, 0, 1);
-    F.prepare();
+    if (const int r = read_frame(path, F)) return r;
     ClearTally T;
     check_clear_frame(F, kClrNone, 0, T);
     print_clear("frame", 1, T);

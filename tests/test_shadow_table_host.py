@@ -23,29 +23,17 @@ import subprocess
 
 import pytest
 
+from host_programs import build, write_frame_file
 from raytracingengine_amd.configs import make_config
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SEED, CASES = 20240607, 2000
-SRC = f"{ROOT}/tests/shadow_table/shadow_main.cpp"
-
-
-def _build(d, name, extra):
-    oracle_o = str(d / f"rt_oracle_{name}.o")
-    subprocess.run(["gcc", "-std=c11", "-O2", "-ffp-contract=off", "-fopenmp", *extra,
-                    f"-I{ROOT}/oracle", "-c", f"{ROOT}/oracle/rt_oracle.c", "-o", oracle_o],
-                   check=True)
-    exe = str(d / name)
-    subprocess.run(["g++", "-std=c++20", "-O2", "-ffp-contract=off", "-Wall", "-Wextra", "-Werror",
-                    *extra, f"-I{ROOT}/raytracingengine_amd/csrc", f"-I{ROOT}/oracle", SRC,
-                    oracle_o, "-o", exe, "-fopenmp", "-lm"], check=True)
-    return exe
+SRC = "tests/shadow_table/shadow_main.cpp"
 
 
 @pytest.fixture(scope="module")
 def shadow_main(tmp_path_factory):
     d = tmp_path_factory.mktemp("shadow")
-    return _build(d, "shadow_main", []), d
+    return build(d, "shadow_main", SRC, []), d
 
 
 def _fields(line):
@@ -95,21 +83,8 @@ def test_c2_frame(shadow_main):
     9 110 candidates; without the hidden-plane rule the entries keep 36 551)."""
     exe, d = shadow_main
     sc = make_config("c2")
-    cam = sc.camera
     path = d / "c2.txt"
-
-    def hexes(vals):
-        return " ".join(float(v).hex() for v in vals)
-
-    with open(path, "w") as fh:
-        fh.write(f"{cam.width} {cam.height} {hexes((*cam.position, cam.focal, 1e-3))} "
-                 f"{len(sc.spheres)} {len(sc.planes)} {len(sc.lights)}\n")
-        for s in sc.spheres:
-            fh.write(hexes((*s[0], s[1])) + "\n")
-        for p in sc.planes:
-            fh.write(hexes((*p[0], *p[1])) + "\n")
-        for l in sc.lights:
-            fh.write(hexes(l[0]) + "\n")
+    write_frame_file(path, sc, 1e-3)
     r = subprocess.run([exe, "frame", str(path)], capture_output=True, text=True, timeout=600)
     print(r.stdout, r.stderr[-2000:])
     assert r.returncode == 0, (r.returncode, r.stdout, r.stderr[-2000:])
@@ -122,9 +97,9 @@ def test_c2_frame(shadow_main):
 
 def test_host_program_under_sanitizers(tmp_path):
     """The same stand-alone program with AddressSanitizer and UBSan, on a short case count."""
-    exe = _build(tmp_path, "shadow_main_san",
-                 ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                  "-fno-omit-frame-pointer"])
+    exe = build(tmp_path, "shadow_main_san", SRC,
+                ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                 "-fno-omit-frame-pointer"])
     env = dict(os.environ, ASAN_OPTIONS="halt_on_error=1:detect_leaks=1:abort_on_error=0",
                UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
     for mutant in ("none", "corner", "nobias", "hide"):

@@ -1,5 +1,5 @@
 """The shadowed-plane tiles' host-callable rule and lists (tile_shadowed_mark, tile_shadowed_entry
-and tile_list_run3, csrc/rt_shadow_table.hpp: what one lane and one wavefront of the table kernel
+and tile_list_run, csrc/rt_shadow_table.hpp: what one lane and one wavefront of the table kernel
 do): tests/tile_shadowed/shadowed_main.cpp, a stand-alone program with its own main, built here
 with g++ like tests/test_tile_lists_host.py's and run on the same 2 000 random frames and on the
 C2 frame.
@@ -13,35 +13,22 @@ keep masks.  Three mutants must be caught: the shadowed class taken when a light
 entry's plane index off by one, and a workgroup with a shadowed wave and a general wave dropped
 from the general list.  CPU only.
 """
-import os
 import re
 import subprocess
 
 import pytest
 
+from host_programs import build, write_frame_file
 from raytracingengine_amd.configs import make_config
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SEED, CASES = 20240607, 2000
-SRC = f"{ROOT}/tests/tile_shadowed/shadowed_main.cpp"
-
-
-def _build(d, name, extra):
-    oracle_o = str(d / f"rt_oracle_{name}.o")
-    subprocess.run(["gcc", "-std=c11", "-O2", "-ffp-contract=off", "-fopenmp", *extra,
-                    f"-I{ROOT}/oracle", "-c", f"{ROOT}/oracle/rt_oracle.c", "-o", oracle_o],
-                   check=True)
-    exe = str(d / name)
-    subprocess.run(["g++", "-std=c++20", "-O2", "-ffp-contract=off", "-Wall", "-Wextra", "-Werror",
-                    "-Wno-unused-function", *extra, f"-I{ROOT}/raytracingengine_amd/csrc",
-                    f"-I{ROOT}/oracle", SRC, oracle_o, "-o", exe, "-fopenmp", "-lm"], check=True)
-    return exe
+SRC = "tests/tile_shadowed/shadowed_main.cpp"
 
 
 @pytest.fixture(scope="module")
 def shadowed_main(tmp_path_factory):
     d = tmp_path_factory.mktemp("tile_shadowed")
-    return _build(d, "shadowed_main", []), d
+    return build(d, "shadowed_main", SRC, []), d
 
 
 def _fields(line):
@@ -80,21 +67,8 @@ def test_mutants_report_violations(shadowed_main, mutant):
 
 def _c2_file(d):
     sc = make_config("c2")
-    cam = sc.camera
     path = d / "c2.txt"
-
-    def hexes(vals):
-        return " ".join(float(v).hex() for v in vals)
-
-    with open(path, "w") as fh:
-        fh.write(f"{cam.width} {cam.height} {hexes((*cam.position, cam.focal, 1e-3))} "
-                 f"{len(sc.spheres)} {len(sc.planes)} {len(sc.lights)}\n")
-        for s in sc.spheres:
-            fh.write(hexes((*s[0], s[1])) + "\n")
-        for p in sc.planes:
-            fh.write(hexes((*p[0], *p[1])) + "\n")
-        for l in sc.lights:
-            fh.write(hexes(l[0]) + "\n")
+    write_frame_file(path, sc, 1e-3)
     return path
 
 

@@ -1,7 +1,7 @@
 // class_main.cpp — stand-alone host check of the tile class words (tile_class_word,
 // csrc/rt_shadow_table.hpp), built and run by tests/test_tile_class_host.py against the C oracle
-// (oracle/rt_oracle.c).  The random frames, the frame file and the oracle's shadow rays are
-// tests/shadow_table/shadow_main.cpp's, included below with its main renamed.
+// (oracle/rt_oracle.c).  The random frames, the frame file, the oracle's shadow rays and the class
+// word itself (class_word) are tests/host_frame.hpp's.
 //
 //   class_main prop SEED CASES [MUTANT]
 //       For every tile that meets the class's geometric conditions (empty cone mask, at most one
@@ -15,63 +15,9 @@
 //   class_main frame FILE
 //       one frame of a real scene (shadow_main's file format): tiles, uniform tiles, workgroups
 //       (two waves side by side) whose tiles are all uniform, and the violations.
-//   class_main shadow ...
-//       shadow_main's own command line.
 // Exit status 0 only when every property holds (mutants: always 0, the caller reads
 // `violations`).
-#define main shadow_table_main
-#include "../shadow_table/shadow_main.cpp"
-#undef main
-
-enum ClassMutant { kClsNone, kClsTwo, kClsHide, kClsIndex };
-
-// the class word of the tile at (x0, yl0), as the table kernel forms it; *all_zero: the tile has
-// an entry and every light's shadow word is 0; *single: the word the tile would get if they were
-static unsigned long long class_word(const Frame& F, uint32_t x0, uint32_t yl0, ClassMutant mut,
-                                     bool* all_zero, unsigned long long* single) {
-    const int ns = static_cast<int>(F.sph.size()), np = static_cast<int>(F.pl.size());
-    const int nl = static_cast<int>(F.lt.size());
-    const double hw = static_cast<double>(F.cam.width) / 2.0,
-                 hh = static_cast<double>(F.cam.height) / 2.0, dz = cam_dz(F.cam);
-    const ConeRect q = cone_tile_rect(x0, yl0, F.cam.width, F.rp);
-    const uint64_t cone = tile_cone_mask(F, x0, yl0);
-    ShadowBound<> B;
-    B.n = 0;
-    B.ok = false;
-    if (cone == 0) {
-        if (mut == kClsHide)
-            B = shadow_tile_bound<kShadowTabPlanes, 4, 1, true>(q, hw, hh, F.cam.position, dz,
-                                                                F.planes.data(), np, F.bias);
-        else
-            B = shadow_tile_bound(q, hw, hh, F.cam.position, dz, F.planes.data(), np, F.bias);
-    }
-    unsigned long long words[kShadowTabLights];
-    *all_zero = true;
-    for (int l = 0; l < nl; ++l) {
-        words[l] = shadow_tile_word(B, F.lt[l].position, F.bias, F.centre.data(), 3,
-                                    F.terms.data() + 7, 8, ns);
-        *all_zero = *all_zero && words[l] == 0;
-    }
-    // s_pln's fourth word, as pk_build_image forms it: the core flag and |n|₁ ≤ 2
-    std::vector<double> pln(4 * static_cast<size_t>(np), 0.0);
-    for (int i = 0; i < np; ++i) {
-        const double* o = &F.planes[8 * static_cast<size_t>(i)];
-        const double n1 = std::fabs(o[3]) + std::fabs(o[4]) + std::fabs(o[5]);
-        pln[4 * static_cast<size_t>(i) + 3] = o[7] != 0.0 && n1 <= 2.0 ? 1.0 : 0.0;
-    }
-    const unsigned long long none[kShadowTabLights] = {0, 0, 0, 0};
-    auto word = [&](const unsigned long long* w) {
-        switch (mut) {
-            case kClsTwo:
-                return tile_class_word<kShadowTabPlanes, 2, 0>(cone, B, w, nl, pln.data(), np);
-            case kClsIndex:
-                return tile_class_word<kShadowTabPlanes, 1, 1>(cone, B, w, nl, pln.data(), np);
-            default: return tile_class_word<kShadowTabPlanes>(cone, B, w, nl, pln.data(), np);
-        }
-    };
-    *single = word(none);
-    return word(words);
-}
+#include "../host_frame.hpp"
 
 struct ClassTally {
     uint64_t tiles = 0, single = 0, uniform = 0, sky = 0, zero_words = 0, workgroups = 0,
@@ -165,38 +111,8 @@ static int run_class_prop(uint64_t seed, int cases, ClassMutant mut) {
 }
 
 static int run_class_frame(const char* path) {
-    // (shadow_main's reader, through a frame file)
-    std::FILE* f = std::fopen(path, "r");
-    if (!f) return 4;
     Frame F{};
-    unsigned W = 0, H = 0, ns = 0, np = 0, nl = 0;
-    if (std::fscanf(f, "%u %u %la %la %la %la %la %u %u %u", &W, &H, &F.cam.position[0],
-                    &F.cam.position[1], &F.cam.position[2], &F.cam.focal, &F.bias, &ns, &np,
-                    &nl) != 10)
-        return 4;
-    if (W == 0 || H == 0 || ns < 1 || ns > 63 || np < 1 || np > unsigned(kShadowTabPlanes) ||
-        nl < 1 || nl > unsigned(kShadowTabLights))
-        return 4;
-    F.cam.width = W;
-    F.cam.height = H;
-    F.cam.aa_samples = 1;
-    F.sph.resize(ns);
-    F.pl.resize(np);
-    F.lt.resize(nl);
-    for (auto& s : F.sph)
-        if (std::fscanf(f, "%la %la %la %la", &s.center[0], &s.center[1], &s.center[2],
-                        &s.radius) != 4)
-            return 4;
-    for (auto& p : F.pl)
-        if (std::fscanf(f, "%la %la %la %la %la %la", &p.point[0], &p.point[1], &p.point[2],
-                        &p.normal[0], &p.normal[1], &p.normal[2]) != 6)
-            return 4;
-    for (auto& l : F.lt)
-        if (std::fscanf(f, "%la %la %la", &l.position[0], &l.position[1], &l.position[2]) != 3)
-            return 4;
-    std::fclose(f);
-    set_rows(F, 0, 0, 1);
-    F.prepare();
+    if (const int r = read_frame(path, F)) return r;
     ClassTally T;
     check_class_frame(F, kClsNone, 0, T);
     print_tally("frame", 1, T);
@@ -204,7 +120,6 @@ static int run_class_frame(const char* path) {
 }
 
 int main(int argc, char** argv) {
-    if (argc >= 2 && !std::strcmp(argv[1], "shadow")) return shadow_table_main(argc - 1, argv + 1);
     if ((argc == 4 || argc == 5) && !std::strcmp(argv[1], "prop")) {
         ClassMutant mut = kClsNone;
         if (argc == 5) {
@@ -217,7 +132,7 @@ int main(int argc, char** argv) {
     }
     if (argc == 3 && !std::strcmp(argv[1], "frame")) return run_class_frame(argv[2]);
     std::fprintf(stderr,
-                 "usage: class_main prop SEED CASES [none|two|hide|index] | class_main frame FILE "
-                 "| class_main shadow ...\n");
+                 "usage: class_main prop SEED CASES [none|two|hide|index] | class_main frame "
+                 "FILE\n");
     return 64;
 }

@@ -1,7 +1,7 @@
 // lists_main.cpp — stand-alone host check of the tile lists (tile_list_run and its helpers,
 // csrc/rt_shadow_table.hpp: the function the table kernel's wavefronts follow), built and run by
 // tests/test_tile_lists_host.py.  The random frames, the frame file and the class words are
-// tests/tile_class/class_main.cpp's, included below.
+// tests/host_frame.hpp's.
 //
 //   lists_main prop SEED CASES [MUTANT]
 //       For every frame: the class word of every tile, then the two lists, run by run.  Every
@@ -15,25 +15,7 @@
 //       the same on one frame of a real scene (shadow_main's file format).
 // Exit status 0 only when every property holds (mutants: always 0, the caller reads
 // `violations`).
-// (class_main.cpp ends with a main of its own, which it names itself: inside a namespace it is an
-// ordinary function; the headers it needs are included first, so their guards keep them out of it)
-#include <cinttypes>
-#include <cmath>
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
-
-#include "rt_cone_table.hpp"
-#include "rt_shadow_table.hpp"
-#include "rt_oracle.h"
-
-namespace tile_class {
-#include "../tile_class/class_main.cpp"
-}
-using namespace rtamd;
-using namespace tile_class;
+#include "../host_frame.hpp"
 
 enum ListMutant { kLstNone, kLstIndex, kLstMixed };
 
@@ -62,7 +44,7 @@ static void check_lists_frame(const Frame& F, ListMutant mut, int tag, ListTally
     std::vector<unsigned long long> uni(tiles);
     std::vector<uint32_t> gen(wgs);
     uint32_t n_uni = 0, n_gen = 0;
-    for (uint32_t pos0 = 0; pos0 < tiles; pos0 += 64) {
+    for (uint32_t pos0 = 0; pos0 < tiles; pos0 += 64) {  // (two lists: no shadowed count)
         if (mut == kLstIndex)
             tile_list_run<1, false>(words.data(), tiles, waves, pos0, origin, uni.data(), &n_uni,
                                     gen.data(), &n_gen);
@@ -141,38 +123,8 @@ static int run_lists_prop(uint64_t seed, int cases, ListMutant mut) {
 }
 
 static int run_lists_frame(const char* path) {
-    // (class_main's reader of shadow_main's frame file)
-    std::FILE* f = std::fopen(path, "r");
-    if (!f) return 4;
     Frame F{};
-    unsigned W = 0, H = 0, ns = 0, np = 0, nl = 0;
-    if (std::fscanf(f, "%u %u %la %la %la %la %la %u %u %u", &W, &H, &F.cam.position[0],
-                    &F.cam.position[1], &F.cam.position[2], &F.cam.focal, &F.bias, &ns, &np,
-                    &nl) != 10)
-        return 4;
-    if (W == 0 || H == 0 || ns < 1 || ns > 63 || np < 1 || np > unsigned(kShadowTabPlanes) ||
-        nl < 1 || nl > unsigned(kShadowTabLights))
-        return 4;
-    F.cam.width = W;
-    F.cam.height = H;
-    F.cam.aa_samples = 1;
-    F.sph.resize(ns);
-    F.pl.resize(np);
-    F.lt.resize(nl);
-    for (auto& s : F.sph)
-        if (std::fscanf(f, "%la %la %la %la", &s.center[0], &s.center[1], &s.center[2],
-                        &s.radius) != 4)
-            return 4;
-    for (auto& p : F.pl)
-        if (std::fscanf(f, "%la %la %la %la %la %la", &p.point[0], &p.point[1], &p.point[2],
-                        &p.normal[0], &p.normal[1], &p.normal[2]) != 6)
-            return 4;
-    for (auto& l : F.lt)
-        if (std::fscanf(f, "%la %la %la", &l.position[0], &l.position[1], &l.position[2]) != 3)
-            return 4;
-    std::fclose(f);
-    set_rows(F, 0, 0, 1);
-    F.prepare();
+    if (const int r = read_frame(path, F)) return r;
     ListTally T;
     check_lists_frame(F, kLstNone, 0, T);
     print_lists("frame", 1, T);

@@ -1,8 +1,8 @@
 // shadowed_main.cpp — stand-alone host check of the shadowed-plane tiles (tile_shadowed_mark,
-// tile_shadowed_entry and tile_list_run3, csrc/rt_shadow_table.hpp: the rule and the three lists
+// tile_shadowed_entry and tile_list_run, csrc/rt_shadow_table.hpp: the rule and the three lists
 // the table kernel's wavefronts follow), built and run by tests/test_tile_shadowed_host.py against
 // the C oracle.  The random frames, the frame file and the oracle's shadow rays are
-// tests/tile_class/class_main.cpp's, included below.
+// tests/host_frame.hpp's.
 //
 //   shadowed_main prop SEED CASES [MUTANT]
 //       For every frame: the table word of every tile as the table kernel forms it (class, keep
@@ -26,23 +26,7 @@
 //       tile_shadowed_census.txt).
 // Exit status 0 only when every property holds (mutants: always 0, the caller reads
 // `violations`).
-#include <cinttypes>
-#include <cmath>
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
-
-#include "rt_cone_table.hpp"
-#include "rt_shadow_table.hpp"
-#include "rt_oracle.h"
-
-namespace tile_class {
-#include "../tile_class/class_main.cpp"
-}
-using namespace rtamd;
-using namespace tile_class;
+#include "../host_frame.hpp"
 
 enum ShMutant { kShNone, kShNoWord, kShIndex, kShMixed };
 
@@ -77,12 +61,7 @@ static TileWord table_word(const Frame& F, uint32_t x0, uint32_t yl0, ShMutant m
         W.keep[l] = shadow_plane_keep(B, F.lt[l].position, F.planes.data(), np, F.cam.position,
                                       F.bias);
     }
-    std::vector<double> pln(4 * static_cast<size_t>(np), 0.0);
-    for (int i = 0; i < np; ++i) {
-        const double* o = &F.planes[8 * static_cast<size_t>(i)];
-        const double n1 = std::fabs(o[3]) + std::fabs(o[4]) + std::fabs(o[5]);
-        pln[4 * static_cast<size_t>(i) + 3] = o[7] != 0.0 && n1 <= 2.0 ? 1.0 : 0.0;
-    }
+    const std::vector<double> pln = plane_flags(F);
     const unsigned long long cls =
         tile_class_word<kShadowTabPlanes>(cone, B, W.sw, nl, pln.data(), np);
     unsigned long long mark;
@@ -134,11 +113,11 @@ static void check_shadowed_frame(const Frame& F, ShMutant mut, int tag, bool ray
     uint32_t n_uni = 0, n_sh = 0, n_gen = 0;
     for (uint32_t pos0 = 0; pos0 < tiles; pos0 += 64) {
         if (mut == kShMixed)
-            tile_list_run3<true>(words.data(), tiles, waves, pos0, origin, uni.data(), &n_uni,
-                                 &n_sh, gen.data(), &n_gen);
+            tile_list_run<0, false, true>(words.data(), tiles, waves, pos0, origin, uni.data(),
+                                          &n_uni, gen.data(), &n_gen, &n_sh);
         else
-            tile_list_run3(words.data(), tiles, waves, pos0, origin, uni.data(), &n_uni, &n_sh,
-                           gen.data(), &n_gen);
+            tile_list_run(words.data(), tiles, waves, pos0, origin, uni.data(), &n_uni,
+                          gen.data(), &n_gen, &n_sh);
     }
     uint32_t want_uni = 0, want_sh = 0;
     for (uint32_t t = 0; t < tiles; ++t) {
@@ -173,7 +152,7 @@ static void check_shadowed_frame(const Frame& F, ShMutant mut, int tag, bool ray
     }
     Shadow S;
     for (uint32_t i = 0; i < n_sh; ++i) {
-        const unsigned long long e = uni[tile_list_shadowed_slot(i, tiles)];
+        const unsigned long long e = uni[TileTabLayout::shadowed_slot(i, tiles)];
         uint32_t t;
         if (!decode(e, t)) continue;
         ++covered[t];
@@ -286,41 +265,6 @@ static int run_shadowed_prop(uint64_t seed, int cases, ShMutant mut) {
     print_shadowed("prop", cases, T);
     if (mut != kShNone) return 0;
     return T.violations ? 1 : 0;
-}
-
-static int read_frame(const char* path, Frame& F) {
-    // (class_main's reader of shadow_main's frame file)
-    std::FILE* f = std::fopen(path, "r");
-    if (!f) return 4;
-    unsigned W = 0, H = 0, ns = 0, np = 0, nl = 0;
-    if (std::fscanf(f, "%u %u %la %la %la %la %la %u %u %u", &W, &H, &F.cam.position[0],
-                    &F.cam.position[1], &F.cam.position[2], &F.cam.focal, &F.bias, &ns, &np,
-                    &nl) != 10)
-        return 4;
-    if (W == 0 || H == 0 || ns < 1 || ns > 63 || np < 1 || np > unsigned(kShadowTabPlanes) ||
-        nl < 1 || nl > unsigned(kShadowTabLights))
-        return 4;
-    F.cam.width = W;
-    F.cam.height = H;
-    F.cam.aa_samples = 1;
-    F.sph.resize(ns);
-    F.pl.resize(np);
-    F.lt.resize(nl);
-    for (auto& s : F.sph)
-        if (std::fscanf(f, "%la %la %la %la", &s.center[0], &s.center[1], &s.center[2],
-                        &s.radius) != 4)
-            return 4;
-    for (auto& p : F.pl)
-        if (std::fscanf(f, "%la %la %la %la %la %la", &p.point[0], &p.point[1], &p.point[2],
-                        &p.normal[0], &p.normal[1], &p.normal[2]) != 6)
-            return 4;
-    for (auto& l : F.lt)
-        if (std::fscanf(f, "%la %la %la", &l.position[0], &l.position[1], &l.position[2]) != 3)
-            return 4;
-    std::fclose(f);
-    set_rows(F, 0, 0, 1);
-    F.prepare();
-    return 0;
 }
 
 static int run_shadowed_frame(const char* path, bool census) {
