@@ -9,10 +9,11 @@ import subprocess
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def build(d, name, src, extra, oracle=True):
+def build(d, name, src, extra, oracle=True, sources=(), cxx_extra=()):
     """Compiles `src` (a path under the repository root) into d/name, with the C oracle unless
     the program does not call it, and returns the executable's path; `extra` goes to both
-    compilers (sanitizer flags)."""
+    compilers (sanitizer flags).  `sources`: further C++ files of the repository to compile in
+    (the library's host code under test); `cxx_extra`: flags they need, for g++ alone."""
     objs = []
     if oracle:
         objs.append(str(d / f"rt_oracle_{name}.o"))
@@ -21,8 +22,9 @@ def build(d, name, src, extra, oracle=True):
                        check=True)
     exe = str(d / name)
     subprocess.run(["g++", "-std=c++20", "-O2", "-ffp-contract=off", "-Wall", "-Wextra", "-Werror",
-                    *extra, f"-I{ROOT}/raytracingengine_amd/csrc", f"-I{ROOT}/oracle",
-                    f"{ROOT}/{src}", *objs, "-o", exe, "-fopenmp", "-lm"], check=True)
+                    *extra, *cxx_extra, f"-I{ROOT}/raytracingengine_amd/csrc", f"-I{ROOT}/oracle",
+                    f"{ROOT}/{src}", *(f"{ROOT}/{s}" for s in sources), *objs, "-o", exe,
+                    "-fopenmp", "-lm"], check=True)
     return exe
 
 

@@ -90,6 +90,14 @@ def _reference(ds, sc, oracle, rows, near=None, far=None):
         assert (typ, idx) == (int(hits[i, 0]), int(hits[i, 1])), i
         if typ:
             assert np.array_equal(o7[:4], hits[i, 2:6]), i  # distance, normal
+    return _expected(sc, hits, len(rows), near, far)
+
+
+def _expected(sc, hits, n, near=None, far=None):
+    """The pass's outputs for n image rows from their rays' closest hits ([n * W, 9] in
+    rt_intersect_rays' layout, the oracle's closest_rays included)."""
+    cam = sc.camera
+    W = cam.width
     hit = hits[:, 0] != 0
     mats = np.concatenate([a["material"]["color"].reshape(-1, 3) for a in
                            (sc.sphere_array(), sc.plane_array(), sc.triangle_array())] +
@@ -101,7 +109,6 @@ def _reference(ds, sc, oracle, rows, near=None, far=None):
     far = cam.far_plane if far is None else far
     with np.errstate(all="ignore"):
         dn = ((t - near) / (far - near)).astype(np.float32)
-    n = len(rows)
     return {
         "depth": t.reshape(n, W),
         "depth_norm": np.where(hit, dn, np.float32(np.inf)).astype(np.float32).reshape(n, W),
