@@ -23,6 +23,11 @@
  *   rt_scatter_rays[_device]       one level of Scene::TraceRay   Scene.h:131-198
  *                                  (what the level adds, and the child rays of Scene.h:178-180 and
  *                                   190-191 with their weights, before they are traced)
+ *   rt_light_transmittance_keyed[_device], rt_direct_light_keyed[_device],
+ *   rt_direct_light_rays_keyed[_device], rt_scatter_rays_keyed[_device]
+ *                                  build-defined: the four entries above with the build-defined area
+ *                                  light's samples appended to directLightning's loop (after
+ *                                  Scene.h:86-124), their random draws under keys the caller supplies
  *   rt_camera_rays[_device]        Rayon Camera::getRay(x, y, AA) const   Math.h:99-121
  *                                  (for every pixel of a frame, with the jitter of one AA sample)
  *   rt_closest_rays[_device]       std::optional<HitInfo> Scene::IntersectClosest(ray) const
@@ -517,9 +522,9 @@ rt_status rt_transmittance_rays_device(rt_context* ctx, const rt_scene* scene,
  *   7. otherwise it is computeTransmittance({p + normal*bias, L}, dist - bias, bias).
  * The three zeros are the reference's `continue`s: that light adds nothing at that point.  The
  * raw T is returned; dropping T <= bias (Scene.h:105) is the shader's decision, not the query's.
- * The caller passes the normal facing the viewer, as TraceRay flips it (Scene.h:146).  Only
- * point lights are served, not the build-defined area light.  A scene without lights returns
- * RT_OK and writes nothing.  opts as for rt_transmittance_rays.  Synchronous. */
+ * The caller passes the normal facing the viewer, as TraceRay flips it (Scene.h:146).  This entry
+ * serves the point lights; rt_light_transmittance_keyed serves the build-defined area light as
+ * well.  A scene without lights returns RT_OK and writes nothing.  opts as for rt_transmittance_rays.  Synchronous. */
 rt_status rt_light_transmittance(rt_context* ctx, const rt_scene* scene, const rt_render_opts* opts,
                                  const double* points, size_t n, double* T_out);
 /* The same on device pointers (d_points: n*6 doubles, d_T: n*n_lights doubles), asynchronous on
@@ -551,8 +556,8 @@ rt_status rt_light_transmittance_device(rt_context* ctx, const rt_scene* scene,
  *                                   directLightning's return value.
  * Every operation is binary64 in the reference's order, so diffuse has no tolerance; where pow is
  * reached, specular and radiance are within 1e-12 * max(1, |value|) of libm's.
- * Only the scene's point lights are read, not the build-defined area light (the rule of
- * rt_light_transmittance).  A scene without lights writes zeros: the outputs have a fixed shape.
+ * This entry reads the scene's point lights; rt_direct_light_keyed reads the build-defined area
+ * light as well.  A scene without lights writes zeros: the outputs have a fixed shape.
  * Of opts only bias and RT_FLAG_NO_BVH are read; opts == NULL gives the defaults (bias 1e-3).
  * RT_ERR_INVALID_ARG: outputs == 0, an unknown bit in outputs, out NULL or a requested output's
  * pointer NULL (pointers of outputs not requested are ignored), NULL inputs with n > 0.
@@ -626,9 +631,9 @@ rt_status rt_direct_light_rays_device(rt_context* ctx, const rt_scene* scene,
  * how a caller ends a composition.  Any max_recursion > 0, the default included, gives the level
  * above.
  * Of opts only max_recursion (its sign), bias and RT_FLAG_NO_BVH are read; opts == NULL gives the
- * defaults.  The build-defined area light is not read, even when attached to the scene (the rule
- * of rt_direct_light and rt_light_transmittance): callers do not supply the pixel and sample keys
- * its random numbers need.
+ * defaults.  This entry does not read the build-defined area light, even when attached to the
+ * scene (the rule of rt_direct_light and rt_light_transmittance): rt_scatter_rays_keyed, which
+ * takes the pixel and sample keys its random numbers need, does.
  * Numerics: child rays, flags and a miss's value carry no tolerance.  A hit's value carries none
  * where directLightning does not reach pow, else it is within 1e-12 * max(1, |value|) of libm's.
  * rw of an opaque material is material.specular bit for bit; fw and rw of a transparent material
@@ -659,6 +664,79 @@ rt_status rt_scatter_rays_device(rt_context* ctx, const rt_scene* scene,
                                  const rt_render_opts* opts, const void* d_rays, size_t n,
                                  int outputs, const struct rt_scatter_out* d_out);
 
+/* The keys of the build-defined area light's draws for a batch of rays or points: what the four
+ * _keyed queries below take next to their sibling's arguments.  The render kernels draw the
+ * point of area sample s of a hit from two uniform numbers of the counter RNG under the key
+ * (opts->seed, pixel, stream, 2s | 2s + 1); a frame uses pixel = y_image*W + x and the AA sample
+ * index, rt_trace_rays pixel = the ray's index and sample 0, both the recursion depth of the hit. */
+typedef struct rt_area_keys {
+    const void* pixel;  /* n uint64 keys, or NULL: element i draws with pixel = i (rt_trace_rays' rule).
+                           Host pointer in the host entries, device pointer in the _device entries. */
+    uint32_t sample;    /* AA sample index s     } stream = 0x10000 + (s << 6) + depth,          */
+    uint32_t depth;     /* recursion depth 0..63 } as the render kernels form it                 */
+} rt_area_keys;
+
+/* The direct-light, shadow and scatter queries with the build-defined area light served
+ * (rt_scene_set_area_light; BASELINE config 5).  Each entry has its sibling's arguments, outputs,
+ * numerics and errors, plus `keys`; its _device twin is asynchronous on the context's stream as
+ * the sibling's.  The struct itself is always host memory and is read before the call returns;
+ * keys == NULL means {NULL, 0, 0}.  RT_ERR_INVALID_ARG in addition to the sibling's: depth > 63
+ * (the streams of neighbouring samples would collide), sample > 0x00FFFFFF (the stream is a
+ * uint32).  Of opts the entries read what the sibling reads, and seed.
+ *
+ * The area samples are appended to directLightning's loop after the point lights, in sample
+ * order s = 0 .. samples-1, into the same diffuse and specular accumulators.  With
+ * k = sqrt(samples), r1 = u01(seed, pixel, stream, 2s), r2 = u01(seed, pixel, stream, 2s + 1):
+ *   fu = ((double)(s % k) + r1) / k;  fv = ((double)(s / k) + r2) / k;
+ *   light point = (corner + edge_u*fu) + edge_v*fv;
+ *   emitted     = color * (intensity / samples);
+ * then steps 1-5 of rt_direct_light with that point and that emitted value.
+ *
+ *   rt_direct_light_keyed, rt_direct_light_rays_keyed: RT_DL_DIFFUSE / RT_DL_SPECULAR are the
+ *     accumulators after the last area sample, RT_DL_RADIANCE their combination as before.
+ *   rt_scatter_rays_keyed: value is formed from that localLight.  Child rays, weights and flags
+ *     do not depend on the keys; a terminal level (max_recursion <= 0) is the sky, as before.
+ *     TraceRay of an area-light scene composes as in rt_scatter_rays, each level asked with
+ *     depth = its recursion level and the pixel keys of the rays its rays descend from.
+ *   rt_light_transmittance_keyed: T_out is n * (n_lights + samples) doubles.  Columns
+ *     0 .. n_lights-1 are rt_light_transmittance's; column n_lights + s is the same seven steps with
+ *     the light point of sample s in place of light.position.  The mean of the last `samples`
+ *     columns is the point's soft visibility.  With no column at all nothing is written.
+ *
+ * A scene without an area light: every keyed entry returns its sibling's bytes; the keys are
+ * validated but otherwise unused, and the light transmittance has n_lights columns. */
+rt_status rt_light_transmittance_keyed(rt_context* ctx, const rt_scene* scene,
+                                       const rt_render_opts* opts, const double* points, size_t n,
+                                       double* T_out, const rt_area_keys* keys);
+rt_status rt_light_transmittance_keyed_device(rt_context* ctx, const rt_scene* scene,
+                                              const rt_render_opts* opts, const void* d_points,
+                                              size_t n, void* d_T, const rt_area_keys* keys);
+rt_status rt_direct_light_keyed(rt_context* ctx, const rt_scene* scene, const rt_render_opts* opts,
+                                const double* points, const rt_material* materials,
+                                size_t n_materials, size_t n, int outputs,
+                                const struct rt_direct_light_out* out, const rt_area_keys* keys);
+rt_status rt_direct_light_keyed_device(rt_context* ctx, const rt_scene* scene,
+                                       const rt_render_opts* opts, const void* d_points,
+                                       const void* d_materials, size_t n_materials, size_t n,
+                                       int outputs, const struct rt_direct_light_out* d_out,
+                                       const rt_area_keys* keys);
+rt_status rt_direct_light_rays_keyed(rt_context* ctx, const rt_scene* scene,
+                                     const rt_render_opts* opts, const double* rays, size_t n,
+                                     int outputs, const struct rt_direct_light_out* out,
+                                     const rt_area_keys* keys);
+rt_status rt_direct_light_rays_keyed_device(rt_context* ctx, const rt_scene* scene,
+                                            const rt_render_opts* opts, const void* d_rays,
+                                            size_t n, int outputs,
+                                            const struct rt_direct_light_out* d_out,
+                                            const rt_area_keys* keys);
+rt_status rt_scatter_rays_keyed(rt_context* ctx, const rt_scene* scene, const rt_render_opts* opts,
+                                const double* rays, size_t n, int outputs,
+                                const struct rt_scatter_out* out, const rt_area_keys* keys);
+rt_status rt_scatter_rays_keyed_device(rt_context* ctx, const rt_scene* scene,
+                                       const rt_render_opts* opts, const void* d_rays, size_t n,
+                                       int outputs, const struct rt_scatter_out* d_out,
+                                       const rt_area_keys* keys);
+
 /* Camera rays: Camera::getRay(x, y, sample > 0 && aa_samples > 1) (Math.h:99-121) for every
  * pixel of the row set of opts — the primary rays the render kernels trace for AA sample
  * `sample` of a frame of this camera, seed and row set.  No scene is involved.
@@ -671,8 +749,8 @@ rt_status rt_scatter_rays_device(rt_context* ctx, const rt_scene* scene,
  * (opts->seed, y_image*W + x, sample, 0 | 1) to the screen x and y, the render kernels' own
  * draw.  So RenderImage is expressible from this interface:
  *   render(x, y) == (TraceRay(ray of sample 0) + ... + TraceRay(ray of sample N-1)) / N
- * summed in that order (Scene.h:289-300), for scenes without an area light (whose random numbers
- * are keyed by the pixel, not by a ray's index).
+ * summed in that order (Scene.h:289-300); for a scene with an area light, whose random numbers are
+ * keyed by the pixel and the sample, from the _keyed queries above under those keys.
  * Of opts only the row set and seed are read; opts == NULL gives the defaults.
  * RT_ERR_INVALID_ARG: a NULL context, camera or output, zero width or height, a row set outside
  * the image, sample < 0 or sample >= max(1, aa_samples).  RT_ERR_UNSUPPORTED: more than 2^31

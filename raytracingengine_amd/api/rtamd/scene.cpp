@@ -384,12 +384,36 @@ std::vector<double> Scene::ComputeTransmittance(const std::vector<Rayon>& rays, 
     return ComputeTransmittance(rays, std::vector<double>(rays.size(), maxDist), bias);
 }
 
+namespace {
+// The C-ABI record of `keys` for n elements: no pixel keys (element i draws with pixel = i), or
+// one per element.
+rt_area_keys areaKeysDesc(const rtamd::AreaKeys& keys, size_t n, const char* who) {
+    if (!keys.pixel.empty() && keys.pixel.size() != n)
+        throw std::invalid_argument(std::string(who) + ": no pixel keys, or one per element");
+    return rt_area_keys{keys.pixel.empty() ? nullptr : keys.pixel.data(), keys.sample, keys.depth};
+}
+}  // namespace
+
 std::vector<double> Scene::LightTransmittance(const std::vector<Vec3>& points,
                                               const std::vector<Vec3>& normals,
                                               double bias) const {
+    return lightTransmittance(points, normals, bias, nullptr);
+}
+
+std::vector<double> Scene::LightTransmittance(const std::vector<Vec3>& points,
+                                              const std::vector<Vec3>& normals,
+                                              const rtamd::AreaKeys& keys, double bias) const {
+    return lightTransmittance(points, normals, bias, &keys);
+}
+
+std::vector<double> Scene::lightTransmittance(const std::vector<Vec3>& points,
+                                              const std::vector<Vec3>& normals, double bias,
+                                              const rtamd::AreaKeys* keys) const {
     if (normals.size() != points.size())
         throw std::invalid_argument("LightTransmittance: one normal per point");
-    std::vector<double> out(points.size() * lights.size());
+    const size_t cols =
+        lights.size() + (keys && areaLight_ ? static_cast<size_t>(areaLight_->samples) : 0);
+    std::vector<double> out(points.size() * cols);
     if (out.empty()) return out;
     rt_scene* sc = upload();
     std::vector<double> pn(6 * points.size());
@@ -400,8 +424,16 @@ std::vector<double> Scene::LightTransmittance(const std::vector<Vec3>& points,
     }
     rt_render_opts o = optsDesc(RT_TONEMAP_NONE);
     o.bias = bias;
-    rtamd::check(rt_light_transmittance(dev_->ctx, sc, &o, pn.data(), points.size(), out.data()),
-                 "rt_light_transmittance");
+    if (keys) {
+        const rt_area_keys k = areaKeysDesc(*keys, points.size(), "LightTransmittance");
+        rtamd::check(rt_light_transmittance_keyed(dev_->ctx, sc, &o, pn.data(), points.size(),
+                                                  out.data(), &k),
+                     "rt_light_transmittance_keyed");
+    } else {
+        rtamd::check(rt_light_transmittance(dev_->ctx, sc, &o, pn.data(), points.size(),
+                                            out.data()),
+                     "rt_light_transmittance");
+    }
     return out;
 }
 
@@ -460,6 +492,20 @@ static std::vector<Vec3> unpackVec3(const std::vector<double>& v) {
 std::vector<Vec3> Scene::DirectLightning(const std::vector<HitInfo>& hits,
                                          const std::vector<Vec3>& viewDirs,
                                          const std::vector<Vec3>& normals, double bias) const {
+    return directLightning(hits, viewDirs, normals, bias, nullptr);
+}
+
+std::vector<Vec3> Scene::DirectLightning(const std::vector<HitInfo>& hits,
+                                         const std::vector<Vec3>& viewDirs,
+                                         const std::vector<Vec3>& normals,
+                                         const rtamd::AreaKeys& keys, double bias) const {
+    return directLightning(hits, viewDirs, normals, bias, &keys);
+}
+
+std::vector<Vec3> Scene::directLightning(const std::vector<HitInfo>& hits,
+                                         const std::vector<Vec3>& viewDirs,
+                                         const std::vector<Vec3>& normals, double bias,
+                                         const rtamd::AreaKeys* keys) const {
     if (viewDirs.size() != hits.size() || normals.size() != hits.size())
         throw std::invalid_argument("DirectLightning: one viewDir and one normal per hit");
     const size_t n = hits.size();
@@ -479,13 +525,30 @@ std::vector<Vec3> Scene::DirectLightning(const std::vector<HitInfo>& hits,
     rt_render_opts o = optsDesc(RT_TONEMAP_NONE);
     o.bias = bias;
     const rt_direct_light_out out{rgb.data(), nullptr, nullptr};
-    rtamd::check(rt_direct_light(dev_->ctx, sc, &o, pts.data(), mats.data(), n, n, RT_DL_RADIANCE,
-                                 &out),
-                 "rt_direct_light");
+    if (keys) {
+        const rt_area_keys k = areaKeysDesc(*keys, n, "DirectLightning");
+        rtamd::check(rt_direct_light_keyed(dev_->ctx, sc, &o, pts.data(), mats.data(), n, n,
+                                           RT_DL_RADIANCE, &out, &k),
+                     "rt_direct_light_keyed");
+    } else {
+        rtamd::check(rt_direct_light(dev_->ctx, sc, &o, pts.data(), mats.data(), n, n,
+                                     RT_DL_RADIANCE, &out),
+                     "rt_direct_light");
+    }
     return unpackVec3(rgb);
 }
 
 std::vector<Vec3> Scene::DirectLightning(const std::vector<Rayon>& rays, double bias) const {
+    return directLightningRays(rays, bias, nullptr);
+}
+
+std::vector<Vec3> Scene::DirectLightning(const std::vector<Rayon>& rays,
+                                         const rtamd::AreaKeys& keys, double bias) const {
+    return directLightningRays(rays, bias, &keys);
+}
+
+std::vector<Vec3> Scene::directLightningRays(const std::vector<Rayon>& rays, double bias,
+                                             const rtamd::AreaKeys* keys) const {
     if (rays.empty()) return {};
     rt_scene* sc = upload();
     static_assert(sizeof(Rayon) == 6 * sizeof(double), "Rayon is not six packed doubles");
@@ -493,14 +556,30 @@ std::vector<Vec3> Scene::DirectLightning(const std::vector<Rayon>& rays, double 
     rt_render_opts o = optsDesc(RT_TONEMAP_NONE);
     o.bias = bias;
     const rt_direct_light_out out{rgb.data(), nullptr, nullptr};
-    rtamd::check(rt_direct_light_rays(dev_->ctx, sc, &o,
-                                      reinterpret_cast<const double*>(rays.data()), rays.size(),
-                                      RT_DL_RADIANCE, &out),
-                 "rt_direct_light_rays");
+    const double* r = reinterpret_cast<const double*>(rays.data());
+    if (keys) {
+        const rt_area_keys k = areaKeysDesc(*keys, rays.size(), "DirectLightning");
+        rtamd::check(rt_direct_light_rays_keyed(dev_->ctx, sc, &o, r, rays.size(), RT_DL_RADIANCE,
+                                                &out, &k),
+                     "rt_direct_light_rays_keyed");
+    } else {
+        rtamd::check(rt_direct_light_rays(dev_->ctx, sc, &o, r, rays.size(), RT_DL_RADIANCE, &out),
+                     "rt_direct_light_rays");
+    }
     return unpackVec3(rgb);
 }
 
 rtamd::Scatter Scene::ScatterRays(const std::vector<Rayon>& rays, bool terminal) const {
+    return scatterRays(rays, terminal, nullptr);
+}
+
+rtamd::Scatter Scene::ScatterRays(const std::vector<Rayon>& rays, const rtamd::AreaKeys& keys,
+                                  bool terminal) const {
+    return scatterRays(rays, terminal, &keys);
+}
+
+rtamd::Scatter Scene::scatterRays(const std::vector<Rayon>& rays, bool terminal,
+                                  const rtamd::AreaKeys* keys) const {
     rtamd::Scatter s;
     const size_t n = rays.size();
     if (n == 0) return s;
@@ -515,9 +594,14 @@ rtamd::Scatter Scene::ScatterRays(const std::vector<Rayon>& rays, bool terminal)
     o.max_recursion = terminal ? 0 : 1;
     const rt_scatter_out out{s.value.data(), s.refraction.data(), s.reflection.data(), w.data(),
                              s.flags.data()};
-    rtamd::check(rt_scatter_rays(dev_->ctx, sc, &o, reinterpret_cast<const double*>(rays.data()), n,
-                                 RT_SC_ALL, &out),
-                 "rt_scatter_rays");
+    const double* r = reinterpret_cast<const double*>(rays.data());
+    if (keys) {
+        const rt_area_keys k = areaKeysDesc(*keys, n, "ScatterRays");
+        rtamd::check(rt_scatter_rays_keyed(dev_->ctx, sc, &o, r, n, RT_SC_ALL, &out, &k),
+                     "rt_scatter_rays_keyed");
+    } else {
+        rtamd::check(rt_scatter_rays(dev_->ctx, sc, &o, r, n, RT_SC_ALL, &out), "rt_scatter_rays");
+    }
     s.refractionWeight.resize(n);
     s.reflectionWeight.resize(n);
     for (size_t i = 0; i < n; ++i) {

@@ -88,6 +88,14 @@ struct Hits {
     std::vector<Vec3> point;            // HitInfo::hitPoint
     std::vector<rt_material> material;  // HitInfo::material, as uploaded
 };
+// The keys of the area light's draws for a batch of rays or points (rt_area_keys): `pixel` one key
+// per element, or empty (element i draws with pixel = i, as TraceRays keys them); `sample` the AA
+// sample index and `depth` the recursion depth of the batch.  A frame's draws are keyed by
+// pixel = GetPixelIndex(x, y), the sample and the level of the hit.
+struct AreaKeys {
+    std::vector<uint64_t> pixel;
+    uint32_t sample = 0, depth = 0;
+};
 }  // namespace rtamd
 
 class Scene {
@@ -117,6 +125,18 @@ class Scene {
     rt_camera cameraDesc() const;
     rt_render_opts optsDesc(int tonemap) const;
     void touch() { ++version_; }
+    // the batch queries below with keys (the area light served) or without (nullptr)
+    std::vector<double> lightTransmittance(const std::vector<Vec3>& points,
+                                           const std::vector<Vec3>& normals, double bias,
+                                           const rtamd::AreaKeys* keys) const;
+    std::vector<Vec3> directLightning(const std::vector<HitInfo>& hits,
+                                      const std::vector<Vec3>& viewDirs,
+                                      const std::vector<Vec3>& normals, double bias,
+                                      const rtamd::AreaKeys* keys) const;
+    std::vector<Vec3> directLightningRays(const std::vector<Rayon>& rays, double bias,
+                                          const rtamd::AreaKeys* keys) const;
+    rtamd::Scatter scatterRays(const std::vector<Rayon>& rays, bool terminal,
+                               const rtamd::AreaKeys* keys) const;
 
 public:
     explicit Scene(const Camera& camera_);
@@ -169,6 +189,13 @@ public:
     std::vector<double> LightTransmittance(const std::vector<Vec3>& points,
                                            const std::vector<Vec3>& normals,
                                            double bias = 1e-3) const;
+    // The same with the area light of SetAreaLight served (rt_light_transmittance_keyed):
+    // [i * (lights + samples) + c], the area light's samples after the lights, their points drawn
+    // under `keys`; the mean of a point's last `samples` values is its soft visibility.  Without
+    // an area light: the answer above.
+    std::vector<double> LightTransmittance(const std::vector<Vec3>& points,
+                                           const std::vector<Vec3>& normals,
+                                           const rtamd::AreaKeys& keys, double bias = 1e-3) const;
     // IntersectClosest (Scene.h:218-257) on the host, over the shapes' GetHitInfoAt members in the
     // reference's visiting order (spheres, planes, triangles, models; a later shape wins only
     // when strictly closer): the HitInfo of the device method, without a device.
@@ -177,7 +204,8 @@ public:
     // the host, over the point lights in the reference's operation order, each shadow ray through
     // the host ComputeTransmittance(ray, maxDist, bias): the values of the batch overloads (where
     // std::pow is reached, within an ulp or two of them).  Reads hit.hitPoint and hit.material;
-    // normalIn faces the viewer.  The area light of SetAreaLight is not read.
+    // normalIn faces the viewer.  The area light of SetAreaLight is not read here; the batch
+    // overloads that take rtamd::AreaKeys read it.
     Vec3 DirectLightning(const HitInfo& hit, const Vec3& viewDir, const Vec3& normalIn,
                          double bias = 1e-3) const;
     // The same for every hit in one launch (rt_direct_light): one viewDir and one normal per hit
@@ -185,16 +213,30 @@ public:
     std::vector<Vec3> DirectLightning(const std::vector<HitInfo>& hits,
                                       const std::vector<Vec3>& viewDirs,
                                       const std::vector<Vec3>& normals, double bias = 1e-3) const;
+    // The same with the area light's samples appended after the point lights, drawn under `keys`
+    // (rt_direct_light_keyed).
+    std::vector<Vec3> DirectLightning(const std::vector<HitInfo>& hits,
+                                      const std::vector<Vec3>& viewDirs,
+                                      const std::vector<Vec3>& normals, const rtamd::AreaKeys& keys,
+                                      double bias = 1e-3) const;
     // directLightning at the first hit of every ray, as TraceRay calls it (Scene.h:136-147, 168),
     // in one launch (rt_direct_light_rays): the hit primitive's material, the normal flipped
     // against the ray, viewDir = -ray.direction.normalize().  (0, 0, 0) where a ray hits nothing.
     std::vector<Vec3> DirectLightning(const std::vector<Rayon>& rays, double bias = 1e-3) const;
+    // ... with the area light (rt_direct_light_rays_keyed).
+    std::vector<Vec3> DirectLightning(const std::vector<Rayon>& rays, const rtamd::AreaKeys& keys,
+                                      double bias = 1e-3) const;
     // One TraceRay level per ray, before its children are traced, in one launch
     // (rt_scatter_rays): what the level adds, the two child rays, their weights and which of them
     // exist.  terminal: every ray is at the recursion limit (Scene.h:132-134): the sky, no
     // intersection, no children — how a caller ends a composition.  The bias is the renderer's
     // (1e-3); maxRecursion is not read, the method never recurses.
     rtamd::Scatter ScatterRays(const std::vector<Rayon>& rays, bool terminal = false) const;
+    // The same with the area light in the level's value (rt_scatter_rays_keyed).  RenderImage of
+    // an area-light scene composes from it: level k asked with keys.depth = k, keys.sample = the
+    // AA sample, and for every ray the pixel key of the camera ray it descends from.
+    rtamd::Scatter ScatterRays(const std::vector<Rayon>& rays, const rtamd::AreaKeys& keys,
+                               bool terminal = false) const;
     // TraceRay(ray, 0, bias) for every ray in one launch (rt_trace_rays), with maxRecursion.
     std::vector<Vec3> TraceRays(const std::vector<Rayon>& rays, double bias = 1e-3) const;
     // camera.getRay(x, y, sample > 0 && antiAliasingAmount > 1) for every pixel in one launch

@@ -7,10 +7,13 @@
 //   triangle v0(3) v1(3) v2(3) translation(3) <material>
 //   model  ntri tx ty tz <material>   followed by ntri lines "v x0 y0 z0 x1 y1 z1 x2 y2 z2"
 //   light  px py pz r g b intensity
+//   arealight corner(3) edge_u(3) edge_v(3) r g b intensity samples   (build-defined, optional:
+//          written by SceneData.to_text(area_light=True))
 // Doubles are parsed with strtod, so repr()-formatted values round-trip exactly.
 #pragma once
 
 #include <fstream>
+#include <optional>
 #include <sstream>
 #include <stdexcept>
 #include <string>
@@ -27,6 +30,7 @@ struct LoadedScene {
     std::vector<Triangle> triangles;
     std::vector<Model> models;
     std::vector<Light> lights;
+    std::optional<rt_area_light> areaLight;
 
     Scene build() const {
         Scene s(camera);
@@ -35,6 +39,7 @@ struct LoadedScene {
         for (const auto& x : triangles) s.AddTriangle(x);
         for (const auto& x : models) s.AddModel(x);
         for (const auto& x : lights) s.AddLight(x);
+        if (areaLight) s.SetAreaLight(areaLight);
         return s;
     }
 };
@@ -105,6 +110,13 @@ inline LoadedScene load_scene_file(const std::string& path) {
             const Vec3 p = vec(s), c = vec(s);
             const double i = num(s);
             L.lights.emplace_back(p, c, i);
+        } else if (tag == "arealight") {
+            rt_area_light a{};
+            for (double* v : {a.corner, a.edge_u, a.edge_v, a.color})
+                for (int k = 0; k < 3; ++k) v[k] = num(s);
+            a.intensity = num(s);
+            a.samples = static_cast<int32_t>(num(s));
+            L.areaLight = a;
         }
     }
     return L;

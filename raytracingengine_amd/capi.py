@@ -103,6 +103,10 @@ EXPORTED = [
     "rt_direct_light", "rt_direct_light_device",
     "rt_direct_light_rays", "rt_direct_light_rays_device",
     "rt_scatter_rays", "rt_scatter_rays_device",
+    "rt_light_transmittance_keyed", "rt_light_transmittance_keyed_device",
+    "rt_direct_light_keyed", "rt_direct_light_keyed_device",
+    "rt_direct_light_rays_keyed", "rt_direct_light_rays_keyed_device",
+    "rt_scatter_rays_keyed", "rt_scatter_rays_keyed_device",
     "rt_camera_rays", "rt_camera_rays_device",
     "rt_closest_rays", "rt_closest_rays_device",
     "rt_trace_rays_device",
@@ -185,6 +189,47 @@ class ScatterPtrs(ctypes.Structure):
 class ClosestPtrs(ctypes.Structure):
     """struct rt_closest_out: one pointer per output, in RT_CH_* bit order."""
     _fields_ = [(name, ctypes.c_void_p) for name, *_ in CH_OUTPUTS]
+
+
+class AreaKeysRec(ctypes.Structure):
+    """struct rt_area_keys."""
+    _fields_ = [("pixel", ctypes.c_void_p), ("sample", ctypes.c_uint32),
+                ("depth", ctypes.c_uint32)]
+
+
+class AreaKeys:
+    """The keys of the area light's draws for a batch (rt_area_keys): `pixel` one key per element
+    or None (element i draws with pixel = i, as trace_rays), `sample` the AA sample index and
+    `depth` the recursion depth of the batch.  pixel on the host: anything
+    np.asarray(..., np.uint64) takes, of length n; on the device: a contiguous torch.int64 tensor
+    of n elements on the context's device, its bits read as uint64."""
+
+    def __init__(self, pixel=None, sample: int = 0, depth: int = 0):
+        self.pixel, self.sample, self.depth = pixel, int(sample), int(depth)
+
+    def at_depth(self, depth: int, pixel=None) -> "AreaKeys":
+        return AreaKeys(self.pixel if pixel is None else pixel, self.sample, depth)
+
+    def _host(self, n: int):
+        """(the record, the array it points into) for a host entry of n elements."""
+        px = None
+        if self.pixel is not None:
+            px = np.ascontiguousarray(np.asarray(self.pixel, np.uint64).reshape(-1))
+            if len(px) != n:
+                raise ValueError("area_keys.pixel: n keys")
+        ptr = None if px is None or n == 0 else px.ctypes.data
+        return AreaKeysRec(ptr, self.sample, self.depth), px
+
+    def _device(self, n: int, dev):
+        """The record for a _device entry of n elements on `dev`."""
+        if self.pixel is None:
+            return AreaKeysRec(None, self.sample, self.depth)
+        import torch
+        if not torch.is_tensor(self.pixel):
+            raise ValueError("area_keys.pixel: a contiguous int64 tensor on the context's device")
+        if _checked_input(self.pixel, dev, torch.int64, 1, "area_keys.pixel") != n:
+            raise ValueError("area_keys.pixel: n keys")
+        return AreaKeysRec(self.pixel.data_ptr() if n else None, self.sample, self.depth)
 
 
 # The records of selectable outputs by the prefix of their bits: the rows (name, bit, element
@@ -352,6 +397,16 @@ def load_library(path: str = LIB_PATH):
         "rt_direct_light_rays_device": [vp, vp, vp, vp, ctypes.c_size_t, i32, vp],
         "rt_scatter_rays": [vp, vp, vp, vp, ctypes.c_size_t, i32, vp],
         "rt_scatter_rays_device": [vp, vp, vp, vp, ctypes.c_size_t, i32, vp],
+        "rt_light_transmittance_keyed": [vp, vp, vp, vp, ctypes.c_size_t, vp, vp],
+        "rt_light_transmittance_keyed_device": [vp, vp, vp, vp, ctypes.c_size_t, vp, vp],
+        "rt_direct_light_keyed": [vp, vp, vp, vp, vp, ctypes.c_size_t, ctypes.c_size_t, i32, vp,
+                                  vp],
+        "rt_direct_light_keyed_device": [vp, vp, vp, vp, vp, ctypes.c_size_t, ctypes.c_size_t,
+                                         i32, vp, vp],
+        "rt_direct_light_rays_keyed": [vp, vp, vp, vp, ctypes.c_size_t, i32, vp, vp],
+        "rt_direct_light_rays_keyed_device": [vp, vp, vp, vp, ctypes.c_size_t, i32, vp, vp],
+        "rt_scatter_rays_keyed": [vp, vp, vp, vp, ctypes.c_size_t, i32, vp, vp],
+        "rt_scatter_rays_keyed_device": [vp, vp, vp, vp, ctypes.c_size_t, i32, vp, vp],
         "rt_camera_rays": [vp, vp, vp, i32, vp],
         "rt_camera_rays_device": [vp, vp, vp, i32, vp],
         "rt_closest_rays": [vp, vp, vp, vp, ctypes.c_size_t, i32, vp],
@@ -443,10 +498,12 @@ def default_opts(**kw) -> RenderOpts:
     return o
 
 
-def _query_opts(bias=None, no_bvh: bool = False, max_recursion=None) -> RenderOpts:
+def _query_opts(bias=None, no_bvh: bool = False, max_recursion=None, seed=None) -> RenderOpts:
     """The options of a batch query: the defaults, RT_FLAG_NO_BVH alone in the flags, and the
-    bias and max_recursion where the query takes them."""
+    bias, max_recursion and seed where the query takes them."""
     o = default_opts(flags=RT_FLAG_NO_BVH if no_bvh else 0)
+    if seed is not None:
+        o.seed = seed
     if bias is not None:
         o.bias = bias
     if max_recursion is not None:
@@ -734,69 +791,97 @@ class DeviceScene:
                                                  out.data_ptr() if n else None))
         return out
 
+    def _light_columns(self, area_keys) -> int:
+        """Columns of the light-transmittance table: the point lights, and with keys the attached
+        area light's samples after them."""
+        keyed = area_keys is not None and self._area is not None
+        return len(self._arrays[3]) + (int(self._area["samples"][0]) if keyed else 0)
+
     def light_transmittance(self, points: np.ndarray, bias: float = 1e-3,
-                            no_bvh: bool = False) -> np.ndarray:
+                            no_bvh: bool = False, area_keys=None, seed=None) -> np.ndarray:
         """directLightning's shadow rays (rt_light_transmittance): points [n,6] {p, normal}, the
         normal facing the viewer -> float64 [n, n_lights], the transmittance from each point to
-        each point light (0.0 where the reference skips the light)."""
+        each point light (0.0 where the reference skips the light).  area_keys (an AreaKeys; the
+        draws under `seed`): rt_light_transmittance_keyed, [n, n_lights + samples] with the area
+        light's samples after the lights."""
         points, n = _host_rows(points, 6)
-        out = np.empty((n, len(self._arrays[3])), np.float64)
-        o = _query_opts(bias, no_bvh)
-        _check(_lib.rt_light_transmittance(self.ctx.handle, self._h, ctypes.byref(o),
-                                           points.ctypes.data if n else None, n,
-                                           out.ctypes.data if out.size else None))
+        out = np.empty((n, self._light_columns(area_keys)), np.float64)
+        o = _query_opts(bias, no_bvh, seed=seed)
+        args = (self.ctx.handle, self._h, ctypes.byref(o), points.ctypes.data if n else None, n,
+                out.ctypes.data if out.size else None)
+        if area_keys is None:
+            _check(_lib.rt_light_transmittance(*args))
+        else:
+            rec, _keep = area_keys._host(n)
+            _check(_lib.rt_light_transmittance_keyed(*args, ctypes.byref(rec)))
         return out
 
     def light_transmittance_device(self, points, out=None, bias: float = 1e-3,
-                                   no_bvh: bool = False):
+                                   no_bvh: bool = False, area_keys=None, seed=None):
         """Asynchronous rt_light_transmittance_device on the context's stream: points a
         contiguous float64 [n,6] tensor on this context's device.  Returns `out`, a float64
-        [n, n_lights] tensor (made when None; a given one needs at least n*n_lights elements)."""
+        [n, n_lights] tensor (made when None; a given one needs at least n*n_lights elements).
+        area_keys: rt_light_transmittance_keyed_device, n_lights + samples columns."""
         import torch
         dev = self._device()
         n = _checked_input(points, dev, torch.float64, 6, "points")
-        nl = len(self._arrays[3])
-        out = _out_tensor(out, dev, torch.float64, (n, nl), need="n*n_lights")
-        o = _query_opts(bias, no_bvh)
-        _check(_lib.rt_light_transmittance_device(self.ctx.handle, self._h, ctypes.byref(o),
-                                                  points.data_ptr() if n else None, n,
-                                                  out.data_ptr() if n * nl else None))
+        nl = self._light_columns(area_keys)
+        out = _out_tensor(out, dev, torch.float64, (n, nl), need="n*columns")
+        o = _query_opts(bias, no_bvh, seed=seed)
+        args = (self.ctx.handle, self._h, ctypes.byref(o), points.data_ptr() if n else None, n,
+                out.data_ptr() if n * nl else None)
+        if area_keys is None:
+            _check(_lib.rt_light_transmittance_device(*args))
+        else:
+            rec = area_keys._device(n, dev)
+            _check(_lib.rt_light_transmittance_keyed_device(*args, ctypes.byref(rec)))
         return out
 
     def direct_light(self, points: np.ndarray, materials, outputs: int = DL_RADIANCE,
-                     bias: float = 1e-3, no_bvh: bool = False) -> dict:
+                     bias: float = 1e-3, no_bvh: bool = False, area_keys=None, seed=None) -> dict:
         """Batch directLightning (rt_direct_light): points [n,9] {p, normal facing the viewer,
         view}; materials a scene.Material or seven values (shared by all points) or an [n,7]
         array -> {"radiance" | "diffuse" | "specular": float64 [n,3]} for the DL_* bits of
-        `outputs`."""
+        `outputs`.  area_keys (an AreaKeys; the draws under `seed`): rt_direct_light_keyed, the
+        area light's samples after the point lights."""
         points, n = _host_rows(points, 9)
         m = material_rows(materials, n)
         res, ptrs = _outputs("DL", outputs, n)
-        o = _query_opts(bias, no_bvh)
-        _check(_lib.rt_direct_light(self.ctx.handle, self._h, ctypes.byref(o),
-                                    points.ctypes.data if n else None, m.ctypes.data, m.shape[0],
-                                    n, outputs, ctypes.byref(ptrs)))
+        o = _query_opts(bias, no_bvh, seed=seed)
+        args = (self.ctx.handle, self._h, ctypes.byref(o), points.ctypes.data if n else None,
+                m.ctypes.data, m.shape[0], n, outputs, ctypes.byref(ptrs))
+        if area_keys is None:
+            _check(_lib.rt_direct_light(*args))
+        else:
+            rec, _keep = area_keys._host(n)
+            _check(_lib.rt_direct_light_keyed(*args, ctypes.byref(rec)))
         return res
 
     def direct_light_rays(self, rays: np.ndarray, outputs: int = DL_RADIANCE, bias: float = 1e-3,
-                          no_bvh: bool = False) -> dict:
+                          no_bvh: bool = False, area_keys=None, seed=None) -> dict:
         """directLightning at the first hit of every ray (rt_direct_light_rays), with the hit
-        primitive's material: rays [n,6] -> the dict of direct_light; zeros where a ray misses."""
+        primitive's material: rays [n,6] -> the dict of direct_light; zeros where a ray misses.
+        area_keys: rt_direct_light_rays_keyed."""
         rays, n = _host_rows(rays, 6)
         res, ptrs = _outputs("DL", outputs, n)
-        o = _query_opts(bias, no_bvh)
-        _check(_lib.rt_direct_light_rays(self.ctx.handle, self._h, ctypes.byref(o),
-                                         rays.ctypes.data if n else None, n, outputs,
-                                         ctypes.byref(ptrs)))
+        o = _query_opts(bias, no_bvh, seed=seed)
+        args = (self.ctx.handle, self._h, ctypes.byref(o), rays.ctypes.data if n else None, n,
+                outputs, ctypes.byref(ptrs))
+        if area_keys is None:
+            _check(_lib.rt_direct_light_rays(*args))
+        else:
+            rec, _keep = area_keys._host(n)
+            _check(_lib.rt_direct_light_rays_keyed(*args, ctypes.byref(rec)))
         return res
 
     def direct_light_device(self, points, materials, outputs: int = DL_RADIANCE, out=None,
-                            bias: float = 1e-3, no_bvh: bool = False) -> dict:
+                            bias: float = 1e-3, no_bvh: bool = False, area_keys=None,
+                            seed=None) -> dict:
         """Asynchronous rt_direct_light_device on the context's stream: points a contiguous
         float64 [n,9] tensor on this context's device; materials a contiguous float64 [n,7]
         tensor there, or a scene.Material / seven values on the host (shared by all points, passed
         in the kernel arguments).  Returns a dict of float64 [n,3] tensors; `out` may hold a
-        tensor per requested name to write into."""
+        tensor per requested name to write into.  area_keys: rt_direct_light_keyed_device."""
         import torch
         dev = self._device()
         n = _checked_input(points, dev, torch.float64, 9, "points")
@@ -810,55 +895,76 @@ class DeviceScene:
             host = material_rows(materials, 1)
             m_ptr, n_m = host.ctypes.data, 1
         res, ptrs = _outputs("DL", outputs, n, dev, out)
-        o = _query_opts(bias, no_bvh)
-        _check(_lib.rt_direct_light_device(self.ctx.handle, self._h, ctypes.byref(o),
-                                           points.data_ptr() if n else None, m_ptr, n_m, n,
-                                           outputs, ctypes.byref(ptrs)))
+        o = _query_opts(bias, no_bvh, seed=seed)
+        args = (self.ctx.handle, self._h, ctypes.byref(o), points.data_ptr() if n else None,
+                m_ptr, n_m, n, outputs, ctypes.byref(ptrs))
+        if area_keys is None:
+            _check(_lib.rt_direct_light_device(*args))
+        else:
+            rec = area_keys._device(n, dev)
+            _check(_lib.rt_direct_light_keyed_device(*args, ctypes.byref(rec)))
         return res
 
     def direct_light_rays_device(self, rays, outputs: int = DL_RADIANCE, out=None,
-                                 bias: float = 1e-3, no_bvh: bool = False) -> dict:
+                                 bias: float = 1e-3, no_bvh: bool = False, area_keys=None,
+                                 seed=None) -> dict:
         """Asynchronous rt_direct_light_rays_device on the context's stream: rays a contiguous
         float64 [n,6] tensor on this context's device.  Returns a dict of float64 [n,3] tensors;
-        `out` may hold a tensor per requested name to write into."""
+        `out` may hold a tensor per requested name to write into.  area_keys:
+        rt_direct_light_rays_keyed_device."""
         import torch
         dev = self._device()
         n = _checked_input(rays, dev, torch.float64, 6, "rays")
         res, ptrs = _outputs("DL", outputs, n, dev, out)
-        o = _query_opts(bias, no_bvh)
-        _check(_lib.rt_direct_light_rays_device(self.ctx.handle, self._h, ctypes.byref(o),
-                                                rays.data_ptr() if n else None, n, outputs,
-                                                ctypes.byref(ptrs)))
+        o = _query_opts(bias, no_bvh, seed=seed)
+        args = (self.ctx.handle, self._h, ctypes.byref(o), rays.data_ptr() if n else None, n,
+                outputs, ctypes.byref(ptrs))
+        if area_keys is None:
+            _check(_lib.rt_direct_light_rays_device(*args))
+        else:
+            rec = area_keys._device(n, dev)
+            _check(_lib.rt_direct_light_rays_keyed_device(*args, ctypes.byref(rec)))
         return res
 
     def scatter(self, rays: np.ndarray, outputs: int = SC_ALL, bias: float = 1e-3,
-                terminal: bool = False, no_bvh: bool = False) -> dict:
+                terminal: bool = False, no_bvh: bool = False, area_keys=None, seed=None) -> dict:
         """One TraceRay level per ray, before its children are traced (rt_scatter_rays): rays
         [n,6] -> {"value" [n,3], "refract_rays" [n,6], "reflect_rays" [n,6], "weights" [n,2] {fw,
         rw}: float64; "flags" [n] uint8: bit 0 hit, bit 1 refraction ray, bit 2 reflection ray}
         for the SC_* bits of `outputs`.  An absent child is zeros.  terminal: every ray is at the
-        recursion limit (max_recursion = 0): sky, no intersection, no children."""
+        recursion limit (max_recursion = 0): sky, no intersection, no children.  area_keys (an
+        AreaKeys; the draws under `seed`): rt_scatter_rays_keyed, the value with the area light."""
         rays, n = _host_rows(rays, 6)
         res, ptrs = _outputs("SC", outputs, n)
-        o = _query_opts(bias, no_bvh, 0 if terminal else 1)
-        _check(_lib.rt_scatter_rays(self.ctx.handle, self._h, ctypes.byref(o),
-                                    rays.ctypes.data if n else None, n, outputs,
-                                    ctypes.byref(ptrs)))
+        o = _query_opts(bias, no_bvh, 0 if terminal else 1, seed=seed)
+        args = (self.ctx.handle, self._h, ctypes.byref(o), rays.ctypes.data if n else None, n,
+                outputs, ctypes.byref(ptrs))
+        if area_keys is None:
+            _check(_lib.rt_scatter_rays(*args))
+        else:
+            rec, _keep = area_keys._host(n)
+            _check(_lib.rt_scatter_rays_keyed(*args, ctypes.byref(rec)))
         return res
 
     def scatter_device(self, rays, outputs: int = SC_ALL, out=None, bias: float = 1e-3,
-                       terminal: bool = False, no_bvh: bool = False) -> dict:
+                       terminal: bool = False, no_bvh: bool = False, area_keys=None,
+                       seed=None) -> dict:
         """Asynchronous rt_scatter_rays_device on the context's stream: rays a contiguous float64
         [n,6] tensor on this context's device.  Returns the dict of scatter() as torch tensors;
-        `out` may hold a tensor per requested name to write into."""
+        `out` may hold a tensor per requested name to write into.  area_keys:
+        rt_scatter_rays_keyed_device."""
         import torch
         dev = self._device()
         n = _checked_input(rays, dev, torch.float64, 6, "rays")
         res, ptrs = _outputs("SC", outputs, n, dev, out)
-        o = _query_opts(bias, no_bvh, 0 if terminal else 1)
-        _check(_lib.rt_scatter_rays_device(self.ctx.handle, self._h, ctypes.byref(o),
-                                           rays.data_ptr() if n else None, n, outputs,
-                                           ctypes.byref(ptrs)))
+        o = _query_opts(bias, no_bvh, 0 if terminal else 1, seed=seed)
+        args = (self.ctx.handle, self._h, ctypes.byref(o), rays.data_ptr() if n else None, n,
+                outputs, ctypes.byref(ptrs))
+        if area_keys is None:
+            _check(_lib.rt_scatter_rays_device(*args))
+        else:
+            rec = area_keys._device(n, dev)
+            _check(_lib.rt_scatter_rays_keyed_device(*args, ctypes.byref(rec)))
         return res
 
     def _camera_record(self, cam):
@@ -1324,21 +1430,31 @@ def render_gather_all_batch(comms: list, scenes: list, cams: np.ndarray, opts: R
 
 
 def compose_trace(ds: "DeviceScene", rays: np.ndarray, depth: int, bias: float = 1e-3,
-                  _level: int = 0) -> np.ndarray:
+                  area_keys=None, seed=None, _level: int = 0) -> np.ndarray:
     """TraceRay(ray, 0) with maxRecursion = depth, composed level by level from scatter():
         TraceRay(ray, k) = value(ray) + TraceRay(refraction child, k + 1) * fw
                                       + TraceRay(reflection child, k + 1) * rw
     in the reference's order of the sum (Scene.h:172, 182, 193).  The children that exist are
     selected by the flags (an absent child adds nothing, not even a zero), and the level `depth`
-    is asked with terminal=True: every ray there is at the recursion limit.  rays [n,6] -> [n,3]."""
+    is asked with terminal=True: every ray there is at the recursion limit.  rays [n,6] -> [n,3].
+    area_keys (an AreaKeys; the draws under `seed`): the scene's area light is served — every
+    level is asked with depth = its level and the pixel keys of the rays its rays descend from
+    (pixel None: ray i of the first level has key i), as TraceRay keys its draws."""
     rays = np.ascontiguousarray(rays, np.float64).reshape(-1, 6)
+    keys = None
+    if area_keys is not None:
+        px = (np.arange(len(rays), dtype=np.uint64) if area_keys.pixel is None
+              else np.asarray(area_keys.pixel, np.uint64).reshape(-1))
+        keys = area_keys.at_depth(_level, px)
     if _level >= depth:
-        return ds.scatter(rays, outputs=SC_VALUE, bias=bias, terminal=True)["value"]
-    s = ds.scatter(rays, outputs=SC_ALL, bias=bias)
+        return ds.scatter(rays, outputs=SC_VALUE, bias=bias, terminal=True, area_keys=keys,
+                          seed=seed)["value"]
+    s = ds.scatter(rays, outputs=SC_ALL, bias=bias, area_keys=keys, seed=seed)
     total = s["value"].copy()
     for key, bit, w in (("refract_rays", 2, 0), ("reflect_rays", 4, 1)):
         live = (s["flags"] & bit) != 0
         if live.any():
-            child = compose_trace(ds, s[key][live], depth, bias, _level + 1)
+            child_keys = None if keys is None else keys.at_depth(_level + 1, keys.pixel[live])
+            child = compose_trace(ds, s[key][live], depth, bias, child_keys, seed, _level + 1)
             total[live] = total[live] + child * s["weights"][live, w:w + 1]
     return total

@@ -151,6 +151,7 @@ enum : unsigned {
     kReadBias = 2,       // bias
     kReadRecursion = 4,  // the sign of max_recursion: 0 is "at the recursion limit"
     kReadAll = 8,        // everything but the row range (rt_trace_rays)
+    kReadSeed = 16,      // seed (the keyed entries: the area light's draws)
 };
 
 struct QueryParams {
@@ -173,6 +174,7 @@ rt_status query_params(rt_context* ctx, const rt_scene* sc, const rt_render_opts
     if (opts && (which & kReadAll)) o = *opts;
     if (opts && (which & kReadNoBvh)) o.flags = opts->flags & RT_FLAG_NO_BVH;
     if (opts && (which & kReadBias)) o.bias = opts->bias;
+    if (opts && (which & kReadSeed)) o.seed = opts->seed;
     o.row_begin = o.row_end = 0;
     bool lds;
     size_t lds_bytes;
@@ -205,6 +207,26 @@ void copy_row_set(const rt_render_opts& from, rt_render_opts& o) {
     o.row_cycle = from.row_cycle;
 }
 
+// ---- the keys of the area light's draws (the _keyed entries) -----------------------------------
+// *keys, or {NULL, 0, 0} for NULL, checked before anything touches a device.
+rt_status check_keys(const rt_area_keys* keys, const char* entry, rt_area_keys& k) {
+    k = keys ? *keys : rt_area_keys{nullptr, 0, 0};
+    if (k.depth > 63)  // the streams of neighbouring samples would collide
+        return fail(RT_ERR_INVALID_ARG, "keys->depth " + std::to_string(k.depth) +
+                                            " above 63 passed to " + entry);
+    if (k.sample > 0x00FFFFFFu)  // the stream is 32 bits
+        return fail(RT_ERR_INVALID_ARG, "keys->sample " + std::to_string(k.sample) +
+                                            " above 0x00FFFFFF passed to " + entry);
+    return RT_OK;
+}
+
+// The kernels' record of k with its pixel keys at d_pixel (device memory, or NULL).
+AreaKeyArgs device_keys(const rt_area_keys& k, const void* d_pixel) {
+    return AreaKeyArgs{static_cast<const unsigned long long*>(d_pixel), k.sample, k.depth};
+}
+
+constexpr unsigned kReadKeyed = kReadNoBvh | kReadBias | kReadSeed;  // what every keyed entry reads
+
 const double* f64(const void* p) { return static_cast<const double*>(p); }
 double* f64(void* p) { return static_cast<double*>(p); }
 
@@ -235,10 +257,23 @@ rt_status enqueue_transmittance(rt_context* ctx, const QueryParams& q, const voi
     return RT_OK;
 }
 
+// keys (here and in the three queries below): the _keyed entries' — with an area light attached
+// its samples are served under them (rt_area_queries.hip); without one, and for keys == nullptr,
+// the query is the un-keyed one.
 rt_status enqueue_light_transmittance(rt_context* ctx, const QueryParams& q, const void* points,
-                                      size_t n, void* T) {
-    RT_HIP(launch_light_transmittance(q.p, q.opaque, f64(points), n, f64(T), ctx->stream));
+                                      size_t n, void* T, const AreaKeyArgs* keys = nullptr) {
+    if (keys && q.p.al_samples > 0)
+        RT_HIP(launch_keyed_shadow_points(q.p, q.opaque, f64(points), *keys, n, f64(T),
+                                          ctx->stream));
+    else
+        RT_HIP(launch_light_transmittance(q.p, q.opaque, f64(points), n, f64(T), ctx->stream));
     return RT_OK;
+}
+
+// Columns of the light-transmittance table: the point lights, and for a keyed query the area
+// light's samples after them.
+size_t light_columns(const QueryParams& q, bool keyed) {
+    return static_cast<size_t>(q.p.nl) + (keyed ? static_cast<size_t>(q.p.al_samples) : 0);
 }
 
 DlOut dl_out(const rt_direct_light_out& o) {
@@ -251,26 +286,38 @@ static_assert(sizeof(rt_material) == 7 * sizeof(double), "rt_material is not sev
 // and passed in the kernel arguments (rt_capi.h).
 rt_status enqueue_direct_light(rt_context* ctx, const QueryParams& q, const void* points,
                                const void* materials, const void* shared_material, size_t n,
-                               const rt_direct_light_out& out) {
+                               const rt_direct_light_out& out, const AreaKeyArgs* keys = nullptr) {
     DlMaterial s{};
     if (shared_material) std::memcpy(s.v, shared_material, sizeof(rt_material));
-    RT_HIP(launch_direct_light_points(q.p, q.opaque, f64(points),
-                                      shared_material ? nullptr : f64(materials), s, n,
-                                      dl_out(out), ctx->stream));
+    const double* per_point = shared_material ? nullptr : f64(materials);
+    if (keys && q.p.al_samples > 0)
+        RT_HIP(launch_keyed_direct_points(q.p, q.opaque, f64(points), per_point, s, *keys, n,
+                                          dl_out(out), ctx->stream));
+    else
+        RT_HIP(launch_direct_light_points(q.p, q.opaque, f64(points), per_point, s, n,
+                                          dl_out(out), ctx->stream));
     return RT_OK;
 }
 
 rt_status enqueue_direct_light_rays(rt_context* ctx, const QueryParams& q, const void* rays,
-                                    size_t n, const rt_direct_light_out& out) {
-    RT_HIP(launch_direct_light_rays(q.p, q.opaque, f64(rays), n, dl_out(out), ctx->stream));
+                                    size_t n, const rt_direct_light_out& out,
+                                    const AreaKeyArgs* keys = nullptr) {
+    if (keys && q.p.al_samples > 0)
+        RT_HIP(launch_keyed_direct_rays(q.p, q.opaque, f64(rays), *keys, n, dl_out(out),
+                                        ctx->stream));
+    else
+        RT_HIP(launch_direct_light_rays(q.p, q.opaque, f64(rays), n, dl_out(out), ctx->stream));
     return RT_OK;
 }
 
 rt_status enqueue_scatter(rt_context* ctx, const QueryParams& q, const void* rays, size_t n,
-                          const rt_scatter_out& o) {
+                          const rt_scatter_out& o, const AreaKeyArgs* keys = nullptr) {
     const ScOut out{f64(o.value), f64(o.refract_rays), f64(o.reflect_rays), f64(o.weights),
                     static_cast<uint8_t*>(o.flags)};
-    RT_HIP(launch_scatter_rays(q.p, q.opaque, f64(rays), n, out, ctx->stream));
+    if (keys && q.p.al_samples > 0 && out.value)  // the child outputs do not depend on the keys
+        RT_HIP(launch_keyed_scatter(q.p, q.opaque, f64(rays), *keys, n, out, ctx->stream));
+    else
+        RT_HIP(launch_scatter_rays(q.p, q.opaque, f64(rays), n, out, ctx->stream));
     return RT_OK;
 }
 
@@ -623,6 +670,168 @@ rt_status rt_scatter_rays(rt_context* ctx, const rt_scene* sc, const rt_render_o
     const int i_rays = s.in(rays, n * kRayBytes), i_out = s.outs(kScOut, outputs, *out, n);
     RT_TRY(s.upload());
     RT_TRY(enqueue_scatter(ctx, q, s.at(i_rays), n, s.outs_at(kScOut, i_out)));
+    return s.finish();
+}
+
+// ---- the same four queries with the area light served (rt_area_queries.hip) --------------------
+// Each is its sibling plus the keys: checked first, the pixel keys one more staged input of the
+// host entries, opts->seed read next to what the sibling reads.
+rt_status rt_light_transmittance_keyed_device(rt_context* ctx, const rt_scene* sc,
+                                              const rt_render_opts* opts, const void* d_points,
+                                              size_t n, void* d_T, const rt_area_keys* keys) {
+    rt_area_keys k;
+    RT_TRY(check_keys(keys, "rt_light_transmittance_keyed_device", k));
+    if (!ctx || (n && !d_points))
+        return fail(RT_ERR_INVALID_ARG, "NULL argument to rt_light_transmittance_keyed_device");
+    DeviceGuard g(ctx->device);
+    QueryParams q;
+    RT_TRY(query_params(ctx, sc, opts, kReadKeyed, q));
+    if (n == 0 || light_columns(q, true) == 0) return RT_OK;
+    if (!d_T)
+        return fail(RT_ERR_INVALID_ARG, "NULL argument to rt_light_transmittance_keyed_device");
+    const AreaKeyArgs dk = device_keys(k, k.pixel);
+    return enqueue_light_transmittance(ctx, q, d_points, n, d_T, &dk);
+}
+
+rt_status rt_light_transmittance_keyed(rt_context* ctx, const rt_scene* sc,
+                                       const rt_render_opts* opts, const double* points, size_t n,
+                                       double* T_out, const rt_area_keys* keys) {
+    rt_area_keys k;
+    RT_TRY(check_keys(keys, "rt_light_transmittance_keyed", k));
+    if (!ctx || (n && !points))
+        return fail(RT_ERR_INVALID_ARG, "NULL argument to rt_light_transmittance_keyed");
+    DeviceGuard g(ctx->device);
+    QueryParams q;
+    RT_TRY(query_params(ctx, sc, opts, kReadKeyed, q));
+    const size_t cols = light_columns(q, true);
+    if (n == 0 || cols == 0) return RT_OK;
+    if (!T_out) return fail(RT_ERR_INVALID_ARG, "NULL argument to rt_light_transmittance_keyed");
+    Stage s(ctx);
+    const int i_pts = s.in(points, n * kRayBytes),
+              i_key = s.in(k.pixel, k.pixel ? n * sizeof(uint64_t) : 0),
+              i_out = s.out(T_out, n * cols * sizeof(double));
+    RT_TRY(s.upload());
+    const AreaKeyArgs dk = device_keys(k, s.at(i_key));
+    RT_TRY(enqueue_light_transmittance(ctx, q, s.at(i_pts), n, s.at(i_out), &dk));
+    return s.finish();
+}
+
+rt_status rt_direct_light_keyed_device(rt_context* ctx, const rt_scene* sc,
+                                       const rt_render_opts* opts, const void* d_points,
+                                       const void* d_materials, size_t n_materials, size_t n,
+                                       int outputs, const struct rt_direct_light_out* d_out,
+                                       const rt_area_keys* keys) {
+    rt_area_keys k;
+    RT_TRY(check_keys(keys, "rt_direct_light_keyed_device", k));
+    RT_TRY(check_outputs(kDlOut, outputs, d_out, !n || (d_points && d_materials), ctx,
+                         "rt_direct_light_keyed_device",
+                         !n || n_materials == n || n_materials == 1));
+    if (n == 0) return RT_OK;
+    DeviceGuard g(ctx->device);
+    QueryParams q;
+    RT_TRY(query_params(ctx, sc, opts, kReadKeyed, q));
+    const AreaKeyArgs dk = device_keys(k, k.pixel);
+    return enqueue_direct_light(ctx, q, d_points, d_materials,
+                                n_materials == 1 ? d_materials : nullptr, n,
+                                requested(kDlOut, outputs, *d_out), &dk);
+}
+
+rt_status rt_direct_light_keyed(rt_context* ctx, const rt_scene* sc, const rt_render_opts* opts,
+                                const double* points, const rt_material* materials,
+                                size_t n_materials, size_t n, int outputs,
+                                const struct rt_direct_light_out* out, const rt_area_keys* keys) {
+    rt_area_keys k;
+    RT_TRY(check_keys(keys, "rt_direct_light_keyed", k));
+    RT_TRY(check_outputs(kDlOut, outputs, out, !n || (points && materials), ctx,
+                         "rt_direct_light_keyed", !n || n_materials == n || n_materials == 1));
+    if (n == 0) return RT_OK;
+    DeviceGuard g(ctx->device);
+    QueryParams q;
+    RT_TRY(query_params(ctx, sc, opts, kReadKeyed, q));
+    const bool shared = n_materials == 1;
+    Stage s(ctx);
+    const int i_pts = s.in(points, n * 9 * sizeof(double)),
+              i_mat = s.in(materials, shared ? 0 : n * sizeof(rt_material)),
+              i_key = s.in(k.pixel, k.pixel ? n * sizeof(uint64_t) : 0),
+              i_out = s.outs(kDlOut, outputs, *out, n);
+    RT_TRY(s.upload());
+    const AreaKeyArgs dk = device_keys(k, s.at(i_key));
+    RT_TRY(enqueue_direct_light(ctx, q, s.at(i_pts), s.at(i_mat), shared ? materials : nullptr, n,
+                                s.outs_at(kDlOut, i_out), &dk));
+    return s.finish();
+}
+
+rt_status rt_direct_light_rays_keyed_device(rt_context* ctx, const rt_scene* sc,
+                                            const rt_render_opts* opts, const void* d_rays,
+                                            size_t n, int outputs,
+                                            const struct rt_direct_light_out* d_out,
+                                            const rt_area_keys* keys) {
+    rt_area_keys k;
+    RT_TRY(check_keys(keys, "rt_direct_light_rays_keyed_device", k));
+    RT_TRY(check_outputs(kDlOut, outputs, d_out, !n || d_rays, ctx,
+                         "rt_direct_light_rays_keyed_device"));
+    if (n == 0) return RT_OK;
+    DeviceGuard g(ctx->device);
+    QueryParams q;
+    RT_TRY(query_params(ctx, sc, opts, kReadKeyed, q));
+    const AreaKeyArgs dk = device_keys(k, k.pixel);
+    return enqueue_direct_light_rays(ctx, q, d_rays, n, requested(kDlOut, outputs, *d_out), &dk);
+}
+
+rt_status rt_direct_light_rays_keyed(rt_context* ctx, const rt_scene* sc,
+                                     const rt_render_opts* opts, const double* rays, size_t n,
+                                     int outputs, const struct rt_direct_light_out* out,
+                                     const rt_area_keys* keys) {
+    rt_area_keys k;
+    RT_TRY(check_keys(keys, "rt_direct_light_rays_keyed", k));
+    RT_TRY(check_outputs(kDlOut, outputs, out, !n || rays, ctx, "rt_direct_light_rays_keyed"));
+    if (n == 0) return RT_OK;
+    DeviceGuard g(ctx->device);
+    QueryParams q;
+    RT_TRY(query_params(ctx, sc, opts, kReadKeyed, q));
+    Stage s(ctx);
+    const int i_rays = s.in(rays, n * kRayBytes),
+              i_key = s.in(k.pixel, k.pixel ? n * sizeof(uint64_t) : 0),
+              i_out = s.outs(kDlOut, outputs, *out, n);
+    RT_TRY(s.upload());
+    const AreaKeyArgs dk = device_keys(k, s.at(i_key));
+    RT_TRY(enqueue_direct_light_rays(ctx, q, s.at(i_rays), n, s.outs_at(kDlOut, i_out), &dk));
+    return s.finish();
+}
+
+rt_status rt_scatter_rays_keyed_device(rt_context* ctx, const rt_scene* sc,
+                                       const rt_render_opts* opts, const void* d_rays, size_t n,
+                                       int outputs, const struct rt_scatter_out* d_out,
+                                       const rt_area_keys* keys) {
+    rt_area_keys k;
+    RT_TRY(check_keys(keys, "rt_scatter_rays_keyed_device", k));
+    RT_TRY(check_outputs(kScOut, outputs, d_out, !n || d_rays, ctx,
+                         "rt_scatter_rays_keyed_device"));
+    if (n == 0) return RT_OK;
+    DeviceGuard g(ctx->device);
+    QueryParams q;
+    RT_TRY(query_params(ctx, sc, opts, kReadKeyed | kReadRecursion, q));
+    const AreaKeyArgs dk = device_keys(k, k.pixel);
+    return enqueue_scatter(ctx, q, d_rays, n, requested(kScOut, outputs, *d_out), &dk);
+}
+
+rt_status rt_scatter_rays_keyed(rt_context* ctx, const rt_scene* sc, const rt_render_opts* opts,
+                                const double* rays, size_t n, int outputs,
+                                const struct rt_scatter_out* out, const rt_area_keys* keys) {
+    rt_area_keys k;
+    RT_TRY(check_keys(keys, "rt_scatter_rays_keyed", k));
+    RT_TRY(check_outputs(kScOut, outputs, out, !n || rays, ctx, "rt_scatter_rays_keyed"));
+    if (n == 0) return RT_OK;
+    DeviceGuard g(ctx->device);
+    QueryParams q;
+    RT_TRY(query_params(ctx, sc, opts, kReadKeyed | kReadRecursion, q));
+    Stage s(ctx);
+    const int i_rays = s.in(rays, n * kRayBytes),
+              i_key = s.in(k.pixel, k.pixel ? n * sizeof(uint64_t) : 0),
+              i_out = s.outs(kScOut, outputs, *out, n);
+    RT_TRY(s.upload());
+    const AreaKeyArgs dk = device_keys(k, s.at(i_key));
+    RT_TRY(enqueue_scatter(ctx, q, s.at(i_rays), n, s.outs_at(kScOut, i_out), &dk));
     return s.finish();
 }
 

@@ -10,18 +10,13 @@
 // point, normal and view as shade_hit does.  Nothing of that is restated here, so the bits are the
 // renderer's.  OPAQUE (no material of the scene is transparent): light_term asks
 // occlusion_opaque before the march, as the render kernels of such scenes do.
-// Only the point lights are read; the build-defined area light is not.
-#include "rt_trace_common.hpp"
+// Only the point lights are read; the build-defined area light is read by the keyed twins of
+// these kernels (rt_area_queries.hip).
+#include "rt_query_out.hpp"
 
 #pragma clang fp contract(off)
 
 namespace rtamd {
-
-// Two doubles at 8-byte alignment: the records of a point (72 B) and of a material (56 B) keep
-// every second thread off a 16-byte boundary, and a 16-byte global load needs none.
-typedef double d2u __attribute__((ext_vector_type(2), aligned(8)));
-
-__device__ __forceinline__ d2u load2(const double* p) { return *reinterpret_cast<const d2u*>(p); }
 
 // directLightning's loop over the point lights for one point; m: {r g b shininess specular
 // transparency ...}, read by light_term at its uses.
@@ -37,23 +32,6 @@ __device__ __forceinline__ void light_loop(const SceneView& S, d3 p, d3 n_in, d3
         light_term<false, OPAQUE>(S, p, n, view, m, mk(lt[0], lt[1], lt[2]),
                                   mk(lt[3], lt[4], lt[5]), bias, diff, spec, cnt);
     }
-}
-
-__device__ __forceinline__ void store3(double* base, size_t i, d3 v) {
-    if (!base) return;
-    double* w = base + 3 * i;
-    w[0] = v.x;
-    w[1] = v.y;
-    w[2] = v.z;
-}
-
-// color * diffuseAccumulation + specularAccumlation * material.specular (Scene.h:126-128), the
-// last line of `direct`.
-__device__ __forceinline__ void store_outputs(const DlOut& out, size_t i, d3 color, double specular,
-                                              d3 diff, d3 spec) {
-    store3(out.radiance, i, hmul(color, diff) + spec * specular);
-    store3(out.diffuse, i, diff);
-    store3(out.specular, i, spec);
 }
 
 // One thread per point {p, normal, view}: 9 doubles in, and with SHARED == false the point's own

@@ -324,8 +324,8 @@ hipError_t launch_direct_light_rays(const TraceParams& p, bool opaque, const dou
                                     const DlOut& out, hipStream_t stream);
 // Scatter query (rt_scatter.hip): one TraceRay level (Scene.h:131-198) per ray, before its
 // children are traced — shade_hit's Node written out.  p.max_rec <= 0: every ray is at the
-// recursion limit (sky, no intersection).  The area light is not read.  A null output is not
-// written; at least one is set.
+// recursion limit (sky, no intersection).  The area light is not read (launch_keyed_scatter
+// reads it).  A null output is not written; at least one is set.
 struct ScOut {
     double* value;         // [n][3] sky on a miss, else localLight * (1 - transparency)
     double* refract_rays;  // [n][6] {o, d}, zeros where absent
@@ -335,6 +335,30 @@ struct ScOut {
 };
 hipError_t launch_scatter_rays(const TraceParams& p, bool opaque, const double* rays, size_t n,
                                const ScOut& out, hipStream_t stream);
+// The keyed twins of the four per-level queries above (rt_area_queries.hip): the same answers with
+// the build-defined area light served — direct()'s samples appended after the point lights; for
+// the shadow points nl + al_samples columns per point, the samples after the lights.  Only for
+// p.al_samples > 0, and the scatter only with out.value set: everything else is the un-keyed
+// launch's.  keys.pixel: n device keys, or null (element i draws with pixel = i); the draws are
+// keyed (p.seed, pixel, 0x10000 + (sample << 6) + depth, 2s | 2s + 1) as direct() keys them.
+struct AreaKeyArgs {
+    const unsigned long long* pixel;
+    uint32_t sample;
+    uint32_t depth;
+};
+hipError_t launch_keyed_scatter(const TraceParams& p, bool opaque, const double* rays,
+                                const AreaKeyArgs& keys, size_t n, const ScOut& out,
+                                hipStream_t stream);
+hipError_t launch_keyed_direct_points(const TraceParams& p, bool opaque, const double* points,
+                                      const double* materials, const DlMaterial& shared,
+                                      const AreaKeyArgs& keys, size_t n, const DlOut& out,
+                                      hipStream_t stream);
+hipError_t launch_keyed_direct_rays(const TraceParams& p, bool opaque, const double* rays,
+                                    const AreaKeyArgs& keys, size_t n, const DlOut& out,
+                                    hipStream_t stream);
+hipError_t launch_keyed_shadow_points(const TraceParams& p, bool opaque, const double* points,
+                                      const AreaKeyArgs& keys, size_t n, double* out,
+                                      hipStream_t stream);
 // Camera rays (rt_camera_rays.hip): Camera::getRay(x, y, sample > 0 && p.aa > 1) for every pixel
 // of p's row set, {o, d} per pixel at its rows-local index; the jitter key is the render
 // kernels' (p.seed, y_image * W + x, sample).  out: p.rows * p.width * 6 doubles.

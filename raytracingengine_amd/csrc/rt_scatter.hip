@@ -10,50 +10,15 @@
 // refraction code, and with TREE == false occlusion_opaque before each shadow march.  DIRECT and
 // CHILDREN are shade_hit's: without RT_SC_VALUE the light loop is not compiled in, without any of
 // the child outputs (rays, weights, flags) the child-ray code is not.
-// The build-defined area light is not read: the kernel's SceneView says the scene has none
+// The build-defined area light is not read (keyed_scatter_kernel, rt_area_queries.hip, reads it
+// under keys the caller supplies): the kernel's SceneView says the scene has none
 // (S.al = 0, a constant there), so direct()'s sample loop, and its second inlined light_term, is
 // not compiled into these kernels at all.
-#include "rt_trace_common.hpp"
+#include "rt_query_out.hpp"
 
 #pragma clang fp contract(off)
 
 namespace rtamd {
-
-__device__ __forceinline__ void sc_store3(double* base, size_t i, d3 v) {
-    if (!base) return;
-    double* w = base + 3 * i;
-    w[0] = v.x;
-    w[1] = v.y;
-    w[2] = v.z;
-}
-
-// A child ray {o, d}, or six +0.0 where the level has none: 48 B per ray, 8-byte aligned.
-__device__ __forceinline__ void sc_store_ray(double* base, size_t i, bool present, d3 o, d3 d) {
-    if (!base) return;
-    double* w = base + 6 * i;
-    w[0] = present ? o.x : 0.0;
-    w[1] = present ? o.y : 0.0;
-    w[2] = present ? o.z : 0.0;
-    w[3] = present ? d.x : 0.0;
-    w[4] = present ? d.y : 0.0;
-    w[5] = present ? d.z : 0.0;
-}
-
-// Every requested output of ray i from its Node; an absent child is zeros, as is its weight.
-template <bool CHILDREN>
-__device__ __forceinline__ void sc_store_node(const ScOut& out, size_t i, const Node& nd) {
-    sc_store3(out.value, i, nd.value);
-    if constexpr (CHILDREN) {
-        sc_store_ray(out.refract_rays, i, nd.refr, nd.fo, nd.fd);
-        sc_store_ray(out.reflect_rays, i, nd.refl, nd.ro, nd.rd);
-        if (out.weights) {
-            out.weights[2 * i + 0] = nd.refr ? nd.fw : 0.0;
-            out.weights[2 * i + 1] = nd.refl ? nd.rw : 0.0;
-        }
-        if (out.flags)
-            out.flags[i] = static_cast<uint8_t>((nd.hit ? 1 : 0) | (nd.refr ? 2 : 0) | (nd.refl ? 4 : 0));
-    }
-}
 
 // One thread per ray {o, d}.  P.max_rec <= 0: the ray is at the recursion limit (Scene.h:132-134),
 // nothing is intersected.
@@ -62,7 +27,7 @@ __global__ __launch_bounds__(256) void scatter_rays_kernel(TraceParams P,
                                                            const double* __restrict__ rays, size_t n,
                                                            ScOut out) {
     SceneView S = stage_scene<false>(P, nullptr, 0, 0);
-    S.al = 0;  // no area light: callers do not supply the pixel and sample keys of its draws
+    S.al = 0;  // no area light: this entry takes no pixel and sample keys for its draws
     const size_t i = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const double* r = rays + 6 * i;

@@ -666,6 +666,8 @@ __device__ __forceinline__ d3 direct(const SceneView& S, const TraceParams& P, d
                           diff, spec, cnt);
     }
 #ifndef RT_LEAN_GENERIC  // ... and without the area light
+    // (restated by area_terms and area_point, rt_area_queries.hip, for the queries that return the
+    // two accumulators apart: a change here is a change there)
     if (S.al > 0) {
         const uint32_t stream = 0x10000u + (sample << 6) + static_cast<uint32_t>(depth);
         const double k = static_cast<double>(P.al_k);

@@ -11,26 +11,13 @@
 // OPAQUE (no material of the scene is transparent, so T is 0 or 1 and the first counted hit
 // decides it): occlusion_opaque classifies the lane first and only the lanes it leaves undecided
 // (-1: triangles, roots near a threshold, values out of range) march — light_term's pair.
-// Lights are read by the light kernel only; the area light by neither.
-#include "rt_trace_common.hpp"
+// Lights are read by the light kernel only; the area light by neither (keyed_shadow_points_kernel,
+// rt_area_queries.hip, answers for its samples).
+#include "rt_query_out.hpp"
 
 #pragma clang fp contract(off)
 
 namespace rtamd {
-
-// computeTransmittance(ray {o, d}, max_dist, bias).  A max_dist that is NaN or <= 0 never enters
-// the march's loop (traveled = 0 < max_dist is false): 1.0, asked before the classification,
-// whose margins are formed from max_dist.
-template <bool OPAQUE>
-__device__ __forceinline__ double transmit_ray(const SceneView& S, d3 o, d3 d, double max_dist,
-                                               double bias) {
-    if (!(max_dist > 0.0)) return 1.0;
-    if constexpr (OPAQUE) {
-        const int occ = occlusion_opaque(S, o, d, max_dist, bias);
-        if (occ >= 0) return static_cast<double>(occ);
-    }
-    return transmittance(S, o, d, max_dist, bias);
-}
 
 // One thread per ray: 7 doubles in (the ray and its max_dist), one double out.
 template <bool OPAQUE>

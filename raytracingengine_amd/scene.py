@@ -218,9 +218,10 @@ class SceneData:
                          f"{self.name}_{width}x{height}")
 
     # ---------------------------------------------------------------- scene file
-    def to_text(self) -> str:
+    def to_text(self, area_light: bool = False) -> str:
         """Scene-file text read by oracle/_ref (ref_harness.cpp load_scene).  Doubles are
-        written with repr() so they round-trip exactly."""
+        written with repr() so they round-trip exactly.  area_light: the build-defined area light
+        gets an `arealight` line (read by api/rtamd/scenefile.hpp; other readers skip it)."""
 
         def f(x):
             return repr(float(x))
@@ -248,12 +249,16 @@ class SceneData:
                 out.append(f"v {vec(v0)} {vec(v1)} {vec(v2)}")
         for p, col, s in self.lights:
             out.append(f"light {vec(p)} {vec(col)} {f(s)}")
+        if area_light and self.area_light is not None:
+            a = self.area_light
+            out.append(f"arealight {vec(a.corner)} {vec(a.edge_u)} {vec(a.edge_v)} {vec(a.color)} "
+                       f"{f(a.intensity)} {a.samples}")
         out.append("end")
         return "\n".join(out) + "\n"
 
-    def write(self, path) -> None:
+    def write(self, path, area_light: bool = False) -> None:
         with open(path, "w") as fh:
-            fh.write(self.to_text())
+            fh.write(self.to_text(area_light))
 
 
 def tinyobj_real(s: str, fallback: float) -> float:
