@@ -232,6 +232,18 @@ class AreaKeys:
         return AreaKeysRec(self.pixel.data_ptr() if n else None, self.sample, self.depth)
 
 
+def _call_level(query: str, args, area_keys, n: int, dev=None) -> None:
+    """One call of a per-level query: the entry `query` itself, or with area_keys its _keyed
+    sibling with the keys' record after the sibling's arguments.  dev: the device of a _device
+    entry's tensors; None: the host entry."""
+    form = "" if dev is None else "_device"
+    if area_keys is None:
+        _check(getattr(_lib, query + form)(*args))
+        return
+    rec, _keep = area_keys._host(n) if dev is None else (area_keys._device(n, dev), None)
+    _check(getattr(_lib, query + "_keyed" + form)(*args, ctypes.byref(rec)))
+
+
 # The records of selectable outputs by the prefix of their bits: the rows (name, bit, element
 # type, elements per item), the ctypes record and all the bits.  DL_OUTPUTS keeps its two columns
 # for its users; every direct-light output is float64 [n, 3].
@@ -367,7 +379,7 @@ def load_library(path: str = LIB_PATH):
     L.rt_device_count.restype = i32
     L.rt_render_opts_default.argtypes = [vp]
     L.rt_render_opts_default.restype = None
-    for name, args in {
+    sigs = {
         "rt_context_create": [i32, vp],
         "rt_context_destroy": [vp],
         "rt_context_set_stream": [vp, vp],
@@ -397,16 +409,6 @@ def load_library(path: str = LIB_PATH):
         "rt_direct_light_rays_device": [vp, vp, vp, vp, ctypes.c_size_t, i32, vp],
         "rt_scatter_rays": [vp, vp, vp, vp, ctypes.c_size_t, i32, vp],
         "rt_scatter_rays_device": [vp, vp, vp, vp, ctypes.c_size_t, i32, vp],
-        "rt_light_transmittance_keyed": [vp, vp, vp, vp, ctypes.c_size_t, vp, vp],
-        "rt_light_transmittance_keyed_device": [vp, vp, vp, vp, ctypes.c_size_t, vp, vp],
-        "rt_direct_light_keyed": [vp, vp, vp, vp, vp, ctypes.c_size_t, ctypes.c_size_t, i32, vp,
-                                  vp],
-        "rt_direct_light_keyed_device": [vp, vp, vp, vp, vp, ctypes.c_size_t, ctypes.c_size_t,
-                                         i32, vp, vp],
-        "rt_direct_light_rays_keyed": [vp, vp, vp, vp, ctypes.c_size_t, i32, vp, vp],
-        "rt_direct_light_rays_keyed_device": [vp, vp, vp, vp, ctypes.c_size_t, i32, vp, vp],
-        "rt_scatter_rays_keyed": [vp, vp, vp, vp, ctypes.c_size_t, i32, vp, vp],
-        "rt_scatter_rays_keyed_device": [vp, vp, vp, vp, ctypes.c_size_t, i32, vp, vp],
         "rt_camera_rays": [vp, vp, vp, i32, vp],
         "rt_camera_rays_device": [vp, vp, vp, i32, vp],
         "rt_closest_rays": [vp, vp, vp, vp, ctypes.c_size_t, i32, vp],
@@ -449,7 +451,13 @@ def load_library(path: str = LIB_PATH):
         "rt_debug_fixup_count": [vp, vp],
         "rt_debug_assemble_rows": [vp, vp, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_uint32,
                                    ctypes.c_uint32, ctypes.c_uint32, vp],
-    }.items():
+    }
+    # a _keyed entry takes its sibling's arguments, then the rt_area_keys record
+    for query in ("rt_light_transmittance", "rt_direct_light", "rt_direct_light_rays",
+                  "rt_scatter_rays"):
+        for form in ("", "_device"):
+            sigs[query + "_keyed" + form] = sigs[query + form] + [vp]
+    for name, args in sigs.items():
         try:
             fn = getattr(L, name)
         except AttributeError:
@@ -809,11 +817,7 @@ class DeviceScene:
         o = _query_opts(bias, no_bvh, seed=seed)
         args = (self.ctx.handle, self._h, ctypes.byref(o), points.ctypes.data if n else None, n,
                 out.ctypes.data if out.size else None)
-        if area_keys is None:
-            _check(_lib.rt_light_transmittance(*args))
-        else:
-            rec, _keep = area_keys._host(n)
-            _check(_lib.rt_light_transmittance_keyed(*args, ctypes.byref(rec)))
+        _call_level("rt_light_transmittance", args, area_keys, n)
         return out
 
     def light_transmittance_device(self, points, out=None, bias: float = 1e-3,
@@ -830,11 +834,7 @@ class DeviceScene:
         o = _query_opts(bias, no_bvh, seed=seed)
         args = (self.ctx.handle, self._h, ctypes.byref(o), points.data_ptr() if n else None, n,
                 out.data_ptr() if n * nl else None)
-        if area_keys is None:
-            _check(_lib.rt_light_transmittance_device(*args))
-        else:
-            rec = area_keys._device(n, dev)
-            _check(_lib.rt_light_transmittance_keyed_device(*args, ctypes.byref(rec)))
+        _call_level("rt_light_transmittance", args, area_keys, n, dev)
         return out
 
     def direct_light(self, points: np.ndarray, materials, outputs: int = DL_RADIANCE,
@@ -850,11 +850,7 @@ class DeviceScene:
         o = _query_opts(bias, no_bvh, seed=seed)
         args = (self.ctx.handle, self._h, ctypes.byref(o), points.ctypes.data if n else None,
                 m.ctypes.data, m.shape[0], n, outputs, ctypes.byref(ptrs))
-        if area_keys is None:
-            _check(_lib.rt_direct_light(*args))
-        else:
-            rec, _keep = area_keys._host(n)
-            _check(_lib.rt_direct_light_keyed(*args, ctypes.byref(rec)))
+        _call_level("rt_direct_light", args, area_keys, n)
         return res
 
     def direct_light_rays(self, rays: np.ndarray, outputs: int = DL_RADIANCE, bias: float = 1e-3,
@@ -867,11 +863,7 @@ class DeviceScene:
         o = _query_opts(bias, no_bvh, seed=seed)
         args = (self.ctx.handle, self._h, ctypes.byref(o), rays.ctypes.data if n else None, n,
                 outputs, ctypes.byref(ptrs))
-        if area_keys is None:
-            _check(_lib.rt_direct_light_rays(*args))
-        else:
-            rec, _keep = area_keys._host(n)
-            _check(_lib.rt_direct_light_rays_keyed(*args, ctypes.byref(rec)))
+        _call_level("rt_direct_light_rays", args, area_keys, n)
         return res
 
     def direct_light_device(self, points, materials, outputs: int = DL_RADIANCE, out=None,
@@ -898,11 +890,7 @@ class DeviceScene:
         o = _query_opts(bias, no_bvh, seed=seed)
         args = (self.ctx.handle, self._h, ctypes.byref(o), points.data_ptr() if n else None,
                 m_ptr, n_m, n, outputs, ctypes.byref(ptrs))
-        if area_keys is None:
-            _check(_lib.rt_direct_light_device(*args))
-        else:
-            rec = area_keys._device(n, dev)
-            _check(_lib.rt_direct_light_keyed_device(*args, ctypes.byref(rec)))
+        _call_level("rt_direct_light", args, area_keys, n, dev)
         return res
 
     def direct_light_rays_device(self, rays, outputs: int = DL_RADIANCE, out=None,
@@ -919,11 +907,7 @@ class DeviceScene:
         o = _query_opts(bias, no_bvh, seed=seed)
         args = (self.ctx.handle, self._h, ctypes.byref(o), rays.data_ptr() if n else None, n,
                 outputs, ctypes.byref(ptrs))
-        if area_keys is None:
-            _check(_lib.rt_direct_light_rays_device(*args))
-        else:
-            rec = area_keys._device(n, dev)
-            _check(_lib.rt_direct_light_rays_keyed_device(*args, ctypes.byref(rec)))
+        _call_level("rt_direct_light_rays", args, area_keys, n, dev)
         return res
 
     def scatter(self, rays: np.ndarray, outputs: int = SC_ALL, bias: float = 1e-3,
@@ -939,11 +923,7 @@ class DeviceScene:
         o = _query_opts(bias, no_bvh, 0 if terminal else 1, seed=seed)
         args = (self.ctx.handle, self._h, ctypes.byref(o), rays.ctypes.data if n else None, n,
                 outputs, ctypes.byref(ptrs))
-        if area_keys is None:
-            _check(_lib.rt_scatter_rays(*args))
-        else:
-            rec, _keep = area_keys._host(n)
-            _check(_lib.rt_scatter_rays_keyed(*args, ctypes.byref(rec)))
+        _call_level("rt_scatter_rays", args, area_keys, n)
         return res
 
     def scatter_device(self, rays, outputs: int = SC_ALL, out=None, bias: float = 1e-3,
@@ -960,11 +940,7 @@ class DeviceScene:
         o = _query_opts(bias, no_bvh, 0 if terminal else 1, seed=seed)
         args = (self.ctx.handle, self._h, ctypes.byref(o), rays.data_ptr() if n else None, n,
                 outputs, ctypes.byref(ptrs))
-        if area_keys is None:
-            _check(_lib.rt_scatter_rays_device(*args))
-        else:
-            rec = area_keys._device(n, dev)
-            _check(_lib.rt_scatter_rays_keyed_device(*args, ctypes.byref(rec)))
+        _call_level("rt_scatter_rays", args, area_keys, n, dev)
         return res
 
     def _camera_record(self, cam):

@@ -208,24 +208,39 @@ void copy_row_set(const rt_render_opts& from, rt_render_opts& o) {
 }
 
 // ---- the keys of the area light's draws (the _keyed entries) -----------------------------------
-// *keys, or {NULL, 0, 0} for NULL, checked before anything touches a device.
-rt_status check_keys(const rt_area_keys* keys, const char* entry, rt_area_keys& k) {
-    k = keys ? *keys : rt_area_keys{nullptr, 0, 0};
-    if (k.depth > 63)  // the streams of neighbouring samples would collide
-        return fail(RT_ERR_INVALID_ARG, "keys->depth " + std::to_string(k.depth) +
-                                            " above 63 passed to " + entry);
-    if (k.sample > 0x00FFFFFFu)  // the stream is 32 bits
-        return fail(RT_ERR_INVALID_ARG, "keys->sample " + std::to_string(k.sample) +
-                                            " above 0x00FFFFFF passed to " + entry);
-    return RT_OK;
-}
+// What an entry of a per-level query does about the keys.  An un-keyed entry has none: nothing is
+// checked or staged, opts->seed is not read and the launch gets a null pointer.
+struct EntryKeys {
+    bool keyed;
+    rt_area_keys k{nullptr, 0, 0};  // *keys, or {NULL, 0, 0} for NULL
+    AreaKeyArgs dk{};
 
-// The kernels' record of k with its pixel keys at d_pixel (device memory, or NULL).
-AreaKeyArgs device_keys(const rt_area_keys& k, const void* d_pixel) {
-    return AreaKeyArgs{static_cast<const unsigned long long*>(d_pixel), k.sample, k.depth};
-}
+    // Checked before anything touches a device.
+    rt_status check(const rt_area_keys* keys, const char* entry) {
+        if (!keyed) return RT_OK;
+        if (keys) k = *keys;
+        if (k.depth > 63)  // the streams of neighbouring samples would collide
+            return fail(RT_ERR_INVALID_ARG, "keys->depth " + std::to_string(k.depth) +
+                                                " above 63 passed to " + entry);
+        if (k.sample > 0x00FFFFFFu)  // the stream is 32 bits
+            return fail(RT_ERR_INVALID_ARG, "keys->sample " + std::to_string(k.sample) +
+                                                " above 0x00FFFFFF passed to " + entry);
+        return RT_OK;
+    }
+    // The members of opts the query reads: `base`, and the seed of the draws.
+    unsigned reads(unsigned base) const { return base | (keyed ? kReadSeed : 0u); }
+    // The pixel keys as one more staged input of a host entry, when given.
+    int stage(Stage& s, size_t n) const {
+        return s.in(k.pixel, k.pixel ? n * sizeof(uint64_t) : 0);
+    }
+    // The kernels' record with the pixel keys at d_pixel (device memory, or NULL).
+    const AreaKeyArgs* device(const void* d_pixel) {
+        dk = AreaKeyArgs{static_cast<const unsigned long long*>(d_pixel), k.sample, k.depth};
+        return keyed ? &dk : nullptr;
+    }
+};
 
-constexpr unsigned kReadKeyed = kReadNoBvh | kReadBias | kReadSeed;  // what every keyed entry reads
+constexpr unsigned kReadLevel = kReadNoBvh | kReadBias;  // what every per-level query reads
 
 const double* f64(const void* p) { return static_cast<const double*>(p); }
 double* f64(void* p) { return static_cast<double*>(p); }
@@ -257,16 +272,11 @@ rt_status enqueue_transmittance(rt_context* ctx, const QueryParams& q, const voi
     return RT_OK;
 }
 
-// keys (here and in the three queries below): the _keyed entries' — with an area light attached
-// its samples are served under them (rt_area_queries.hip); without one, and for keys == nullptr,
-// the query is the un-keyed one.
+// keys (here and in the three queries below): the _keyed entries', or nullptr for the un-keyed
+// ones; which kernel answers is the launch's matter (rt_internal.hpp).
 rt_status enqueue_light_transmittance(rt_context* ctx, const QueryParams& q, const void* points,
-                                      size_t n, void* T, const AreaKeyArgs* keys = nullptr) {
-    if (keys && q.p.al_samples > 0)
-        RT_HIP(launch_keyed_shadow_points(q.p, q.opaque, f64(points), *keys, n, f64(T),
-                                          ctx->stream));
-    else
-        RT_HIP(launch_light_transmittance(q.p, q.opaque, f64(points), n, f64(T), ctx->stream));
+                                      size_t n, void* T, const AreaKeyArgs* keys) {
+    RT_HIP(launch_light_transmittance(q.p, q.opaque, f64(points), keys, n, f64(T), ctx->stream));
     return RT_OK;
 }
 
@@ -286,38 +296,27 @@ static_assert(sizeof(rt_material) == 7 * sizeof(double), "rt_material is not sev
 // and passed in the kernel arguments (rt_capi.h).
 rt_status enqueue_direct_light(rt_context* ctx, const QueryParams& q, const void* points,
                                const void* materials, const void* shared_material, size_t n,
-                               const rt_direct_light_out& out, const AreaKeyArgs* keys = nullptr) {
+                               const rt_direct_light_out& out, const AreaKeyArgs* keys) {
     DlMaterial s{};
     if (shared_material) std::memcpy(s.v, shared_material, sizeof(rt_material));
-    const double* per_point = shared_material ? nullptr : f64(materials);
-    if (keys && q.p.al_samples > 0)
-        RT_HIP(launch_keyed_direct_points(q.p, q.opaque, f64(points), per_point, s, *keys, n,
-                                          dl_out(out), ctx->stream));
-    else
-        RT_HIP(launch_direct_light_points(q.p, q.opaque, f64(points), per_point, s, n,
-                                          dl_out(out), ctx->stream));
+    RT_HIP(launch_direct_light_points(q.p, q.opaque, f64(points),
+                                      shared_material ? nullptr : f64(materials), s, keys, n,
+                                      dl_out(out), ctx->stream));
     return RT_OK;
 }
 
 rt_status enqueue_direct_light_rays(rt_context* ctx, const QueryParams& q, const void* rays,
                                     size_t n, const rt_direct_light_out& out,
-                                    const AreaKeyArgs* keys = nullptr) {
-    if (keys && q.p.al_samples > 0)
-        RT_HIP(launch_keyed_direct_rays(q.p, q.opaque, f64(rays), *keys, n, dl_out(out),
-                                        ctx->stream));
-    else
-        RT_HIP(launch_direct_light_rays(q.p, q.opaque, f64(rays), n, dl_out(out), ctx->stream));
+                                    const AreaKeyArgs* keys) {
+    RT_HIP(launch_direct_light_rays(q.p, q.opaque, f64(rays), keys, n, dl_out(out), ctx->stream));
     return RT_OK;
 }
 
 rt_status enqueue_scatter(rt_context* ctx, const QueryParams& q, const void* rays, size_t n,
-                          const rt_scatter_out& o, const AreaKeyArgs* keys = nullptr) {
+                          const rt_scatter_out& o, const AreaKeyArgs* keys) {
     const ScOut out{f64(o.value), f64(o.refract_rays), f64(o.reflect_rays), f64(o.weights),
                     static_cast<uint8_t*>(o.flags)};
-    if (keys && q.p.al_samples > 0 && out.value)  // the child outputs do not depend on the keys
-        RT_HIP(launch_keyed_scatter(q.p, q.opaque, f64(rays), *keys, n, out, ctx->stream));
-    else
-        RT_HIP(launch_scatter_rays(q.p, q.opaque, f64(rays), n, out, ctx->stream));
+    RT_HIP(launch_scatter_rays(q.p, q.opaque, f64(rays), keys, n, out, ctx->stream));
     return RT_OK;
 }
 
@@ -429,6 +428,161 @@ rt_status check_resolve_args(const rt_context* ctx, const void* sum, size_t n, i
     if (!sum && n > 0) return fail(RT_ERR_INVALID_ARG, "NULL sum passed to " + name);
     if (!ctx) return fail(RT_ERR_INVALID_ARG, "NULL context passed to " + name);
     return RT_OK;
+}
+
+// ---- the four per-level queries: each form once ------------------------------------------------
+// keyed: the call came through the _keyed entry; `entry` is the called entry's name and ends
+// every message.  The light query builds its parameters before the n == 0 return (a NULL or
+// foreign scene fails it even then); with no columns nothing is written and there is no output
+// to point to: a NULL one is accepted.  The others return RT_OK for n == 0 before the scene or a
+// device is touched; with n_materials == 1 the material is a host record, for both forms.
+rt_status light_transmittance_device(rt_context* ctx, const rt_scene* sc,
+                                     const rt_render_opts* opts, const void* d_points, size_t n,
+                                     void* d_T, const rt_area_keys* keys, bool keyed,
+                                     const char* entry) {
+    EntryKeys K{keyed};
+    RT_TRY(K.check(keys, entry));
+    const std::string null_arg = std::string("NULL argument to ") + entry;
+    if (!ctx || (n && !d_points)) return fail(RT_ERR_INVALID_ARG, null_arg);
+    DeviceGuard g(ctx->device);
+    QueryParams q;
+    RT_TRY(query_params(ctx, sc, opts, K.reads(kReadLevel), q));
+    if (n == 0 || light_columns(q, K.keyed) == 0) return RT_OK;
+    if (!d_T) return fail(RT_ERR_INVALID_ARG, null_arg);
+    return enqueue_light_transmittance(ctx, q, d_points, n, d_T, K.device(K.k.pixel));
+}
+
+rt_status light_transmittance_host(rt_context* ctx, const rt_scene* sc,
+                                   const rt_render_opts* opts, const double* points, size_t n,
+                                   double* T_out, const rt_area_keys* keys, bool keyed,
+                                   const char* entry) {
+    EntryKeys K{keyed};
+    RT_TRY(K.check(keys, entry));
+    const std::string null_arg = std::string("NULL argument to ") + entry;
+    if (!ctx || (n && !points)) return fail(RT_ERR_INVALID_ARG, null_arg);
+    DeviceGuard g(ctx->device);
+    QueryParams q;
+    RT_TRY(query_params(ctx, sc, opts, K.reads(kReadLevel), q));
+    const size_t cols = light_columns(q, K.keyed);
+    if (n == 0 || cols == 0) return RT_OK;
+    if (!T_out) return fail(RT_ERR_INVALID_ARG, null_arg);
+    Stage s(ctx);
+    const int i_pts = s.in(points, n * kRayBytes), i_key = K.stage(s, n),
+              i_out = s.out(T_out, n * cols * sizeof(double));
+    RT_TRY(s.upload());
+    RT_TRY(enqueue_light_transmittance(ctx, q, s.at(i_pts), n, s.at(i_out),
+                                       K.device(s.at(i_key))));
+    return s.finish();
+}
+
+rt_status direct_light_device(rt_context* ctx, const rt_scene* sc, const rt_render_opts* opts,
+                              const void* d_points, const void* d_materials, size_t n_materials,
+                              size_t n, int outputs, const rt_direct_light_out* d_out,
+                              const rt_area_keys* keys, bool keyed, const char* entry) {
+    EntryKeys K{keyed};
+    RT_TRY(K.check(keys, entry));
+    RT_TRY(check_outputs(kDlOut, outputs, d_out, !n || (d_points && d_materials), ctx, entry,
+                         !n || n_materials == n || n_materials == 1));
+    if (n == 0) return RT_OK;
+    DeviceGuard g(ctx->device);
+    QueryParams q;
+    RT_TRY(query_params(ctx, sc, opts, K.reads(kReadLevel), q));
+    return enqueue_direct_light(ctx, q, d_points, d_materials,
+                                n_materials == 1 ? d_materials : nullptr, n,
+                                requested(kDlOut, outputs, *d_out), K.device(K.k.pixel));
+}
+
+rt_status direct_light_host(rt_context* ctx, const rt_scene* sc, const rt_render_opts* opts,
+                            const double* points, const rt_material* materials,
+                            size_t n_materials, size_t n, int outputs,
+                            const rt_direct_light_out* out, const rt_area_keys* keys, bool keyed,
+                            const char* entry) {
+    EntryKeys K{keyed};
+    RT_TRY(K.check(keys, entry));
+    RT_TRY(check_outputs(kDlOut, outputs, out, !n || (points && materials), ctx, entry,
+                         !n || n_materials == n || n_materials == 1));
+    if (n == 0) return RT_OK;
+    DeviceGuard g(ctx->device);
+    QueryParams q;
+    RT_TRY(query_params(ctx, sc, opts, K.reads(kReadLevel), q));
+    const bool shared = n_materials == 1;
+    Stage s(ctx);
+    const int i_pts = s.in(points, n * 9 * sizeof(double)),
+              i_mat = s.in(materials, shared ? 0 : n * sizeof(rt_material)),
+              i_key = K.stage(s, n), i_out = s.outs(kDlOut, outputs, *out, n);
+    RT_TRY(s.upload());
+    RT_TRY(enqueue_direct_light(ctx, q, s.at(i_pts), s.at(i_mat), shared ? materials : nullptr, n,
+                                s.outs_at(kDlOut, i_out), K.device(s.at(i_key))));
+    return s.finish();
+}
+
+rt_status direct_light_rays_device(rt_context* ctx, const rt_scene* sc,
+                                   const rt_render_opts* opts, const void* d_rays, size_t n,
+                                   int outputs, const rt_direct_light_out* d_out,
+                                   const rt_area_keys* keys, bool keyed, const char* entry) {
+    EntryKeys K{keyed};
+    RT_TRY(K.check(keys, entry));
+    RT_TRY(check_outputs(kDlOut, outputs, d_out, !n || d_rays, ctx, entry));
+    if (n == 0) return RT_OK;
+    DeviceGuard g(ctx->device);
+    QueryParams q;
+    RT_TRY(query_params(ctx, sc, opts, K.reads(kReadLevel), q));
+    return enqueue_direct_light_rays(ctx, q, d_rays, n, requested(kDlOut, outputs, *d_out),
+                                     K.device(K.k.pixel));
+}
+
+rt_status direct_light_rays_host(rt_context* ctx, const rt_scene* sc, const rt_render_opts* opts,
+                                 const double* rays, size_t n, int outputs,
+                                 const rt_direct_light_out* out, const rt_area_keys* keys,
+                                 bool keyed, const char* entry) {
+    EntryKeys K{keyed};
+    RT_TRY(K.check(keys, entry));
+    RT_TRY(check_outputs(kDlOut, outputs, out, !n || rays, ctx, entry));
+    if (n == 0) return RT_OK;
+    DeviceGuard g(ctx->device);
+    QueryParams q;
+    RT_TRY(query_params(ctx, sc, opts, K.reads(kReadLevel), q));
+    Stage s(ctx);
+    const int i_rays = s.in(rays, n * kRayBytes), i_key = K.stage(s, n),
+              i_out = s.outs(kDlOut, outputs, *out, n);
+    RT_TRY(s.upload());
+    RT_TRY(enqueue_direct_light_rays(ctx, q, s.at(i_rays), n, s.outs_at(kDlOut, i_out),
+                                     K.device(s.at(i_key))));
+    return s.finish();
+}
+
+rt_status scatter_rays_device(rt_context* ctx, const rt_scene* sc, const rt_render_opts* opts,
+                              const void* d_rays, size_t n, int outputs,
+                              const rt_scatter_out* d_out, const rt_area_keys* keys, bool keyed,
+                              const char* entry) {
+    EntryKeys K{keyed};
+    RT_TRY(K.check(keys, entry));
+    RT_TRY(check_outputs(kScOut, outputs, d_out, !n || d_rays, ctx, entry));
+    if (n == 0) return RT_OK;
+    DeviceGuard g(ctx->device);
+    QueryParams q;
+    RT_TRY(query_params(ctx, sc, opts, K.reads(kReadLevel | kReadRecursion), q));
+    return enqueue_scatter(ctx, q, d_rays, n, requested(kScOut, outputs, *d_out),
+                           K.device(K.k.pixel));
+}
+
+rt_status scatter_rays_host(rt_context* ctx, const rt_scene* sc, const rt_render_opts* opts,
+                            const double* rays, size_t n, int outputs, const rt_scatter_out* out,
+                            const rt_area_keys* keys, bool keyed, const char* entry) {
+    EntryKeys K{keyed};
+    RT_TRY(K.check(keys, entry));
+    RT_TRY(check_outputs(kScOut, outputs, out, !n || rays, ctx, entry));
+    if (n == 0) return RT_OK;
+    DeviceGuard g(ctx->device);
+    QueryParams q;
+    RT_TRY(query_params(ctx, sc, opts, K.reads(kReadLevel | kReadRecursion), q));
+    Stage s(ctx);
+    const int i_rays = s.in(rays, n * kRayBytes), i_key = K.stage(s, n),
+              i_out = s.outs(kScOut, outputs, *out, n);
+    RT_TRY(s.upload());
+    RT_TRY(enqueue_scatter(ctx, q, s.at(i_rays), n, s.outs_at(kScOut, i_out),
+                           K.device(s.at(i_key))));
+    return s.finish();
 }
 
 }  // namespace
@@ -552,168 +706,47 @@ rt_status rt_transmittance_rays(rt_context* ctx, const rt_scene* sc, const rt_re
     return s.finish();
 }
 
-// With no lights nothing is written and there is no output to point to: a NULL one is accepted.
+// ---- the per-level queries (rt_transmit.hip, rt_direct.hip, rt_scatter.hip) -------------------
+// Sixteen entries over the eight implementations above: {host, _device} x {un-keyed, _keyed}.
 rt_status rt_light_transmittance_device(rt_context* ctx, const rt_scene* sc,
                                         const rt_render_opts* opts, const void* d_points, size_t n,
                                         void* d_T) {
-    if (!ctx || (n && !d_points))
-        return fail(RT_ERR_INVALID_ARG, "NULL argument to rt_light_transmittance_device");
-    DeviceGuard g(ctx->device);
-    QueryParams q;
-    RT_TRY(query_params(ctx, sc, opts, kReadNoBvh | kReadBias, q));
-    if (n == 0 || q.p.nl == 0) return RT_OK;
-    if (!d_T) return fail(RT_ERR_INVALID_ARG, "NULL argument to rt_light_transmittance_device");
-    return enqueue_light_transmittance(ctx, q, d_points, n, d_T);
+    return light_transmittance_device(ctx, sc, opts, d_points, n, d_T, nullptr, false,
+                                      "rt_light_transmittance_device");
 }
 
 rt_status rt_light_transmittance(rt_context* ctx, const rt_scene* sc, const rt_render_opts* opts,
                                  const double* points, size_t n, double* T_out) {
-    if (!ctx || (n && !points))
-        return fail(RT_ERR_INVALID_ARG, "NULL argument to rt_light_transmittance");
-    DeviceGuard g(ctx->device);
-    QueryParams q;
-    RT_TRY(query_params(ctx, sc, opts, kReadNoBvh | kReadBias, q));
-    if (n == 0 || q.p.nl == 0) return RT_OK;
-    if (!T_out) return fail(RT_ERR_INVALID_ARG, "NULL argument to rt_light_transmittance");
-    Stage s(ctx);
-    const int i_pts = s.in(points, n * kRayBytes),
-              i_out = s.out(T_out, n * static_cast<size_t>(q.p.nl) * sizeof(double));
-    RT_TRY(s.upload());
-    RT_TRY(enqueue_light_transmittance(ctx, q, s.at(i_pts), n, s.at(i_out)));
-    return s.finish();
+    return light_transmittance_host(ctx, sc, opts, points, n, T_out, nullptr, false,
+                                    "rt_light_transmittance");
 }
 
-// ---- direct lighting (rt_direct.hip) -----------------------------------------------------------
-// These, the scatter and the closest-hit entries return RT_OK for n == 0 before the scene or a
-// device is touched.  With n_materials == 1 the material is a host record, for both twins.
-rt_status rt_direct_light_device(rt_context* ctx, const rt_scene* sc, const rt_render_opts* opts,
-                                 const void* d_points, const void* d_materials, size_t n_materials,
-                                 size_t n, int outputs, const struct rt_direct_light_out* d_out) {
-    RT_TRY(check_outputs(kDlOut, outputs, d_out, !n || (d_points && d_materials), ctx,
-                         "rt_direct_light_device", !n || n_materials == n || n_materials == 1));
-    if (n == 0) return RT_OK;
-    DeviceGuard g(ctx->device);
-    QueryParams q;
-    RT_TRY(query_params(ctx, sc, opts, kReadNoBvh | kReadBias, q));
-    return enqueue_direct_light(ctx, q, d_points, d_materials,
-                                n_materials == 1 ? d_materials : nullptr, n,
-                                requested(kDlOut, outputs, *d_out));
-}
-
-rt_status rt_direct_light(rt_context* ctx, const rt_scene* sc, const rt_render_opts* opts,
-                          const double* points, const rt_material* materials, size_t n_materials,
-                          size_t n, int outputs, const struct rt_direct_light_out* out) {
-    RT_TRY(check_outputs(kDlOut, outputs, out, !n || (points && materials), ctx, "rt_direct_light",
-                         !n || n_materials == n || n_materials == 1));
-    if (n == 0) return RT_OK;
-    DeviceGuard g(ctx->device);
-    QueryParams q;
-    RT_TRY(query_params(ctx, sc, opts, kReadNoBvh | kReadBias, q));
-    const bool shared = n_materials == 1;
-    Stage s(ctx);
-    const int i_pts = s.in(points, n * 9 * sizeof(double)),
-              i_mat = s.in(materials, shared ? 0 : n * sizeof(rt_material)),
-              i_out = s.outs(kDlOut, outputs, *out, n);
-    RT_TRY(s.upload());
-    RT_TRY(enqueue_direct_light(ctx, q, s.at(i_pts), s.at(i_mat),
-                                shared ? materials : nullptr, n, s.outs_at(kDlOut, i_out)));
-    return s.finish();
-}
-
-rt_status rt_direct_light_rays_device(rt_context* ctx, const rt_scene* sc,
-                                      const rt_render_opts* opts, const void* d_rays, size_t n,
-                                      int outputs, const struct rt_direct_light_out* d_out) {
-    RT_TRY(check_outputs(kDlOut, outputs, d_out, !n || d_rays, ctx, "rt_direct_light_rays_device"));
-    if (n == 0) return RT_OK;
-    DeviceGuard g(ctx->device);
-    QueryParams q;
-    RT_TRY(query_params(ctx, sc, opts, kReadNoBvh | kReadBias, q));
-    return enqueue_direct_light_rays(ctx, q, d_rays, n, requested(kDlOut, outputs, *d_out));
-}
-
-rt_status rt_direct_light_rays(rt_context* ctx, const rt_scene* sc, const rt_render_opts* opts,
-                               const double* rays, size_t n, int outputs,
-                               const struct rt_direct_light_out* out) {
-    RT_TRY(check_outputs(kDlOut, outputs, out, !n || rays, ctx, "rt_direct_light_rays"));
-    if (n == 0) return RT_OK;
-    DeviceGuard g(ctx->device);
-    QueryParams q;
-    RT_TRY(query_params(ctx, sc, opts, kReadNoBvh | kReadBias, q));
-    Stage s(ctx);
-    const int i_rays = s.in(rays, n * kRayBytes), i_out = s.outs(kDlOut, outputs, *out, n);
-    RT_TRY(s.upload());
-    RT_TRY(enqueue_direct_light_rays(ctx, q, s.at(i_rays), n, s.outs_at(kDlOut, i_out)));
-    return s.finish();
-}
-
-// ---- scatter (rt_scatter.hip) ------------------------------------------------------------------
-rt_status rt_scatter_rays_device(rt_context* ctx, const rt_scene* sc, const rt_render_opts* opts,
-                                 const void* d_rays, size_t n, int outputs,
-                                 const struct rt_scatter_out* d_out) {
-    RT_TRY(check_outputs(kScOut, outputs, d_out, !n || d_rays, ctx, "rt_scatter_rays_device"));
-    if (n == 0) return RT_OK;
-    DeviceGuard g(ctx->device);
-    QueryParams q;
-    RT_TRY(query_params(ctx, sc, opts, kReadNoBvh | kReadBias | kReadRecursion, q));
-    return enqueue_scatter(ctx, q, d_rays, n, requested(kScOut, outputs, *d_out));
-}
-
-rt_status rt_scatter_rays(rt_context* ctx, const rt_scene* sc, const rt_render_opts* opts,
-                          const double* rays, size_t n, int outputs,
-                          const struct rt_scatter_out* out) {
-    RT_TRY(check_outputs(kScOut, outputs, out, !n || rays, ctx, "rt_scatter_rays"));
-    if (n == 0) return RT_OK;
-    DeviceGuard g(ctx->device);
-    QueryParams q;
-    RT_TRY(query_params(ctx, sc, opts, kReadNoBvh | kReadBias | kReadRecursion, q));
-    Stage s(ctx);
-    const int i_rays = s.in(rays, n * kRayBytes), i_out = s.outs(kScOut, outputs, *out, n);
-    RT_TRY(s.upload());
-    RT_TRY(enqueue_scatter(ctx, q, s.at(i_rays), n, s.outs_at(kScOut, i_out)));
-    return s.finish();
-}
-
-// ---- the same four queries with the area light served (rt_area_queries.hip) --------------------
-// Each is its sibling plus the keys: checked first, the pixel keys one more staged input of the
-// host entries, opts->seed read next to what the sibling reads.
 rt_status rt_light_transmittance_keyed_device(rt_context* ctx, const rt_scene* sc,
                                               const rt_render_opts* opts, const void* d_points,
                                               size_t n, void* d_T, const rt_area_keys* keys) {
-    rt_area_keys k;
-    RT_TRY(check_keys(keys, "rt_light_transmittance_keyed_device", k));
-    if (!ctx || (n && !d_points))
-        return fail(RT_ERR_INVALID_ARG, "NULL argument to rt_light_transmittance_keyed_device");
-    DeviceGuard g(ctx->device);
-    QueryParams q;
-    RT_TRY(query_params(ctx, sc, opts, kReadKeyed, q));
-    if (n == 0 || light_columns(q, true) == 0) return RT_OK;
-    if (!d_T)
-        return fail(RT_ERR_INVALID_ARG, "NULL argument to rt_light_transmittance_keyed_device");
-    const AreaKeyArgs dk = device_keys(k, k.pixel);
-    return enqueue_light_transmittance(ctx, q, d_points, n, d_T, &dk);
+    return light_transmittance_device(ctx, sc, opts, d_points, n, d_T, keys, true,
+                                      "rt_light_transmittance_keyed_device");
 }
 
 rt_status rt_light_transmittance_keyed(rt_context* ctx, const rt_scene* sc,
                                        const rt_render_opts* opts, const double* points, size_t n,
                                        double* T_out, const rt_area_keys* keys) {
-    rt_area_keys k;
-    RT_TRY(check_keys(keys, "rt_light_transmittance_keyed", k));
-    if (!ctx || (n && !points))
-        return fail(RT_ERR_INVALID_ARG, "NULL argument to rt_light_transmittance_keyed");
-    DeviceGuard g(ctx->device);
-    QueryParams q;
-    RT_TRY(query_params(ctx, sc, opts, kReadKeyed, q));
-    const size_t cols = light_columns(q, true);
-    if (n == 0 || cols == 0) return RT_OK;
-    if (!T_out) return fail(RT_ERR_INVALID_ARG, "NULL argument to rt_light_transmittance_keyed");
-    Stage s(ctx);
-    const int i_pts = s.in(points, n * kRayBytes),
-              i_key = s.in(k.pixel, k.pixel ? n * sizeof(uint64_t) : 0),
-              i_out = s.out(T_out, n * cols * sizeof(double));
-    RT_TRY(s.upload());
-    const AreaKeyArgs dk = device_keys(k, s.at(i_key));
-    RT_TRY(enqueue_light_transmittance(ctx, q, s.at(i_pts), n, s.at(i_out), &dk));
-    return s.finish();
+    return light_transmittance_host(ctx, sc, opts, points, n, T_out, keys, true,
+                                    "rt_light_transmittance_keyed");
+}
+
+rt_status rt_direct_light_device(rt_context* ctx, const rt_scene* sc, const rt_render_opts* opts,
+                                 const void* d_points, const void* d_materials, size_t n_materials,
+                                 size_t n, int outputs, const struct rt_direct_light_out* d_out) {
+    return direct_light_device(ctx, sc, opts, d_points, d_materials, n_materials, n, outputs,
+                               d_out, nullptr, false, "rt_direct_light_device");
+}
+
+rt_status rt_direct_light(rt_context* ctx, const rt_scene* sc, const rt_render_opts* opts,
+                          const double* points, const rt_material* materials, size_t n_materials,
+                          size_t n, int outputs, const struct rt_direct_light_out* out) {
+    return direct_light_host(ctx, sc, opts, points, materials, n_materials, n, outputs, out,
+                             nullptr, false, "rt_direct_light");
 }
 
 rt_status rt_direct_light_keyed_device(rt_context* ctx, const rt_scene* sc,
@@ -721,44 +754,30 @@ rt_status rt_direct_light_keyed_device(rt_context* ctx, const rt_scene* sc,
                                        const void* d_materials, size_t n_materials, size_t n,
                                        int outputs, const struct rt_direct_light_out* d_out,
                                        const rt_area_keys* keys) {
-    rt_area_keys k;
-    RT_TRY(check_keys(keys, "rt_direct_light_keyed_device", k));
-    RT_TRY(check_outputs(kDlOut, outputs, d_out, !n || (d_points && d_materials), ctx,
-                         "rt_direct_light_keyed_device",
-                         !n || n_materials == n || n_materials == 1));
-    if (n == 0) return RT_OK;
-    DeviceGuard g(ctx->device);
-    QueryParams q;
-    RT_TRY(query_params(ctx, sc, opts, kReadKeyed, q));
-    const AreaKeyArgs dk = device_keys(k, k.pixel);
-    return enqueue_direct_light(ctx, q, d_points, d_materials,
-                                n_materials == 1 ? d_materials : nullptr, n,
-                                requested(kDlOut, outputs, *d_out), &dk);
+    return direct_light_device(ctx, sc, opts, d_points, d_materials, n_materials, n, outputs,
+                               d_out, keys, true, "rt_direct_light_keyed_device");
 }
 
 rt_status rt_direct_light_keyed(rt_context* ctx, const rt_scene* sc, const rt_render_opts* opts,
                                 const double* points, const rt_material* materials,
                                 size_t n_materials, size_t n, int outputs,
                                 const struct rt_direct_light_out* out, const rt_area_keys* keys) {
-    rt_area_keys k;
-    RT_TRY(check_keys(keys, "rt_direct_light_keyed", k));
-    RT_TRY(check_outputs(kDlOut, outputs, out, !n || (points && materials), ctx,
-                         "rt_direct_light_keyed", !n || n_materials == n || n_materials == 1));
-    if (n == 0) return RT_OK;
-    DeviceGuard g(ctx->device);
-    QueryParams q;
-    RT_TRY(query_params(ctx, sc, opts, kReadKeyed, q));
-    const bool shared = n_materials == 1;
-    Stage s(ctx);
-    const int i_pts = s.in(points, n * 9 * sizeof(double)),
-              i_mat = s.in(materials, shared ? 0 : n * sizeof(rt_material)),
-              i_key = s.in(k.pixel, k.pixel ? n * sizeof(uint64_t) : 0),
-              i_out = s.outs(kDlOut, outputs, *out, n);
-    RT_TRY(s.upload());
-    const AreaKeyArgs dk = device_keys(k, s.at(i_key));
-    RT_TRY(enqueue_direct_light(ctx, q, s.at(i_pts), s.at(i_mat), shared ? materials : nullptr, n,
-                                s.outs_at(kDlOut, i_out), &dk));
-    return s.finish();
+    return direct_light_host(ctx, sc, opts, points, materials, n_materials, n, outputs, out, keys,
+                             true, "rt_direct_light_keyed");
+}
+
+rt_status rt_direct_light_rays_device(rt_context* ctx, const rt_scene* sc,
+                                      const rt_render_opts* opts, const void* d_rays, size_t n,
+                                      int outputs, const struct rt_direct_light_out* d_out) {
+    return direct_light_rays_device(ctx, sc, opts, d_rays, n, outputs, d_out, nullptr, false,
+                                    "rt_direct_light_rays_device");
+}
+
+rt_status rt_direct_light_rays(rt_context* ctx, const rt_scene* sc, const rt_render_opts* opts,
+                               const double* rays, size_t n, int outputs,
+                               const struct rt_direct_light_out* out) {
+    return direct_light_rays_host(ctx, sc, opts, rays, n, outputs, out, nullptr, false,
+                                  "rt_direct_light_rays");
 }
 
 rt_status rt_direct_light_rays_keyed_device(rt_context* ctx, const rt_scene* sc,
@@ -766,73 +785,45 @@ rt_status rt_direct_light_rays_keyed_device(rt_context* ctx, const rt_scene* sc,
                                             size_t n, int outputs,
                                             const struct rt_direct_light_out* d_out,
                                             const rt_area_keys* keys) {
-    rt_area_keys k;
-    RT_TRY(check_keys(keys, "rt_direct_light_rays_keyed_device", k));
-    RT_TRY(check_outputs(kDlOut, outputs, d_out, !n || d_rays, ctx,
-                         "rt_direct_light_rays_keyed_device"));
-    if (n == 0) return RT_OK;
-    DeviceGuard g(ctx->device);
-    QueryParams q;
-    RT_TRY(query_params(ctx, sc, opts, kReadKeyed, q));
-    const AreaKeyArgs dk = device_keys(k, k.pixel);
-    return enqueue_direct_light_rays(ctx, q, d_rays, n, requested(kDlOut, outputs, *d_out), &dk);
+    return direct_light_rays_device(ctx, sc, opts, d_rays, n, outputs, d_out, keys, true,
+                                    "rt_direct_light_rays_keyed_device");
 }
 
 rt_status rt_direct_light_rays_keyed(rt_context* ctx, const rt_scene* sc,
                                      const rt_render_opts* opts, const double* rays, size_t n,
                                      int outputs, const struct rt_direct_light_out* out,
                                      const rt_area_keys* keys) {
-    rt_area_keys k;
-    RT_TRY(check_keys(keys, "rt_direct_light_rays_keyed", k));
-    RT_TRY(check_outputs(kDlOut, outputs, out, !n || rays, ctx, "rt_direct_light_rays_keyed"));
-    if (n == 0) return RT_OK;
-    DeviceGuard g(ctx->device);
-    QueryParams q;
-    RT_TRY(query_params(ctx, sc, opts, kReadKeyed, q));
-    Stage s(ctx);
-    const int i_rays = s.in(rays, n * kRayBytes),
-              i_key = s.in(k.pixel, k.pixel ? n * sizeof(uint64_t) : 0),
-              i_out = s.outs(kDlOut, outputs, *out, n);
-    RT_TRY(s.upload());
-    const AreaKeyArgs dk = device_keys(k, s.at(i_key));
-    RT_TRY(enqueue_direct_light_rays(ctx, q, s.at(i_rays), n, s.outs_at(kDlOut, i_out), &dk));
-    return s.finish();
+    return direct_light_rays_host(ctx, sc, opts, rays, n, outputs, out, keys, true,
+                                  "rt_direct_light_rays_keyed");
+}
+
+rt_status rt_scatter_rays_device(rt_context* ctx, const rt_scene* sc, const rt_render_opts* opts,
+                                 const void* d_rays, size_t n, int outputs,
+                                 const struct rt_scatter_out* d_out) {
+    return scatter_rays_device(ctx, sc, opts, d_rays, n, outputs, d_out, nullptr, false,
+                               "rt_scatter_rays_device");
+}
+
+rt_status rt_scatter_rays(rt_context* ctx, const rt_scene* sc, const rt_render_opts* opts,
+                          const double* rays, size_t n, int outputs,
+                          const struct rt_scatter_out* out) {
+    return scatter_rays_host(ctx, sc, opts, rays, n, outputs, out, nullptr, false,
+                             "rt_scatter_rays");
 }
 
 rt_status rt_scatter_rays_keyed_device(rt_context* ctx, const rt_scene* sc,
                                        const rt_render_opts* opts, const void* d_rays, size_t n,
                                        int outputs, const struct rt_scatter_out* d_out,
                                        const rt_area_keys* keys) {
-    rt_area_keys k;
-    RT_TRY(check_keys(keys, "rt_scatter_rays_keyed_device", k));
-    RT_TRY(check_outputs(kScOut, outputs, d_out, !n || d_rays, ctx,
-                         "rt_scatter_rays_keyed_device"));
-    if (n == 0) return RT_OK;
-    DeviceGuard g(ctx->device);
-    QueryParams q;
-    RT_TRY(query_params(ctx, sc, opts, kReadKeyed | kReadRecursion, q));
-    const AreaKeyArgs dk = device_keys(k, k.pixel);
-    return enqueue_scatter(ctx, q, d_rays, n, requested(kScOut, outputs, *d_out), &dk);
+    return scatter_rays_device(ctx, sc, opts, d_rays, n, outputs, d_out, keys, true,
+                               "rt_scatter_rays_keyed_device");
 }
 
 rt_status rt_scatter_rays_keyed(rt_context* ctx, const rt_scene* sc, const rt_render_opts* opts,
                                 const double* rays, size_t n, int outputs,
                                 const struct rt_scatter_out* out, const rt_area_keys* keys) {
-    rt_area_keys k;
-    RT_TRY(check_keys(keys, "rt_scatter_rays_keyed", k));
-    RT_TRY(check_outputs(kScOut, outputs, out, !n || rays, ctx, "rt_scatter_rays_keyed"));
-    if (n == 0) return RT_OK;
-    DeviceGuard g(ctx->device);
-    QueryParams q;
-    RT_TRY(query_params(ctx, sc, opts, kReadKeyed | kReadRecursion, q));
-    Stage s(ctx);
-    const int i_rays = s.in(rays, n * kRayBytes),
-              i_key = s.in(k.pixel, k.pixel ? n * sizeof(uint64_t) : 0),
-              i_out = s.outs(kScOut, outputs, *out, n);
-    RT_TRY(s.upload());
-    const AreaKeyArgs dk = device_keys(k, s.at(i_key));
-    RT_TRY(enqueue_scatter(ctx, q, s.at(i_rays), n, s.outs_at(kScOut, i_out), &dk));
-    return s.finish();
+    return scatter_rays_host(ctx, sc, opts, rays, n, outputs, out, keys, true,
+                             "rt_scatter_rays_keyed");
 }
 
 // ---- closest hit with selectable outputs (rt_closest.hip) --------------------------------------

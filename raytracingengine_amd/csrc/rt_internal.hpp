@@ -297,15 +297,27 @@ hipError_t launch_intersect_rays(const TraceParams& p, const double* rays, size_
 // Any-hit query (rt_anyhit.hip): per ray, 1 iff a primitive lies at 0 < t < max_dist[i].
 hipError_t launch_occluded_rays(const TraceParams& p, const double* rays, const double* max_dist,
                                 size_t n, uint8_t* out, hipStream_t stream);
+// The keys of the build-defined area light's draws, for the per-level queries below.  Each
+// launch takes `keys`: null is the un-keyed kernel (point lights only); with keys, and only for
+// p.al_samples > 0, the keyed_ kernel, which serves the area light's samples after the point
+// lights.  keys->pixel: n device keys, or null (element i draws with pixel = i); the draws are
+// keyed (p.seed, pixel, 0x10000 + (sample << 6) + depth, 2s | 2s + 1) as direct_terms keys them.
+struct AreaKeyArgs {
+    const unsigned long long* pixel;
+    uint32_t sample;
+    uint32_t depth;
+};
 // Transmittance queries (rt_transmit.hip): per ray, computeTransmittance(ray, max_dist[i], p.bias);
-// per point {p, normal} and point light l, directLightning's shadow ray, out[i * p.nl + l].
+// per point {p, normal} and point light l, directLightning's shadow ray, out[i * p.nl + l] — with
+// keys served, nl + al_samples columns per point, the samples after the lights.
 // opaque: the scene has no transparent material (the variant that asks occlusion_opaque first).
 hipError_t launch_transmittance_rays(const TraceParams& p, bool opaque, const double* rays,
                                      const double* max_dist, size_t n, double* out,
                                      hipStream_t stream);
 hipError_t launch_light_transmittance(const TraceParams& p, bool opaque, const double* points,
-                                      size_t n, double* out, hipStream_t stream);
-// Direct-lighting queries (rt_direct.hip): directLightning (Scene.h:79-129) over the scene's point
+                                      const AreaKeyArgs* keys, size_t n, double* out,
+                                      hipStream_t stream);
+// Direct-lighting queries (rt_direct.hip): directLightning (Scene.h:79-129) over the scene's
 // lights, per point {p, normal, view} with a material of rt_material's layout (materials: one per
 // point, or null: `shared` for all of them), and per ray at its closest hit with the hit
 // primitive's material (a miss writes zeros).  Each output is [n][3] doubles, or null: not written.
@@ -318,14 +330,16 @@ struct DlMaterial {
     double v[8];  // r g b shininess specular transparency ior -
 };
 hipError_t launch_direct_light_points(const TraceParams& p, bool opaque, const double* points,
-                                      const double* materials, const DlMaterial& shared, size_t n,
-                                      const DlOut& out, hipStream_t stream);
-hipError_t launch_direct_light_rays(const TraceParams& p, bool opaque, const double* rays, size_t n,
-                                    const DlOut& out, hipStream_t stream);
+                                      const double* materials, const DlMaterial& shared,
+                                      const AreaKeyArgs* keys, size_t n, const DlOut& out,
+                                      hipStream_t stream);
+hipError_t launch_direct_light_rays(const TraceParams& p, bool opaque, const double* rays,
+                                    const AreaKeyArgs* keys, size_t n, const DlOut& out,
+                                    hipStream_t stream);
 // Scatter query (rt_scatter.hip): one TraceRay level (Scene.h:131-198) per ray, before its
 // children are traced — shade_hit's Node written out.  p.max_rec <= 0: every ray is at the
-// recursion limit (sky, no intersection).  The area light is not read (launch_keyed_scatter
-// reads it).  A null output is not written; at least one is set.
+// recursion limit (sky, no intersection).  keys are served only with out.value set.  A null
+// output is not written; at least one is set.
 struct ScOut {
     double* value;         // [n][3] sky on a miss, else localLight * (1 - transparency)
     double* refract_rays;  // [n][6] {o, d}, zeros where absent
@@ -333,32 +347,9 @@ struct ScOut {
     double* weights;       // [n][2] {fw, rw}, zero where the child is absent
     uint8_t* flags;        // [n]    bit 0 hit, bit 1 refraction ray, bit 2 reflection ray
 };
-hipError_t launch_scatter_rays(const TraceParams& p, bool opaque, const double* rays, size_t n,
-                               const ScOut& out, hipStream_t stream);
-// The keyed twins of the four per-level queries above (rt_area_queries.hip): the same answers with
-// the build-defined area light served — direct()'s samples appended after the point lights; for
-// the shadow points nl + al_samples columns per point, the samples after the lights.  Only for
-// p.al_samples > 0, and the scatter only with out.value set: everything else is the un-keyed
-// launch's.  keys.pixel: n device keys, or null (element i draws with pixel = i); the draws are
-// keyed (p.seed, pixel, 0x10000 + (sample << 6) + depth, 2s | 2s + 1) as direct() keys them.
-struct AreaKeyArgs {
-    const unsigned long long* pixel;
-    uint32_t sample;
-    uint32_t depth;
-};
-hipError_t launch_keyed_scatter(const TraceParams& p, bool opaque, const double* rays,
-                                const AreaKeyArgs& keys, size_t n, const ScOut& out,
-                                hipStream_t stream);
-hipError_t launch_keyed_direct_points(const TraceParams& p, bool opaque, const double* points,
-                                      const double* materials, const DlMaterial& shared,
-                                      const AreaKeyArgs& keys, size_t n, const DlOut& out,
-                                      hipStream_t stream);
-hipError_t launch_keyed_direct_rays(const TraceParams& p, bool opaque, const double* rays,
-                                    const AreaKeyArgs& keys, size_t n, const DlOut& out,
-                                    hipStream_t stream);
-hipError_t launch_keyed_shadow_points(const TraceParams& p, bool opaque, const double* points,
-                                      const AreaKeyArgs& keys, size_t n, double* out,
-                                      hipStream_t stream);
+hipError_t launch_scatter_rays(const TraceParams& p, bool opaque, const double* rays,
+                               const AreaKeyArgs* keys, size_t n, const ScOut& out,
+                               hipStream_t stream);
 // Camera rays (rt_camera_rays.hip): Camera::getRay(x, y, sample > 0 && p.aa > 1) for every pixel
 // of p's row set, {o, d} per pixel at its rows-local index; the jitter key is the render
 // kernels' (p.seed, y_image * W + x, sample).  out: p.rows * p.width * 6 doubles.

@@ -1,7 +1,16 @@
 // rt_query_out.hpp — what the per-level batch queries (rt_transmit.hip, rt_direct.hip,
-// rt_scatter.hip) and their keyed twins (rt_area_queries.hip) share besides the shading of
-// rt_trace_common.hpp: the 16-byte record loads, computeTransmittance with its fast path, and the
-// stores of the output records (DlOut, ScOut).  Plain vector stores, one thread per element.
+// rt_scatter.hip), un-keyed and keyed, share besides the shading of rt_trace_common.hpp: the
+// 16-byte record loads, the pixel key of an element, computeTransmittance with its fast path, the
+// shadow ray of one light point, and the stores of the output records (DlOut, ScOut).  Plain
+// vector stores, one thread per element.
+//
+// Each query's kernel body is written once, with a bool AREA: false is the un-keyed kernel, whose
+// SceneView says the scene has no area light (S.al = 0, a constant there, so no sample loop is
+// compiled in) and which ignores the keys; true serves the area light's samples under the
+// caller's keys — one 64-bit pixel key per element (or none: element i draws with pixel = i, the
+// rule of rt_trace_rays), the sample and the depth for the whole batch.  Whether there are pixel
+// keys is a kernel argument, so that test is a scalar branch; sample, depth and the seed travel
+// in the kernel arguments and stay scalar.
 #pragma once
 
 #include "rt_trace_common.hpp"
@@ -16,6 +25,10 @@ typedef double d2u __attribute__((ext_vector_type(2), aligned(8)));
 
 __device__ __forceinline__ d2u load2(const double* p) { return *reinterpret_cast<const d2u*>(p); }
 
+__device__ __forceinline__ uint64_t pixel_key(const AreaKeyArgs& k, size_t i) {
+    return k.pixel ? static_cast<uint64_t>(k.pixel[i]) : static_cast<uint64_t>(i);
+}
+
 // computeTransmittance(ray {o, d}, max_dist, bias).  A max_dist that is NaN or <= 0 never enters
 // the march's loop (traveled = 0 < max_dist is false): 1.0, asked before the classification,
 // whose margins are formed from max_dist.
@@ -28,6 +41,19 @@ __device__ __forceinline__ double transmit_ray(const SceneView& S, d3 o, d3 d, d
         if (occ >= 0) return static_cast<double>(occ);
     }
     return transmittance(S, o, d, max_dist, bias);
+}
+
+// The seven steps of rt_light_transmittance (rt_capi.h) from point p to the light point lpos; the
+// three skips are directLightning's `continue`s (Scene.h:89, 92, 95) and answer 0.0.
+template <bool OPAQUE>
+__device__ __forceinline__ double shadow_T(const SceneView& S, d3 p, d3 normal, d3 lpos,
+                                           double bias) {
+    double dist, inv_d2;
+    d3 L;
+    light_dir(lpos - p, dist, L, inv_d2);
+    if (!(dist <= 0.0) && !(smax(0.0, dot(normal, L)) <= 0.0) && !(dist <= bias))
+        return transmit_ray<OPAQUE>(S, p + normal * bias, L, dist - bias, bias);
+    return 0.0;
 }
 
 __device__ __forceinline__ void store3(double* base, size_t i, d3 v) {

@@ -652,40 +652,54 @@ __device__ __forceinline__ void light_term_wave(const SceneView& S, bool active,
     }
 }
 
-// Scene::directLightning (Scene.h:79-129), plus the build-defined area-light samples.
+// The random stream of the area light's draws at one TraceRay level of one AA sample.
+__device__ __forceinline__ uint32_t area_stream(uint32_t sample, int depth) {
+    return 0x10000u + (sample << 6) + static_cast<uint32_t>(depth);
+}
+
+// The point of area sample s: two draws keyed (seed, pix, stream, 2s | 2s + 1) place it in
+// stratum (s % k, s / k) of the k x k grid over the light's parallelogram.
+__device__ __forceinline__ d3 area_point(const TraceParams& P, uint64_t pix, uint32_t stream,
+                                         int s) {
+    const double k = static_cast<double>(P.al_k);
+    const d3 corner = mk(P.al_corner[0], P.al_corner[1], P.al_corner[2]);
+    const d3 eu = mk(P.al_u[0], P.al_u[1], P.al_u[2]);
+    const d3 ev = mk(P.al_v[0], P.al_v[1], P.al_v[2]);
+    const double r1 = u01(P.seed, pix, stream, 2u * static_cast<uint32_t>(s));
+    const double r2 = u01(P.seed, pix, stream, 2u * static_cast<uint32_t>(s) + 1u);
+    const double fu = (static_cast<double>(s % P.al_k) + r1) / k;
+    const double fv = (static_cast<double>(s / P.al_k) + r2) / k;
+    return (corner + eu * fu) + ev * fv;
+}
+
+// directLightning's light loop (Scene.h:79-124) with the build-defined area light's S.al samples
+// appended: Scene::directLightning up to, not including, its last line (Scene.h:126-128) — the
+// two accumulators, still apart.  m: {r g b shininess specular transparency ...}, read by
+// light_term at its uses.
 template <bool COUNT, bool OPQ>
-__device__ __forceinline__ d3 direct(const SceneView& S, const TraceParams& P, d3 hp, d3 view,
-                                     d3 n_in, const double* m, uint64_t pix, uint32_t sample,
-                                     int depth, Counts& cnt) {
+__device__ __forceinline__ void direct_terms(const SceneView& S, const TraceParams& P, d3 hp,
+                                             d3 view, d3 n_in, const double* m, uint64_t pix,
+                                             uint32_t sample, int depth, Counts& cnt,
+                                             d3& diff_out, d3& spec_out) {
     const double bias = P.bias;
-    const d3 n = unit(n_in);
+    const d3 n = unit(n_in);  // Scene.h:81
     d3 diff = mk(0.0, 0.0, 0.0), spec = mk(0.0, 0.0, 0.0);
     for (int i = 0; i < S.nl; ++i) {
         const double* l = S.lt + kLtStride * i;
         light_term<COUNT, OPQ>(S, hp, n, view, m, mk(l[0], l[1], l[2]), mk(l[3], l[4], l[5]), bias,
-                          diff, spec, cnt);
+                               diff, spec, cnt);
     }
 #ifndef RT_LEAN_GENERIC  // ... and without the area light
-    // (restated by area_terms and area_point, rt_area_queries.hip, for the queries that return the
-    // two accumulators apart: a change here is a change there)
     if (S.al > 0) {
-        const uint32_t stream = 0x10000u + (sample << 6) + static_cast<uint32_t>(depth);
-        const double k = static_cast<double>(P.al_k);
-        const d3 corner = mk(P.al_corner[0], P.al_corner[1], P.al_corner[2]);
-        const d3 eu = mk(P.al_u[0], P.al_u[1], P.al_u[2]);
-        const d3 ev = mk(P.al_v[0], P.al_v[1], P.al_v[2]);
+        const uint32_t stream = area_stream(sample, depth);
         const d3 E = mk(P.al_E[0], P.al_E[1], P.al_E[2]);
-        for (int s = 0; s < S.al; ++s) {
-            const double r1 = u01(P.seed, pix, stream, 2u * static_cast<uint32_t>(s));
-            const double r2 = u01(P.seed, pix, stream, 2u * static_cast<uint32_t>(s) + 1u);
-            const double fu = (static_cast<double>(s % P.al_k) + r1) / k;
-            const double fv = (static_cast<double>(s / P.al_k) + r2) / k;
-            const d3 lp = (corner + eu * fu) + ev * fv;
-            light_term<COUNT, OPQ>(S, hp, n, view, m, lp, E, bias, diff, spec, cnt);
-        }
+        for (int s = 0; s < S.al; ++s)
+            light_term<COUNT, OPQ>(S, hp, n, view, m, area_point(P, pix, stream, s), E, bias, diff,
+                                   spec, cnt);
     }
 #endif
-    return hmul(mk(m[0], m[1], m[2]), diff) + spec * m[4];
+    diff_out = diff;
+    spec_out = spec;
 }
 
 // What one TraceRay invocation yields before its children are traced.
@@ -738,7 +752,11 @@ __device__ __forceinline__ Node shade_hit(const SceneView& S, const TraceParams&
         __asm__ volatile("" ::: "memory");  // no forwarding of the stored values
     }
     d3 local = mk(0.0, 0.0, 0.0);
-    if constexpr (DIRECT) local = direct<COUNT, !TREE>(S, P, hp, view, n, m, pix, sample, depth, cnt);
+    if constexpr (DIRECT) {
+        d3 diff, spec;
+        direct_terms<COUNT, !TREE>(S, P, hp, view, n, m, pix, sample, depth, cnt, diff, spec);
+        local = hmul(mk(m[0], m[1], m[2]), diff) + spec * m[4];  // Scene.h:126-128
+    }
     d3 hp_c = hp, n_c = n, inc_c = inc;  // the values the child rays start from
     if (save) {
         __asm__ volatile("" ::: "memory");

@@ -393,20 +393,11 @@ __global__ __launch_bounds__(kWfThreads, RT_WF_DIRECT_WAVES) void wf_direct_kern
         }
 #ifndef RT_LEAN_GENERIC  // the build-defined area light: per-lane sample points, full marches
         if (active && P.al_samples > 0) {
-            const uint32_t stream = 0x10000u + (sample << 6) + static_cast<uint32_t>(level);
-            const double k = static_cast<double>(P.al_k);
-            const d3 corner = mk(P.al_corner[0], P.al_corner[1], P.al_corner[2]);
-            const d3 eu = mk(P.al_u[0], P.al_u[1], P.al_u[2]);
-            const d3 ev = mk(P.al_v[0], P.al_v[1], P.al_v[2]);
+            const uint32_t stream = area_stream(sample, level);
             const d3 E = mk(P.al_E[0], P.al_E[1], P.al_E[2]);
-            for (int s = 0; s < P.al_samples; ++s) {
-                const double r1 = u01(P.seed, pix, stream, 2u * static_cast<uint32_t>(s));
-                const double r2 = u01(P.seed, pix, stream, 2u * static_cast<uint32_t>(s) + 1u);
-                const double fu = (static_cast<double>(s % P.al_k) + r1) / k;
-                const double fv = (static_cast<double>(s / P.al_k) + r2) / k;
-                const d3 lp = (corner + eu * fu) + ev * fv;
-                light_term<false, false>(S, hp, nn, view, m, lp, E, bias, diff, spec, cnt);
-            }
+            for (int s = 0; s < P.al_samples; ++s)
+                light_term<false, false>(S, hp, nn, view, m, area_point(P, pix, stream, s), E, bias,
+                                         diff, spec, cnt);
         }
 #endif
         if (!active) continue;

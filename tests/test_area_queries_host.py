@@ -169,16 +169,20 @@ def test_binding_lists_the_entries():
 
 
 def test_kernels_and_register_budget():
-    """The new source is in the build recipe; its object holds the keyed kernels under names the
-    other host tests' selections do not match, each within 256 VGPRs + AGPRs: two waves per SIMD,
-    the rule tests/test_kernel_occupancy.py applies to the generic trace kernels."""
-    assert "rt_area_queries.hip" in build.SOURCES
-    ks = _kernels("rt_area_queries.hip")
-    for want, count in zip(KERNELS, (4, 4, 2, 2)):
+    """The keyed kernels stand next to their un-keyed siblings, in the objects of rt_scatter.hip,
+    rt_direct.hip and rt_transmit.hip, under names the other host tests' selections do not match,
+    each within 256 VGPRs + AGPRs: two waves per SIMD, the rule tests/test_kernel_occupancy.py
+    applies to the generic trace kernels."""
+    sources = ("rt_scatter.hip", "rt_direct.hip", "rt_direct.hip", "rt_transmit.hip")
+    keyed = {}
+    for want, source, count in zip(KERNELS, sources, (4, 4, 2, 2)):
+        assert source in build.SOURCES
+        ks = _kernels(source)
         got = {n: r for n, r in ks.items() if want in n}
         assert len(got) == count, (want, sorted(ks))
         for name, (regs, priv) in sorted(got.items()):
             print(f"{name}: {regs} registers, {priv} B private")
             assert regs <= 256, name
-    for name in ks:
+        keyed.update(got)
+    for name in keyed:
         assert not any(t in name for t in TAKEN), name

@@ -1,8 +1,10 @@
-"""The keyed queries on the device (rt_area_queries.hip): rt_scatter_rays_keyed,
+"""The keyed queries on the device (the keyed_ kernels of rt_scatter.hip, rt_direct.hip and
+rt_transmit.hip, each the un-keyed kernel's body with the area light on): rt_scatter_rays_keyed,
 rt_direct_light_keyed, rt_direct_light_rays_keyed, rt_light_transmittance_keyed and their _device
 twins — the per-level queries with the build-defined area light served under keys the caller
 supplies — on the two small area-light scenes of tests/raysets.py (c5: 16 samples, no point
-light, no pow; glass_tri_area: 4 samples, one point light, glass, mirrors and pow).
+light, no pow; glass_tri_area: 4 samples, one point light, glass, mirrors and pow).  The un-keyed
+entries, which share that body, are held to ignore the light.
 
 The comparator is tests/area_query_sets.py, which tests/test_area_queries_host.py holds to the
 oracle's TraceRay and RenderImage on the CPU; the second group below compares with the oracle
@@ -326,6 +328,60 @@ def test_no_area_light_is_the_sibling(ctx, oracle, name):
             assert_same(a, b, name)
     finally:
         ds.close()
+
+
+def _unkeyed_host(ds, w, shared):
+    """Every un-keyed host entry's answer on the rays and hit points of w, as one flat dict."""
+    rays, pts = w["rays"], w["points"]
+    out = {"light_T": ds.light_transmittance(pts[:, :6]),
+           "sc.value": ds.scatter(rays, capi.SC_VALUE)["value"]}
+    for who, res in (("rays", ds.direct_light_rays(rays, capi.DL_ALL)),
+                     ("pts", ds.direct_light(pts, w["materials"], capi.DL_ALL)),
+                     ("shared", ds.direct_light(pts, shared, capi.DL_ALL))):
+        out.update({f"{who}.{k}": v for k, v in res.items()})
+    return out
+
+
+def _unkeyed_device(ctx, ds, w, shared):
+    """The same dict from the _device entries."""
+    d_rays = torch.from_numpy(w["rays"].copy()).cuda()
+    d_pts = torch.from_numpy(w["points"].copy()).cuda()
+    d_mats = torch.from_numpy(w["materials"].copy()).cuda()
+    torch.cuda.synchronize()
+    out = {"light_T": ds.light_transmittance_device(d_pts[:, :6].contiguous()),
+           "sc.value": ds.scatter_device(d_rays, capi.SC_VALUE)["value"]}
+    for who, res in (("rays", ds.direct_light_rays_device(d_rays, capi.DL_ALL)),
+                     ("pts", ds.direct_light_device(d_pts, d_mats, capi.DL_ALL)),
+                     ("shared", ds.direct_light_device(d_pts, shared, capi.DL_ALL))):
+        out.update({f"{who}.{k}": v for k, v in res.items()})
+    ctx.synchronize()
+    return {k: v.cpu().numpy() for k, v in out.items()}
+
+
+@pytest.mark.parametrize("name", aq.SCENES)
+def test_unkeyed_entries_ignore_the_area_light(ctx, world, name):
+    """The un-keyed kernels are the keyed kernels' text with the area light switched off: on a
+    scene with its area light attached every un-keyed entry, host and _device, answers with the
+    bits it gives on the same scene built without the light.  The keyed radiance differs from the
+    un-keyed one on at least 50 rays, so the light would show."""
+    w = world(name)
+    sc, ds = w["sc"], w["ds"]
+    shared = aq.table(name, "default")["shared"]
+    bare_sc = ss.without_area_light(sc)
+    assert sc.area_light is not None and bare_sc.area_light is None
+    bare = ctx.scene(bare_sc)
+    try:
+        want = _unkeyed_host(bare, w, shared)
+        assert want["light_T"].shape == (len(w["index"]), len(sc.lights))
+        assert_outputs_same(_unkeyed_host(ds, w, shared), want, (name, "host"))
+        assert_outputs_same(_unkeyed_device(ctx, ds, w, shared), want, (name, "device, area light"))
+        assert_outputs_same(_unkeyed_device(ctx, bare, w, shared), want, (name, "device, none"))
+    finally:
+        bare.close()
+    keyed = w["got"]["default"]["rays_dl"]["radiance"]
+    differ = int((bits(keyed) != bits(want["rays.radiance"])).any(axis=1).sum())
+    print(f"{name}: the area light changes the radiance of {differ} of {len(keyed)} rays")
+    assert len(keyed) == 648 and differ >= 50
 
 
 # ------------------------------------------------------------------ 6. device forms

@@ -1,4 +1,4 @@
-"""The keyed queries (rt_area_queries.hip: the scatter, direct-light and shadow queries with the
+"""The keyed queries (the keyed_ kernels: the scatter, direct-light and shadow queries with the
 area light served) on C5 next to the kernel that already shades the same hits inside a frame.
 
 Per size (default 1920x1080 and C5's own 3840x2160, one sample per pixel):
