@@ -257,8 +257,8 @@ public:
     void AccumulateSamples(int begin, int end, std::vector<Vec3>& sum) const;
     void SetDevice(int device) { device_ = device; dev_.reset(); devices_.clear(); }
     // RenderImage / RenderImageTonemapped / RenderImageF32 over several GPUs of the node from
-    // this process: one scene copy per GPU, block-cyclic rows, assembled on the host (distinct
-    // device ids: one context per device and thread)
+    // this process: one scene copy per GPU, block-cyclic rows, gathered to the first GPU and
+    // copied to the host from there (distinct device ids: one context per device and thread)
     void SetDevices(const std::vector<int>& devices) { devices_ = devices; multi_.clear(); }
     void SetMaxRecursion(int depth) { maxRecursion = depth; }
     // build-defined area light (BASELINE config 5); nullopt removes it

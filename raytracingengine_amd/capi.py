@@ -1195,7 +1195,10 @@ class DeviceScene:
 def render_multi(scenes: list, *, hdr64=True, tonemap: int = TONEMAP_NONE, stats=False,
                  row_block: int = 0, **opt_kw) -> dict:
     """One frame over several contexts (rt_render_multi): `scenes` are DeviceScenes of the same
-    SceneData, one per context; block-cyclic rows, assembled on the host."""
+    SceneData, one per context; block-cyclic rows, gathered to the first context's device and
+    copied to the host from there (RTAMD_MULTI_HOST=1, or no framebuffer at all: each context's
+    rows copied to the host by itself).  With stats, `launches` is the rt_stats member: under
+    RT_FLAG_TIME_KERNEL one per context with rows on the host path, 1 on the gathered one."""
     L = load_library()
     n = len(scenes)
     cam = scenes[0].data.camera
@@ -1216,6 +1219,7 @@ def render_multi(scenes: list, *, hdr64=True, tonemap: int = TONEMAP_NONE, stats
         out["ldr"] = ldr
     if stats:
         out["trace_rays"], out["shadow_rays"] = st.trace_rays, st.shadow_rays
+        out["launches"] = st.launches
     return out
 
 

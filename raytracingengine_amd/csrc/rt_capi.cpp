@@ -44,19 +44,6 @@ rt_status hip_fail(hipError_t e, const char* what) {
 
 namespace rtamd {
 
-// Rows a render call produces: [row_begin, row_end), or with row_cycle > 1 the row_block-row
-// blocks starting at row_begin + k*row_cycle*row_block inside it (rt_render_opts).
-uint32_t rendered_rows(const rt_render_opts& o, uint32_t height) {
-    const uint32_t r1 = o.row_end ? std::min(o.row_end, height) : height;
-    if (r1 <= o.row_begin) return 0;
-    if (o.row_cycle <= 1 || o.row_block == 0) return r1 - o.row_begin;
-    const uint64_t stride = static_cast<uint64_t>(o.row_block) * o.row_cycle;
-    uint64_t rows = 0;
-    for (uint64_t b = o.row_begin; b < r1; b += stride)
-        rows += std::min<uint64_t>(o.row_block, r1 - b);
-    return static_cast<uint32_t>(rows);
-}
-
 void pack_material(const rt_material& m, double* o) {
     o[0] = m.color[0];
     o[1] = m.color[1];
@@ -100,6 +87,62 @@ rt_status harvest_events(rt_context* ctx, bool all) {
     return RT_OK;
 }
 
+rt_status timing_begin(rt_context* ctx, int flags, EventPair& ev) {
+    if (!(flags & RT_FLAG_TIME_KERNEL)) return RT_OK;
+    if (ctx->pending.size() >= 1024) RT_TRY(harvest_events(ctx, false));
+    if (!ctx->free_events.empty()) {
+        ev = ctx->free_events.back();
+        ctx->free_events.pop_back();
+    } else {
+        RT_HIP(hipEventCreate(&ev.first));
+        RT_HIP(hipEventCreate(&ev.second));
+    }
+    RT_HIP(hipEventRecord(ev.first, ctx->stream));
+    return RT_OK;
+}
+
+rt_status timing_end(rt_context* ctx, int flags, const EventPair& ev) {
+    if (!(flags & RT_FLAG_TIME_KERNEL)) return RT_OK;
+    RT_HIP(hipEventRecord(ev.second, ctx->stream));
+    ctx->pending.push_back(ev);
+    return RT_OK;
+}
+
+rt_status counters_zero(rt_context* ctx) {
+    RT_HIP(hipMemsetAsync(ctx->counters.ptr, 0, 2 * sizeof(unsigned long long), ctx->stream));
+    return RT_OK;
+}
+
+rt_status counters_read(rt_context* ctx, unsigned long long c[2], bool on_stream) {
+    const size_t bytes = 2 * sizeof(unsigned long long);
+    if (on_stream)
+        RT_HIP(hipMemcpyAsync(c, ctx->counters.ptr, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    else
+        RT_HIP(hipMemcpy(c, ctx->counters.ptr, bytes, hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+rt_status check_row_set(const rt_render_opts& o, uint32_t height, const std::string& suffix) {
+    const uint32_t r1 = o.row_end ? o.row_end : height;
+    if (r1 > height || o.row_begin >= r1)
+        return fail(RT_ERR_INVALID_ARG, "row range [" + std::to_string(o.row_begin) + "," +
+                                            std::to_string(r1) + ") invalid for height " +
+                                            std::to_string(height) + suffix);
+    if (o.row_cycle > 1 && o.row_block == 0)
+        return fail(RT_ERR_INVALID_ARG, suffix.empty() ? "row_cycle > 1 needs row_block >= 1"
+                                                       : "row_cycle > 1 without row_block >= 1" + suffix);
+    return RT_OK;
+}
+
+void set_row_set(const rt_render_opts& o, uint32_t height, TraceParams& p) {
+    p.row0 = o.row_begin;
+    if (o.row_cycle > 1) {
+        p.row_block = o.row_block;
+        p.row_stride = static_cast<uint32_t>(o.row_block) * o.row_cycle;
+    }
+    p.rows = rendered_rows(o, height);
+}
+
 rt_status validate_camera(const rt_camera* cam) {
     if (!cam) return fail(RT_ERR_INVALID_ARG, "camera is NULL");
     if (cam->width == 0 || cam->height == 0)
@@ -116,22 +159,11 @@ rt_status build_params(rt_context* ctx, const rt_scene* sc, const rt_camera* cam
     if (!ctx) return fail(RT_ERR_INVALID_ARG, "context is NULL");
     if (!sc) return fail(RT_ERR_INVALID_ARG, "scene is NULL");
     if (sc->ctx != ctx) return fail(RT_ERR_INVALID_ARG, "scene belongs to another context");
-    rt_status st = validate_camera(cam);
-    if (st != RT_OK) return st;
-    rt_render_opts opts;
-    if (opts_in) opts = *opts_in;
-    else rt_render_opts_default(&opts);
-    const uint32_t r0 = opts.row_begin;
-    const uint32_t r1 = opts.row_end ? opts.row_end : cam->height;
-    if (r1 > cam->height || r0 >= r1)
-        return fail(RT_ERR_INVALID_ARG, "row range [" + std::to_string(r0) + "," +
-                                            std::to_string(r1) + ") invalid for height " +
-                                            std::to_string(cam->height));
-    if (opts.row_cycle > 1 && opts.row_block == 0)
-        return fail(RT_ERR_INVALID_ARG, "row_cycle > 1 needs row_block >= 1");
+    RT_TRY(validate_camera(cam));
+    const rt_render_opts opts = resolved(opts_in);
+    RT_TRY(check_row_set(opts, cam->height, ""));
     if (opts.tonemap < RT_TONEMAP_NONE || opts.tonemap >= RT_TONEMAP_COUNT)
         return fail(RT_ERR_INVALID_ARG, "tonemap operator out of range");
-    rows = rendered_rows(opts, cam->height);
 
     const double* base = static_cast<const double*>(sc->buf.ptr);
     std::memset(&p, 0, sizeof p);
@@ -159,10 +191,8 @@ rt_status build_params(rt_context* ctx, const rt_scene* sc, const rt_camera* cam
     p.nt = sc->nt;
     p.nl = sc->nl;
     if (sc->has_area && sc->area.samples > 0) {
-        const rt_area_light& a = sc->area;
+        const rt_area_light& a = sc->area;  // samples = k * k (rt_scene_set_area_light)
         const int k = static_cast<int>(std::lround(std::sqrt(static_cast<double>(a.samples))));
-        if (k * k != a.samples)
-            return fail(RT_ERR_INVALID_ARG, "area light samples must be a perfect square");
         const double li = a.intensity / static_cast<double>(a.samples);
         for (int i = 0; i < 3; ++i) {
             p.al_corner[i] = a.corner[i];
@@ -186,12 +216,8 @@ rt_status build_params(rt_context* ctx, const rt_scene* sc, const rt_camera* cam
     p.max_rec = opts.max_recursion;
     p.bias = opts.bias;
     p.seed = opts.seed;
-    p.row0 = r0;
-    if (opts.row_cycle > 1) {
-        p.row_block = opts.row_block;
-        p.row_stride = static_cast<uint32_t>(opts.row_block) * opts.row_cycle;
-    }
-    p.rows = rows;
+    set_row_set(opts, cam->height, p);
+    rows = p.rows;
     p.tonemap = opts.tonemap;
 
     // Which TraceRay shape can this scene produce?  (Scene.h:175-195)
@@ -206,15 +232,6 @@ rt_status build_params(rt_context* ctx, const rt_scene* sc, const rt_camera* cam
                                   static_cast<size_t>(kLtStride) * sc->nl);
     lds = lds_bytes <= ctx->lds_limit;
     return RT_OK;
-}
-
-// Whether a render of this TraceRay shape takes the breadth-first path, whose arena (ctx->wf,
-// ctx->wf_ctl) is one per context: refraction trees, and reflection chains when
-// RTAMD_WF_CHAIN=1 forces them there.
-bool uses_wavefront_arena(int path, int flags) {
-    if (flags & RT_FLAG_GENERIC_KERNEL) return false;
-    const char* wf_chain = std::getenv("RTAMD_WF_CHAIN");
-    return path == kPathTree || (path == kPathChain && wf_chain && std::atoi(wf_chain) == 1);
 }
 
 rt_status scratch_wait(rt_context* ctx) {
@@ -257,8 +274,7 @@ rt_status fixup_buffers(rt_context* ctx, size_t px, TraceParams& p) {
 rt_status check_batch(const rt_camera* cams, int nframes) {
     if (!cams || nframes < 1) return fail(RT_ERR_INVALID_ARG, "frame batch: no cameras");
     for (int f = 0; f < nframes; ++f) {
-        rt_status st = validate_camera(cams + f);
-        if (st != RT_OK) return st;
+        RT_TRY(validate_camera(cams + f));
         if (cams[f].width != cams[0].width || cams[f].height != cams[0].height ||
             cams[f].aa_samples != cams[0].aa_samples ||
             std::memcmp(&cams[f].focal, &cams[0].focal, sizeof(double)) != 0)
@@ -294,6 +310,104 @@ static void count_packet_frames(rt_context* ctx, const TraceParams& p, int nfram
     count(rt_context::kCntTileShadowed, split.tiles && split.sh_n, static_cast<uint64_t>(nframes));
 }
 
+// Which kernel serves a frame (or frame batch) of a scene, decided once per enqueue_frames call,
+// and what its launch needs beside the TraceParams.
+struct FrameRoute {
+    // kPacket: scenes without secondary rays whose LDS image fits (rt_packet.hip).  kBox:
+    // reflection chains of scenes made of planes and up to kBoxMaxSpheres spheres, the
+    // scalar-cache chain kernel (rt_box.hip).  kLeanGeneric: the generic kernels without triangle
+    // / area-light code, for scenes that use neither.  kGeneric: everything else.
+    enum Kernel { kPacket, kBox, kLeanGeneric, kGeneric } kernel;
+    bool sample_parallel;
+    // the breadth-first TraceRay serves the image launch when its roots fit the arena
+    // (enqueue_wavefront): refraction trees, and reflection chains under RTAMD_WF_CHAIN=1
+    bool arena;
+    // kPacket: the fix-up variant (undecided shadow rays re-rendered per pixel after the launch).
+    // Known once the frames' images are placed: packet_uses_fixup reads p.tile_cost / p.nframes.
+    bool fixup = false;
+    int path;
+    bool lds;
+    size_t lds_bytes;
+    bool any_specular;
+};
+
+static FrameRoute choose_route(const TraceParams& p, int path, int flags, const rt_scene* sc,
+                               const rt_context* ctx, bool lds, size_t lds_bytes) {
+    FrameRoute r;
+    r.path = path;
+    r.lds = lds;
+    r.lds_bytes = lds_bytes;
+    r.any_specular = sc->max_specular > 0.0;
+    r.sample_parallel = !(flags & RT_FLAG_NO_SAMPLE_PARALLEL);
+    const bool specialised = !(flags & RT_FLAG_GENERIC_KERNEL);
+    const char* wf_chain = std::getenv("RTAMD_WF_CHAIN");
+    r.arena = specialised && (path == kPathTree ||
+                              (path == kPathChain && wf_chain && std::atoi(wf_chain) == 1));
+    // RTAMD_BOX_SPH=0 keeps scenes with spheres on the generic chain kernel (A/B runs)
+    static const bool box_sph = [] {
+        const char* e = std::getenv("RTAMD_BOX_SPH");
+        return !(e && std::atoi(e) == 0);
+    }();
+    const bool lean = p.nt == 0 && p.al_samples == 0;
+    if (specialised && path == kPathDirect && p.ns <= packet_max_spheres() &&
+        packet_lds_bytes(p.ns, p.np, p.nl) <= ctx->lds_limit)
+        r.kernel = FrameRoute::kPacket;
+    else if (specialised && path == kPathChain && lean &&
+             (p.ns == 0 ? p.np > 0 : (box_sph && p.ns <= kBoxMaxSpheres)))
+        r.kernel = FrameRoute::kBox;
+    else
+        r.kernel = lean ? FrameRoute::kLeanGeneric : FrameRoute::kGeneric;
+    return r;
+}
+
+// The image launch (split: the packet batch's tile lists) or the counting launch of a route.
+static hipError_t launch(const FrameRoute& r, const TraceParams& q, bool count, hipStream_t stream,
+                         const PkSplit* split) {
+    switch (r.kernel) {
+    case FrameRoute::kPacket:
+        return launch_packet_direct(q, count, r.any_specular, stream, count ? nullptr : split);
+    case FrameRoute::kBox: return launch_box_chain(q, count, r.sample_parallel, stream);
+    case FrameRoute::kLeanGeneric:
+        return lean::launch_trace(q, r.path, count, r.lds, r.lds_bytes, stream, r.sample_parallel);
+    default: return launch_trace(q, r.path, count, r.lds, r.lds_bytes, stream, r.sample_parallel);
+    }
+}
+
+// Scenes with refraction trees take the breadth-first TraceRay when the roots fit the arena
+// budget (RTAMD_WF_MB, default 4096 MiB); trees that overflow it are re-rendered per pixel.
+// Reflection chains stay per pixel: measured 2-3x faster there (coherent, no stack), while
+// the glass tree renders 4.6x faster breadth-first.  RTAMD_WF_CHAIN=1 forces chains too.
+// *enqueued: whether the breadth-first launch went onto the stream (else the caller launches).
+static rt_status enqueue_wavefront(rt_context* ctx, const TraceParams& p, const FrameRoute& r,
+                                   bool* enqueued) {
+    *enqueued = false;
+    if (!r.arena) return RT_OK;
+    const size_t n0 = static_cast<size_t>(p.rows) * p.width *
+                      static_cast<size_t>(p.aa > 0 ? p.aa : 0);
+    const char* env = std::getenv("RTAMD_WF_MB");
+    const size_t budget = (env && std::atoll(env) > 0 ? static_cast<size_t>(std::atoll(env))
+                                                      : size_t(4096)) << 20;
+    // the deferred-direct queue is laid out only when that pass runs (refraction trees)
+    const bool defer = r.path == kPathTree && wf_defer_selected();
+    const size_t root_bytes = wf_arena_bytes(n0, n0, defer);
+    if (n0 >= (size_t(1) << 30) || root_bytes > budget) return RT_OK;
+    // ~100 B per non-root node (+16 B of queue when deferred)
+    size_t extra = (budget - root_bytes) / (defer ? 116 : 100);
+    extra = std::min(extra, std::max<size_t>(n0, 1) * 64);
+    extra = std::min(extra, (size_t(1) << 31) - 1 - n0);
+    const size_t cap = n0 + extra;
+    RT_HIP(ctx->wf.ensure(wf_arena_bytes(n0, cap, defer)));
+    RT_HIP(ctx->wf_ctl.ensure(sizeof(WfCtl)));
+    const WfArena A = wf_arena_layout(ctx->wf.ptr, n0, cap, static_cast<WfCtl*>(ctx->wf_ctl.ptr),
+                                      defer);
+    // (an arena route is never the packet kernel's; the box kernel's scenes are lean ones)
+    RT_HIP(r.kernel == FrameRoute::kGeneric
+               ? launch_wavefront(p, r.path, A, r.lds, r.lds_bytes, ctx->stream)
+               : lean::launch_wavefront(p, r.path, A, r.lds, r.lds_bytes, ctx->stream));
+    *enqueued = true;
+    return RT_OK;
+}
+
 rt_status enqueue_frames(rt_context* ctx, const rt_scene* sc, const rt_camera* cams, int nframes,
                          const rt_render_opts* opts, double* d64, float* d32, uint8_t* dldr,
                          uint32_t frame_rows) {
@@ -302,53 +416,34 @@ rt_status enqueue_frames(rt_context* ctx, const rt_scene* sc, const rt_camera* c
     bool lds;
     size_t lds_bytes;
     uint32_t rows;
-    rt_status st = nframes == 1 ? RT_OK : check_batch(cams, nframes);
-    if (st != RT_OK) return st;
-    st = build_params(ctx, sc, cams, opts, p, path, lds, lds_bytes, rows);
-    if (st != RT_OK) return st;
+    if (nframes != 1) RT_TRY(check_batch(cams, nframes));
+    RT_TRY(build_params(ctx, sc, cams, opts, p, path, lds, lds_bytes, rows));
     p.out64 = d64;
     p.out32 = d32;
     p.ldr = dldr;
     const int flags = opts ? opts->flags : 0;
     if (!dldr) p.tonemap = RT_TONEMAP_NONE;
     if (dldr && p.tonemap == RT_TONEMAP_NONE) p.ldr = nullptr;
-    const bool packet_path = path == kPathDirect && !(flags & RT_FLAG_GENERIC_KERNEL) &&
-                             p.ns <= packet_max_spheres() &&
-                             packet_lds_bytes(p.ns, p.np, p.nl) <= ctx->lds_limit;
+    FrameRoute route = choose_route(p, path, flags, sc, ctx, lds, lds_bytes);
+    const bool packet = route.kernel == FrameRoute::kPacket;
     if (frame_rows && frame_rows < rows)
         return fail(RT_ERR_INVALID_ARG, "frame batch: frame stride below the rendered rows");
     const size_t frame_px = static_cast<size_t>(frame_rows ? frame_rows : rows) * p.width;
-    if (nframes > 1 && (!packet_path || nframes > kPkMaxBatch)) {
+    if (nframes > 1 && (!packet || nframes > kPkMaxBatch)) {
         // one launch per frame (other kernels), or per kPkMaxBatch frames
-        const int step = packet_path ? kPkMaxBatch : 1;
+        const int step = packet ? kPkMaxBatch : 1;
         for (int f0 = 0; f0 < nframes; f0 += step) {
             const size_t off = 3 * frame_px * static_cast<size_t>(f0);
-            st = enqueue_frames(ctx, sc, cams + f0, std::min(step, nframes - f0), opts,
-                                d64 ? d64 + off : nullptr, d32 ? d32 + off : nullptr,
-                                dldr ? dldr + off : nullptr, frame_rows);
-            if (st != RT_OK) return st;
+            RT_TRY(enqueue_frames(ctx, sc, cams + f0, std::min(step, nframes - f0), opts,
+                                  d64 ? d64 + off : nullptr, d32 ? d32 + off : nullptr,
+                                  dldr ? dldr + off : nullptr, frame_rows));
         }
         return RT_OK;
     }
-    bool scratch = (flags & RT_FLAG_COUNT_RAYS) || uses_wavefront_arena(path, flags);
+    bool scratch = (flags & RT_FLAG_COUNT_RAYS) || route.arena;
 
-    std::pair<hipEvent_t, hipEvent_t> ev{nullptr, nullptr};
-    if (flags & RT_FLAG_TIME_KERNEL) {
-        if (ctx->pending.size() >= 1024) {
-            st = harvest_events(ctx, false);
-            if (st != RT_OK) return st;
-        }
-        if (!ctx->free_events.empty()) {
-            ev = ctx->free_events.back();
-            ctx->free_events.pop_back();
-        } else {
-            RT_HIP(hipEventCreate(&ev.first));
-            RT_HIP(hipEventCreate(&ev.second));
-        }
-        RT_HIP(hipEventRecord(ev.first, ctx->stream));
-    }
-    // Scenes without secondary rays take the packet-culled kernel when its LDS image fits.
-    const bool packet = packet_path;
+    EventPair ev{nullptr, nullptr};
+    RT_TRY(timing_begin(ctx, flags, ev));
     rt_scene::PkImage::TileOrder* rec = nullptr;  // set: this launch records wave durations
     int batch_ring = -1;  // the ring entry of this batch's formed images, if any
     PkSplit pk_split{0u, 0u, 0u};  // the batch's tile lists, if every frame has them
@@ -357,82 +452,27 @@ rt_status enqueue_frames(rt_context* ctx, const rt_scene* sc, const rt_camera* c
         // most one small launch (packet_batch_images)
         p.nframes = static_cast<uint32_t>(nframes);
         p.frame_px = frame_px;
-        st = packet_batch_images(ctx, sc, cams, nframes, p, flags, &rec, &batch_ring, &pk_split);
-        if (st != RT_OK) return st;
+        RT_TRY(packet_batch_images(ctx, sc, cams, nframes, p, flags, &rec, &batch_ring, &pk_split));
     } else if (packet) {
-        st = packet_image(ctx, sc, p, flags, &rec);
-        if (st != RT_OK) return st;
+        RT_TRY(packet_image(ctx, sc, p, flags, &rec));
     }
-    // the fix-up variant of the packet kernel (undecided shadow rays re-rendered per pixel after
-    // the launch) uses the context's fix-up list: ordered across streams like the counters
-    const bool fixup = packet && packet_uses_fixup(p, false, sc->max_specular > 0.0);
-    if (fixup) {
-        st = fixup_buffers(ctx, nframes > 1 ? static_cast<size_t>(nframes) * frame_px
-                                             : static_cast<size_t>(rows) * p.width, p);
-        if (st != RT_OK) return st;
+    // the fix-up variant uses the context's fix-up list: ordered across streams like the counters
+    route.fixup = packet && packet_uses_fixup(p, false, route.any_specular);
+    if (route.fixup) {
+        RT_TRY(fixup_buffers(ctx, nframes > 1 ? static_cast<size_t>(nframes) * frame_px
+                                              : static_cast<size_t>(rows) * p.width, p));
         scratch = true;
     }
-    if (scratch) {
-        st = scratch_wait(ctx);
-        if (st != RT_OK) return st;
-    }
+    if (scratch) RT_TRY(scratch_wait(ctx));
     // The fix-up variant's split launch (rt_packet.hip launch_packet_split): every frame of the
     // batch has its tile lists (packet_batch_images formed none under a tile order), and the two
     // launches go onto the render's stream one after the other
-    if (!fixup || p.tile_order) pk_split.tiles = 0;
-    if (packet) count_packet_frames(ctx, p, nframes, fixup, pk_split);
-    // generic kernels without triangle / area-light code for scenes that use neither
-    const bool lean_generic = p.nt == 0 && p.al_samples == 0;
-    // reflection chains of scenes made of planes (and up to kBoxMaxSpheres spheres) take the
-    // scalar-cache chain kernel (rt_box.hip); RTAMD_BOX_SPH=0 keeps scenes with spheres on the
-    // generic chain kernel (A/B runs)
-    static const bool box_sph = [] {
-        const char* e = std::getenv("RTAMD_BOX_SPH");
-        return !(e && std::atoi(e) == 0);
-    }();
-    const bool box = path == kPathChain && p.nt == 0 && p.al_samples == 0 &&
-                     (p.ns == 0 ? p.np > 0 : (box_sph && p.ns <= kBoxMaxSpheres)) &&
-                     !(flags & RT_FLAG_GENERIC_KERNEL);
-    const bool spar = !(flags & RT_FLAG_NO_SAMPLE_PARALLEL);
-    auto launch = [&](const TraceParams& q, bool count) {
-        if (box)
-            return launch_box_chain(q, count, !(flags & RT_FLAG_NO_SAMPLE_PARALLEL), ctx->stream);
-        return packet ? launch_packet_direct(q, count, sc->max_specular > 0.0, ctx->stream,
-                                             count ? nullptr : &pk_split)
-                      : (lean_generic ? lean::launch_trace(q, path, count, lds, lds_bytes, ctx->stream, spar)
-                                      : launch_trace(q, path, count, lds, lds_bytes, ctx->stream, spar));
-    };
-    // Scenes with refraction trees take the breadth-first TraceRay when the roots fit the arena
-    // budget (RTAMD_WF_MB, default 4096 MiB); trees that overflow it are re-rendered per pixel.
-    // Reflection chains stay per pixel: measured 2-3x faster there (coherent, no stack), while
-    // the glass tree renders 4.6x faster breadth-first.  RTAMD_WF_CHAIN=1 forces chains too.
-    bool wavefront = false;
-    if (uses_wavefront_arena(path, flags)) {
-        const size_t n0 = static_cast<size_t>(rows) * p.width *
-                          static_cast<size_t>(p.aa > 0 ? p.aa : 0);
-        const char* env = std::getenv("RTAMD_WF_MB");
-        const size_t budget = (env && std::atoll(env) > 0 ? static_cast<size_t>(std::atoll(env))
-                                                          : size_t(4096)) << 20;
-        // the deferred-direct queue is laid out only when that pass runs (refraction trees)
-        const bool defer = path == kPathTree && wf_defer_selected();
-        const size_t root_bytes = wf_arena_bytes(n0, n0, defer);
-        if (n0 < (size_t(1) << 30) && root_bytes <= budget) {
-            // ~100 B per non-root node (+16 B of queue when deferred)
-            size_t extra = (budget - root_bytes) / (defer ? 116 : 100);
-            extra = std::min(extra, std::max<size_t>(n0, 1) * 64);
-            extra = std::min(extra, (size_t(1) << 31) - 1 - n0);
-            const size_t cap = n0 + extra;
-            RT_HIP(ctx->wf.ensure(wf_arena_bytes(n0, cap, defer)));
-            RT_HIP(ctx->wf_ctl.ensure(sizeof(WfCtl)));
-            const WfArena A = wf_arena_layout(ctx->wf.ptr, n0, cap,
-                                              static_cast<WfCtl*>(ctx->wf_ctl.ptr), defer);
-            RT_HIP(lean_generic ? lean::launch_wavefront(p, path, A, lds, lds_bytes, ctx->stream)
-                                : launch_wavefront(p, path, A, lds, lds_bytes, ctx->stream));
-            wavefront = true;
-        }
-    }
-    if (!wavefront) RT_HIP(launch(p, false));
-    if (fixup) {
+    if (!route.fixup || p.tile_order) pk_split.tiles = 0;
+    if (packet) count_packet_frames(ctx, p, nframes, route.fixup, pk_split);
+    bool wavefront;
+    RT_TRY(enqueue_wavefront(ctx, p, route, &wavefront));
+    if (!wavefront) RT_HIP(launch(route, p, false, ctx->stream, &pk_split));
+    if (route.fixup) {
         const hipError_t fe = launch_packet_fixup(p, ctx->stream);
         if (fe != hipSuccess) {
             // the packet launch appended to the list and no fix-up launch zeroes the next count:
@@ -443,10 +483,7 @@ rt_status enqueue_frames(rt_context* ctx, const rt_scene* sc, const rt_camera* c
         ctx->fix_parity ^= 1;  // the next fix-variant launch appends to the count just zeroed
     }
     if (rec) RT_HIP(hipEventRecord(rec->recorded, ctx->stream));
-    if (flags & RT_FLAG_TIME_KERNEL) {
-        RT_HIP(hipEventRecord(ev.second, ctx->stream));
-        ctx->pending.push_back(ev);
-    }
+    RT_TRY(timing_end(ctx, flags, ev));
     if (flags & RT_FLAG_COUNT_RAYS) {
         // Counting variant: same trace with wave-reduced atomics, outputs discarded.
         TraceParams pc = p;
@@ -455,7 +492,7 @@ rt_status enqueue_frames(rt_context* ctx, const rt_scene* sc, const rt_camera* c
         pc.ldr = nullptr;
         pc.counters = static_cast<unsigned long long*>(ctx->counters.ptr);
         pc.tile_cost = nullptr;  // the durations are the image launch's
-        RT_HIP(launch(pc, true));
+        RT_HIP(launch(route, pc, true, ctx->stream, nullptr));
     }
     if (batch_ring >= 0) {  // the entry is free again once these launches have completed
         RT_HIP(hipEventRecord(sc->pk_batch_done[batch_ring], ctx->stream));
@@ -482,11 +519,8 @@ rt_status check_gbuffer_args(int outputs, const rt_gbuffer_out* out) {
 // the caller, which holds a DeviceGuard); at most kPkMaxBatch frames per launch.
 rt_status enqueue_gbuffer(rt_context* ctx, const rt_scene* sc, const rt_camera* cams, int nframes,
                           const rt_render_opts* opts_in, int outputs, const rt_gbuffer_out& out) {
-    rt_status st = check_batch(cams, nframes);
-    if (st != RT_OK) return st;
-    rt_render_opts opts;
-    if (opts_in) opts = *opts_in;
-    else rt_render_opts_default(&opts);
+    RT_TRY(check_batch(cams, nframes));
+    rt_render_opts opts = resolved(opts_in);
     // not read here: whatever the caller left in them must neither fail nor steer the pass
     opts.max_recursion = 1;
     opts.tonemap = RT_TONEMAP_NONE;
@@ -496,29 +530,15 @@ rt_status enqueue_gbuffer(rt_context* ctx, const rt_scene* sc, const rt_camera* 
     bool lds;
     size_t lds_bytes;
     uint32_t rows;
-    st = build_params(ctx, sc, cams, &opts, p, path, lds, lds_bytes, rows);
-    if (st != RT_OK) return st;
+    RT_TRY(build_params(ctx, sc, cams, &opts, p, path, lds, lds_bytes, rows));
     const bool packet = !(opts.flags & RT_FLAG_GENERIC_KERNEL) &&
                         gbuffer_packet_fits(p, ctx->lds_limit);
     if (packet) p.nl = 0;  // the packet image is laid out without light records
     p.frame_px = static_cast<uint64_t>(rows) * p.width;
     GbOut g;
 
-    std::pair<hipEvent_t, hipEvent_t> ev{nullptr, nullptr};
-    if (opts.flags & RT_FLAG_TIME_KERNEL) {
-        if (ctx->pending.size() >= 1024) {
-            st = harvest_events(ctx, false);
-            if (st != RT_OK) return st;
-        }
-        if (!ctx->free_events.empty()) {
-            ev = ctx->free_events.back();
-            ctx->free_events.pop_back();
-        } else {
-            RT_HIP(hipEventCreate(&ev.first));
-            RT_HIP(hipEventCreate(&ev.second));
-        }
-        RT_HIP(hipEventRecord(ev.first, ctx->stream));
-    }
+    EventPair ev{nullptr, nullptr};
+    RT_TRY(timing_begin(ctx, opts.flags, ev));
     for (int f0 = 0; f0 < nframes; f0 += kPkMaxBatch) {
         const int n = std::min(kPkMaxBatch, nframes - f0);
         p.nframes = static_cast<uint32_t>(n);
@@ -538,11 +558,7 @@ rt_status enqueue_gbuffer(rt_context* ctx, const rt_scene* sc, const rt_camera* 
         g.albedo = reinterpret_cast<float*>(at(out.albedo, RT_GB_ALBEDO, kGbBytes[4]));
         RT_HIP(launch_gbuffer(p, g, packet, 0, ctx->stream));
     }
-    if (opts.flags & RT_FLAG_TIME_KERNEL) {
-        RT_HIP(hipEventRecord(ev.second, ctx->stream));
-        ctx->pending.push_back(ev);
-    }
-    return RT_OK;
+    return timing_end(ctx, opts.flags, ev);
 }
 
 }  // namespace rtamd
@@ -870,8 +886,7 @@ rt_status rt_render_batch(rt_context* ctx, const rt_scene* sc, const rt_camera* 
                           int nframes, const rt_render_opts* opts, void* d64, void* d32,
                           void* dldr) {
     if (!ctx) return fail(RT_ERR_INVALID_ARG, "context is NULL");
-    rt_status st = check_batch(cams, nframes);
-    if (st != RT_OK) return st;
+    RT_TRY(check_batch(cams, nframes));
     DeviceGuard g(ctx->device);
     return enqueue_frames(ctx, sc, cams, nframes, opts, static_cast<double*>(d64),
                           static_cast<float*>(d32), static_cast<uint8_t*>(dldr));
@@ -880,8 +895,7 @@ rt_status rt_render_batch(rt_context* ctx, const rt_scene* sc, const rt_camera* 
 rt_status rt_gbuffer_device(rt_context* ctx, const rt_scene* sc, const rt_camera* cams,
                             int nframes, const rt_render_opts* opts, int outputs,
                             const struct rt_gbuffer* d_out) {
-    rt_status st = check_gbuffer_args(outputs, d_out);
-    if (st != RT_OK) return st;
+    RT_TRY(check_gbuffer_args(outputs, d_out));
     if (!ctx) return fail(RT_ERR_INVALID_ARG, "context is NULL");
     DeviceGuard g(ctx->device);
     return enqueue_gbuffer(ctx, sc, cams, nframes, opts, outputs, *d_out);
@@ -889,15 +903,11 @@ rt_status rt_gbuffer_device(rt_context* ctx, const rt_scene* sc, const rt_camera
 
 rt_status rt_gbuffer(rt_context* ctx, const rt_scene* sc, const rt_camera* cam,
                      const rt_render_opts* opts, int outputs, const struct rt_gbuffer* h_out) {
-    rt_status st = check_gbuffer_args(outputs, h_out);
-    if (st != RT_OK) return st;
+    RT_TRY(check_gbuffer_args(outputs, h_out));
     if (!ctx) return fail(RT_ERR_INVALID_ARG, "context is NULL");
-    st = validate_camera(cam);
-    if (st != RT_OK) return st;
+    RT_TRY(validate_camera(cam));
     DeviceGuard g(ctx->device);
-    rt_render_opts o;
-    if (opts) o = *opts;
-    else rt_render_opts_default(&o);
+    const rt_render_opts o = resolved(opts);
     const size_t npx = static_cast<size_t>(rendered_rows(o, cam->height)) * cam->width;
     // one staging allocation, every requested output at a 256-byte boundary
     void* const host[5] = {h_out->depth, h_out->depth_norm, h_out->normal, h_out->prim,
@@ -910,8 +920,7 @@ rt_status rt_gbuffer(rt_context* ctx, const rt_scene* sc, const rt_camera* cam,
     RT_HIP(ctx->out64.ensure(total));
     char* base = static_cast<char*>(ctx->out64.ptr);
     rt_gbuffer_out d{base + off[0], base + off[1], base + off[2], base + off[3], base + off[4]};
-    st = enqueue_gbuffer(ctx, sc, cam, 1, &o, outputs, d);
-    if (st != RT_OK) return st;
+    RT_TRY(enqueue_gbuffer(ctx, sc, cam, 1, &o, outputs, d));
     for (int k = 0; k < 5; ++k)
         if (outputs & (1 << k))
             RT_HIP(hipMemcpyAsync(host[k], base + off[k], npx * kGbBytes[k], hipMemcpyDeviceToHost,
@@ -924,42 +933,25 @@ rt_status rt_render(rt_context* ctx, const rt_scene* sc, const rt_camera* cam,
                     const rt_render_opts* opts, double* h64, float* h32, uint8_t* hldr,
                     rt_stats* stats) {
     if (!ctx) return fail(RT_ERR_INVALID_ARG, "context is NULL");
-    rt_status st = validate_camera(cam);
-    if (st != RT_OK) return st;
+    RT_TRY(validate_camera(cam));
     DeviceGuard g(ctx->device);
-    rt_render_opts o;
-    if (opts) o = *opts;
-    else rt_render_opts_default(&o);
+    rt_render_opts o = resolved(opts);
     if (stats) o.flags |= RT_FLAG_COUNT_RAYS;
-    const uint32_t rows = rendered_rows(o, cam->height);
-    const size_t npx = static_cast<size_t>(rows) * cam->width;
-    if (h64) RT_HIP(ctx->out64.ensure(npx * 3 * sizeof(double)));
-    if (h32) RT_HIP(ctx->out32.ensure(npx * 3 * sizeof(float)));
-    if (hldr) RT_HIP(ctx->ldr.ensure(npx * 3));
+    const FrameStage fs(ctx, h64, h32, hldr,
+                        static_cast<size_t>(rendered_rows(o, cam->height)) * cam->width);
+    RT_TRY(fs.grow());
     if (stats) {
-        st = scratch_wait(ctx);  // the counters: after any counting render on another stream
-        if (st != RT_OK) return st;
-        RT_HIP(hipMemsetAsync(ctx->counters.ptr, 0, 2 * sizeof(unsigned long long), ctx->stream));
+        RT_TRY(scratch_wait(ctx));  // the counters: after any counting render on another stream
+        RT_TRY(counters_zero(ctx));
     }
-    st = enqueue_render(ctx, sc, cam, &o, h64 ? static_cast<double*>(ctx->out64.ptr) : nullptr,
-                 h32 ? static_cast<float*>(ctx->out32.ptr) : nullptr,
-                 hldr ? static_cast<uint8_t*>(ctx->ldr.ptr) : nullptr);
-    if (st != RT_OK) return st;
-    if (h64)
-        RT_HIP(hipMemcpyAsync(h64, ctx->out64.ptr, npx * 3 * sizeof(double),
-                              hipMemcpyDeviceToHost, ctx->stream));
-    if (h32)
-        RT_HIP(hipMemcpyAsync(h32, ctx->out32.ptr, npx * 3 * sizeof(float),
-                              hipMemcpyDeviceToHost, ctx->stream));
-    if (hldr)
-        RT_HIP(hipMemcpyAsync(hldr, ctx->ldr.ptr, npx * 3, hipMemcpyDeviceToHost, ctx->stream));
+    RT_TRY(enqueue_render(ctx, sc, cam, &o, fs.d64(), fs.d32(), fs.dldr()));
+    RT_TRY(fs.download());
     unsigned long long c[2] = {0, 0};
     if (stats) {
         // the read-back is the counters' last use: a counting render queued on another stream
         // waits for it (scratch_event), not only for the counting launch
-        RT_HIP(hipMemcpyAsync(c, ctx->counters.ptr, sizeof c, hipMemcpyDeviceToHost, ctx->stream));
-        st = scratch_done(ctx);
-        if (st != RT_OK) return st;
+        RT_TRY(counters_read(ctx, c, true));
+        RT_TRY(scratch_done(ctx));
     }
     RT_HIP(hipStreamSynchronize(ctx->stream));
     if (stats) {
@@ -967,8 +959,7 @@ rt_status rt_render(rt_context* ctx, const rt_scene* sc, const rt_camera* cam,
         stats->trace_rays = c[0];
         stats->shadow_rays = c[1];
         if (o.flags & RT_FLAG_TIME_KERNEL) {
-            st = harvest_events(ctx, true);
-            if (st != RT_OK) return st;
+            RT_TRY(harvest_events(ctx, true));
             stats->kernel_ms = ctx->timed_ms;
             stats->launches = ctx->launches;
         }
@@ -980,10 +971,9 @@ rt_status rt_stats_read(rt_context* ctx, rt_stats* out) {
     if (!ctx || !out) return fail(RT_ERR_INVALID_ARG, "NULL argument to rt_stats_read");
     DeviceGuard g(ctx->device);
     RT_HIP(hipStreamSynchronize(ctx->stream));
-    rt_status st = harvest_events(ctx, true);
-    if (st != RT_OK) return st;
+    RT_TRY(harvest_events(ctx, true));
     unsigned long long c[2] = {0, 0};
-    RT_HIP(hipMemcpy(c, ctx->counters.ptr, sizeof c, hipMemcpyDeviceToHost));
+    RT_TRY(counters_read(ctx, c, false));
     out->trace_rays = c[0];
     out->shadow_rays = c[1];
     out->kernel_ms = ctx->timed_ms;
@@ -995,8 +985,7 @@ rt_status rt_stats_reset(rt_context* ctx) {
     if (!ctx) return fail(RT_ERR_INVALID_ARG, "context is NULL");
     DeviceGuard g(ctx->device);
     RT_HIP(hipStreamSynchronize(ctx->stream));
-    rt_status st = harvest_events(ctx, true);
-    if (st != RT_OK) return st;
+    RT_TRY(harvest_events(ctx, true));
     ctx->timed_ms = 0.0;
     ctx->launches = 0;
     RT_HIP(hipMemset(ctx->counters.ptr, 0, 2 * sizeof(unsigned long long)));

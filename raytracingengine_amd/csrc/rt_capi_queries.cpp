@@ -186,19 +186,6 @@ rt_status query_params(rt_context* ctx, const rt_scene* sc, const rt_render_opts
     return RT_OK;
 }
 
-// The row set of opts against a camera's height, as build_params checks it, for the entries
-// whose messages end in their name.
-rt_status check_row_set(const rt_render_opts& o, uint32_t height, const std::string& name) {
-    const uint32_t r1 = o.row_end ? o.row_end : height;
-    if (r1 > height || o.row_begin >= r1)
-        return fail(RT_ERR_INVALID_ARG, "row range [" + std::to_string(o.row_begin) + "," +
-                                            std::to_string(r1) + ") invalid for height " +
-                                            std::to_string(height) + " passed to " + name);
-    if (o.row_cycle > 1 && o.row_block == 0)
-        return fail(RT_ERR_INVALID_ARG, "row_cycle > 1 without row_block >= 1 passed to " + name);
-    return RT_OK;
-}
-
 void copy_row_set(const rt_render_opts& from, rt_render_opts& o) {
     o.seed = from.seed;
     o.row_begin = from.row_begin;
@@ -363,7 +350,7 @@ rt_status camera_rays_params(const rt_context* ctx, const rt_camera* cam,
     rt_render_opts o;
     rt_render_opts_default(&o);
     if (opts) copy_row_set(*opts, o);
-    RT_TRY(check_row_set(o, cam->height, name));
+    RT_TRY(check_row_set(o, cam->height, " passed to " + name));
     std::memset(&p, 0, sizeof p);
     for (int i = 0; i < 3; ++i) p.cam_pos[i] = cam->position[i];
     p.focal = cam->focal;
@@ -371,12 +358,7 @@ rt_status camera_rays_params(const rt_context* ctx, const rt_camera* cam,
     p.height = cam->height;
     p.aa = cam->aa_samples;
     p.seed = o.seed;
-    p.row0 = o.row_begin;
-    if (o.row_cycle > 1) {
-        p.row_block = o.row_block;
-        p.row_stride = static_cast<uint32_t>(o.row_block) * o.row_cycle;
-    }
-    p.rows = rendered_rows(o, cam->height);
+    set_row_set(o, cam->height, p);
     return RT_OK;
 }
 
@@ -404,7 +386,7 @@ rt_status accumulate_params(rt_context* ctx, const rt_scene* sc, const rt_camera
         o.flags = opts->flags & RT_FLAG_NO_BVH;
     }
     o.tonemap = RT_TONEMAP_NONE;
-    RT_TRY(check_row_set(o, cam->height, name));
+    RT_TRY(check_row_set(o, cam->height, " passed to " + name));
     bool lds;
     size_t lds_bytes;
     uint32_t rows;
@@ -620,9 +602,9 @@ rt_status rt_trace_rays(rt_context* ctx, const rt_scene* sc, const rt_render_opt
     if (stats) {  // the counting pass: the same trace with wave-reduced atomics
         q.p.counters = static_cast<unsigned long long*>(ctx->counters.ptr);
         RT_TRY(scratch_wait(ctx));
-        RT_HIP(hipMemsetAsync(q.p.counters, 0, sizeof c, ctx->stream));
+        RT_TRY(counters_zero(ctx));
         RT_TRY(enqueue_trace_rays(ctx, q, true, s.at(i_rays), n, s.at(i_rgb)));
-        RT_HIP(hipMemcpyAsync(c, q.p.counters, sizeof c, hipMemcpyDeviceToHost, ctx->stream));
+        RT_TRY(counters_read(ctx, c, true));
         RT_TRY(scratch_done(ctx));  // the counters' last user is this read-back
     }
     RT_TRY(s.sync());
@@ -918,22 +900,20 @@ rt_status rt_resolve(rt_context* ctx, const double* sum, size_t n, int samples, 
     if (n == 0) return RT_OK;
     DeviceGuard g(ctx->device);
     const size_t planes = tonemap == RT_TONEMAP_COUNT ? RT_TONEMAP_COUNT : 1;
-    // each output in its own buffer of the context, the bytes of every copy back
-    struct { void* host; DeviceBuffer* buf; size_t bytes; } outs[3] = {
-        {hdr64, &ctx->out64, n * 3 * sizeof(double)},
-        {hdr32, &ctx->out32, n * 3 * sizeof(float)},
-        {ldr, &ctx->tm_out, planes * n * 3}};
+    // the two HDR outputs as a frame's; the bytes (every operator's plane under RT_TONEMAP_COUNT)
+    // in rt_tonemap's buffer
+    const FrameStage fs(ctx, hdr64, hdr32, nullptr, n);
+    RT_TRY(fs.grow());
     RT_HIP(ctx->tm_in.ensure(n * 3 * sizeof(double)));
-    for (auto& o : outs)
-        if (o.host) RT_HIP(o.buf->ensure(o.bytes));
+    if (ldr) RT_HIP(ctx->tm_out.ensure(planes * n * 3));
     RT_HIP(hipMemcpyAsync(ctx->tm_in.ptr, sum, n * 3 * sizeof(double), hipMemcpyHostToDevice,
                           ctx->stream));
-    RT_TRY(enqueue_resolve(ctx, ctx->tm_in.ptr, n, samples, tonemap,
-                           hdr64 ? ctx->out64.ptr : nullptr, hdr32 ? ctx->out32.ptr : nullptr,
+    RT_TRY(enqueue_resolve(ctx, ctx->tm_in.ptr, n, samples, tonemap, fs.dev(0), fs.dev(1),
                            ldr ? ctx->tm_out.ptr : nullptr));
-    for (auto& o : outs)
-        if (o.host)
-            RT_HIP(hipMemcpyAsync(o.host, o.buf->ptr, o.bytes, hipMemcpyDeviceToHost, ctx->stream));
+    RT_TRY(fs.download());
+    if (ldr)
+        RT_HIP(hipMemcpyAsync(ldr, ctx->tm_out.ptr, planes * n * 3, hipMemcpyDeviceToHost,
+                              ctx->stream));
     RT_HIP(hipStreamSynchronize(ctx->stream));
     return RT_OK;
 }

@@ -12,6 +12,7 @@
 
 #include "rt_capi.h"
 #include "rt_internal.hpp"
+#include "rt_row_plan.hpp"
 
 namespace rtamd {
 
@@ -192,10 +193,58 @@ struct rt_scene {
 
 namespace rtamd {
 
-// Rows a render call produces: [row_begin, row_end), or with row_cycle > 1 the row_block-row
-// blocks starting at row_begin + k*row_cycle*row_block inside it (rt_render_opts).
-uint32_t rendered_rows(const rt_render_opts& o, uint32_t height);
+// The three frame outputs, in the order of every {hdr64, hdr32, ldr} pointer triple: the RT_OUT_*
+// bit, the bytes of a pixel and the context buffer a host framebuffer is staged in.
+struct FrameOutput {
+    int bit;
+    size_t px_bytes;
+    DeviceBuffer rt_context::*buf;
+};
+constexpr FrameOutput kFrameOutputs[3] = {{RT_OUT_HDR64, 3 * sizeof(double), &rt_context::out64},
+                                          {RT_OUT_HDR32, 3 * sizeof(float), &rt_context::out32},
+                                          {RT_OUT_LDR, 3, &rt_context::ldr}};
+
+// Host framebuffers of npx pixels through those buffers: grow() the requested ones (host pointer
+// not NULL), hand their device pointers to the render, download() enqueues the copies back on
+// ctx->stream.  The caller holds a DeviceGuard and synchronizes.
+struct FrameStage {
+    rt_context* ctx;
+    void* host[3];
+    size_t npx;
+    FrameStage(rt_context* c, void* h64, void* h32, void* hldr, size_t n)
+        : ctx(c), host{h64, h32, hldr}, npx(n) {}
+    rt_status grow() const {
+        for (int k = 0; k < 3; ++k)
+            if (host[k]) RT_HIP((ctx->*kFrameOutputs[k].buf).ensure(npx * kFrameOutputs[k].px_bytes));
+        return RT_OK;
+    }
+    void* dev(int k) const { return host[k] ? (ctx->*kFrameOutputs[k].buf).ptr : nullptr; }
+    double* d64() const { return static_cast<double*>(dev(0)); }
+    float* d32() const { return static_cast<float*>(dev(1)); }
+    uint8_t* dldr() const { return static_cast<uint8_t*>(dev(2)); }
+    rt_status download() const {
+        for (int k = 0; k < 3; ++k)
+            if (host[k])
+                RT_HIP(hipMemcpyAsync(host[k], dev(k), npx * kFrameOutputs[k].px_bytes,
+                                      hipMemcpyDeviceToHost, ctx->stream));
+        return RT_OK;
+    }
+};
+
+// *opts, or the defaults for NULL.
+inline rt_render_opts resolved(const rt_render_opts* opts) {
+    rt_render_opts o;
+    if (opts) o = *opts;
+    else rt_render_opts_default(&o);
+    return o;
+}
+
 rt_status validate_camera(const rt_camera* cam);
+// The row set of o against a camera's height.  suffix: empty, or " passed to NAME" for the
+// entries whose messages end in their name.
+rt_status check_row_set(const rt_render_opts& o, uint32_t height, const std::string& suffix);
+// The row set of o (checked) as the kernels read it: p.row0 / row_block / row_stride / rows.
+void set_row_set(const rt_render_opts& o, uint32_t height, TraceParams& p);
 // Enqueues one render (plus the counting pass with RT_FLAG_COUNT_RAYS) on ctx's stream into
 // device outputs in the packed row order of opts.  The caller holds a DeviceGuard.
 rt_status enqueue_render(rt_context* ctx, const rt_scene* sc, const rt_camera* cam,
@@ -227,14 +276,23 @@ rt_status packet_batch_images(rt_context* ctx, const rt_scene* sc, const rt_came
                               int nframes, TraceParams& p, int flags,
                               rt_scene::PkImage::TileOrder** rec, int* batch_ring,
                               PkSplit* split);
-// Whether a render takes the breadth-first TraceRay path, whose arena is one per context (as are
-// the ray counters): renders that use them are ordered across streams (scratch_wait/_done).
-bool uses_wavefront_arena(int path, int flags);
-// Orders work on ctx->stream after the last render that used the context's scratch (any
-// stream), and marks ctx->stream's work so far as the latest such user.
+// The breadth-first TraceRay arena, the ray counters and the fix-up list are one per context:
+// renders that use them are ordered across streams.  scratch_wait orders work on ctx->stream
+// after the last such render (any stream), scratch_done marks ctx->stream's work so far as the
+// latest such user.
 rt_status scratch_wait(rt_context* ctx);
 rt_status scratch_done(rt_context* ctx);
-// Adds the elapsed time of completed RT_FLAG_TIME_KERNEL event pairs to the context totals.
+// The two ray counters [trace, shadow]: zeroed on ctx->stream; read into c, either enqueued on
+// ctx->stream (c is valid once the stream has been synchronized) or with a blocking copy.
+rt_status counters_zero(rt_context* ctx);
+rt_status counters_read(rt_context* ctx, unsigned long long c[2], bool on_stream);
+// RT_FLAG_TIME_KERNEL (flags without it: nothing happens): timing_begin takes an event pair (a
+// recycled one, or a new one) and records its first event on ctx->stream, timing_end records the
+// second and queues the pair; harvest_events adds the elapsed time of the completed pairs (all:
+// waits for every one) to the context totals and recycles them.
+using EventPair = std::pair<hipEvent_t, hipEvent_t>;
+rt_status timing_begin(rt_context* ctx, int flags, EventPair& ev);
+rt_status timing_end(rt_context* ctx, int flags, const EventPair& ev);
 rt_status harvest_events(rt_context* ctx, bool all);
 // rt_multi.cpp: releases the communicators rt_render_multi cached in ctx.
 void release_group(rt_context* ctx);

@@ -79,11 +79,6 @@ struct rt_comm {
 
 namespace {
 
-constexpr int kOutputs[3] = {RT_OUT_HDR64, RT_OUT_HDR32, RT_OUT_LDR};
-constexpr uint32_t kDefaultBlock = 16;
-
-size_t bytes_per_px(int k) { return k == 0 ? 24 : (k == 1 ? 12 : 3); }
-
 rt_status nccl_fail(ncclResult_t r, const char* what) {
     return fail(RT_ERR_RCCL, std::string(what) + ": " + ncclGetErrorString(r));
 }
@@ -143,67 +138,12 @@ rt_status comm_wait(rt_comm* c, const char* what) {
     }
 }
 
-// This rank's share of the frame: rt_render_opts selecting the block-cyclic row set `rank` of
-// `n` (a contiguous full frame when n == 1), and the rows it produces.
-struct Plan {
-    rt_render_opts opts;  // the first slot's
-    uint32_t block = 0, rows = 0, max_rows = 0;
-    // the split's row sets ("slots"): V = root_weight + n − 1 of them, dealt block-cyclically;
-    // rank 0 owns slots [0, root_weight), rank r ≥ 1 slot root_weight + r − 1
-    int slots = 1, first_slot = 0, nslots = 1;
-    uint32_t slot_rows[64];  // rows of each of this rank's slots
-};
-
-// Slot s of a V-slot block-cyclic split of H rows in blocks of b: opts and rows.
-void slot_opts(const rt_render_opts& base, uint32_t b, int V, int s, rt_render_opts& o) {
-    o = base;
-    o.row_begin = static_cast<uint32_t>(s) * b;
-    o.row_block = static_cast<uint16_t>(b);
-    o.row_cycle = static_cast<uint16_t>(V);
-}
-
-rt_status make_plan(const rt_camera* cam, const rt_render_opts* in, int n, int rank, Plan& pl,
-                    int weight = 1) {
-    rt_render_opts o;
-    if (in) o = *in;
-    else rt_render_opts_default(&o);
-    if (o.row_begin != 0 || (o.row_end != 0 && o.row_end != cam->height) || o.row_cycle > 1)
-        return fail(RT_ERR_INVALID_ARG, "multi-GPU frames render the whole image; the row "
-                                        "split is their own (set row_block only)");
-    const uint32_t H = cam->height;
-    pl.block = n == 1 ? H : (o.row_block ? o.row_block : kDefaultBlock);
-    o.row_end = H;
-    o.row_begin = static_cast<uint32_t>(rank) * pl.block;
-    o.row_block = n == 1 ? 0 : static_cast<uint16_t>(pl.block);
-    o.row_cycle = n == 1 ? 0 : static_cast<uint16_t>(n);
-    pl.opts = o;
-    pl.rows = o.row_begin < H ? rendered_rows(o, H) : 0;
-    pl.max_rows = 0;
-    pl.slots = n;
-    pl.first_slot = rank;
-    pl.nslots = 1;
-    pl.slot_rows[0] = pl.rows;
-    if (n > 1 && weight > 1) {  // the weighted split: V slots, rank 0 owns `weight` of them
-        const int V = weight + n - 1;
-        pl.slots = V;
-        pl.first_slot = rank == 0 ? 0 : weight + rank - 1;
-        pl.nslots = rank == 0 ? weight : 1;
-        pl.rows = 0;
-        for (int j = 0; j < pl.nslots; ++j) {
-            rt_render_opts q;
-            slot_opts(o, pl.block, V, pl.first_slot + j, q);
-            pl.slot_rows[j] = q.row_begin < H ? rendered_rows(q, H) : 0;
-            pl.rows += pl.slot_rows[j];
-        }
-        slot_opts(o, pl.block, V, pl.first_slot, pl.opts);
-    }
-    for (int r = 0; r < pl.slots; ++r) {
-        rt_render_opts q;
-        slot_opts(o, pl.block, pl.slots, r, q);
-        if (n == 1) q = o;
-        if (q.row_begin < H) pl.max_rows = std::max(pl.max_rows, rendered_rows(q, H));
-    }
-    return RT_OK;
+// The plan of `rank` of n for cam's frame (rt_row_plan.hpp), o: the caller's resolved opts.
+rt_status plan_frame(const rt_camera* cam, const rt_render_opts& o, int n, int rank, int weight,
+                     Plan& pl) {
+    if (make_plan(cam->height, o, n, rank, weight, pl)) return RT_OK;
+    return fail(RT_ERR_INVALID_ARG, "multi-GPU frames render the whole image; the row "
+                                    "split is their own (set row_block only)");
 }
 
 rt_status check_outputs(int outputs) {
@@ -253,7 +193,14 @@ struct Frame {
 // cost 75 µs of stream time against 15 µs for one gather of the same bytes, measured on one
 // rank: profiles/r04_rccl_group_vs_one.txt.)
 size_t send_bytes(const Plan& pl, uint32_t width, int nframes, int k) {
-    return static_cast<size_t>(nframes) * pl.max_rows * width * bytes_per_px(k);
+    return pl.send_bytes(width, nframes, kFrameOutputs[k].px_bytes);
+}
+
+// ... and where slot s of the batch sits in rank 0's receive buffer of output k.
+char* recv_slot(const rt_comm* root, int slot, int k, const Plan& pl, uint32_t width, int nframes,
+                int s) {
+    return static_cast<char*>(root->recv[slot][k].ptr) +
+           pl.recv_offset(s, width, nframes, kFrameOutputs[k].px_bytes);
 }
 
 rt_status record(rt_comm::Ev* ev, int k, hipStream_t s) {
@@ -271,10 +218,9 @@ rt_status render_part(rt_comm* c, const rt_scene* sc, const rt_camera* cams, int
     if (sc->ctx != ctx)
         return fail(RT_ERR_INVALID_ARG, "scene does not belong to the communicator's context");
     const rt_camera* cam = cams;
-    rt_status st = make_plan(cam, opts, c->nranks, c->rank, f.pl, c->root_weight);
-    if (st != RT_OK) return st;
+    RT_TRY(plan_frame(cam, resolved(opts), c->nranks, c->rank, c->root_weight, f.pl));
     Plan& pl = f.pl;
-    const bool weighted = pl.slots > c->nranks;  // rank 0's slots land in its receive buffer
+    const bool weighted = pl.weighted();  // rank 0's slots land in its receive buffer
     f.nframes = nframes;
     // one rank: its rows are the whole frame in image order, rendered straight into the
     // caller's framebuffers (no send buffer, no gather, no assembly)
@@ -282,22 +228,19 @@ rt_status render_part(rt_comm* c, const rt_scene* sc, const rt_camera* cams, int
     f.pipelined = !f.direct && (pl.opts.flags & RT_FLAG_PIPELINE) != 0;
     f.slot = f.pipelined ? static_cast<int>(c->frame & 1) : 0;
     f.gs = f.pipelined ? c->gstream : ctx->stream;
-    const size_t npx = static_cast<size_t>(pl.max_rows) * cam->width * nframes;
     for (int k = 0; k < 3 && !f.direct; ++k) {
-        if (!(outputs & kOutputs[k])) continue;
+        if (!(outputs & kFrameOutputs[k].bit)) continue;
         if (!(weighted && c->rank == 0))
             RT_HIP(c->send[f.slot][k].ensure(send_bytes(pl, cam->width, nframes, k)));
         if (c->rank == 0)
-            RT_HIP(c->recv[f.slot][k].ensure(npx * bytes_per_px(k) * static_cast<size_t>(pl.slots)));
+            RT_HIP(c->recv[f.slot][k].ensure(
+                pl.recv_bytes(cam->width, nframes, kFrameOutputs[k].px_bytes)));
     }
     c->rows = pl.rows;
     c->max_rows = pl.max_rows;
     f.ev = nullptr;
     if (pl.opts.flags & RT_FLAG_TIME_KERNEL) {
-        if (c->pending.size() >= 256) {
-            st = harvest(c, false);
-            if (st != RT_OK) return st;
-        }
+        if (c->pending.size() >= 256) RT_TRY(harvest(c, false));
         c->pending.emplace_back();
         rt_comm::Ev& e = c->pending.back();
         if (!c->spare.empty()) {
@@ -321,40 +264,31 @@ rt_status render_part(rt_comm* c, const rt_scene* sc, const rt_camera* cams, int
     for (int s = 0; s < 2; ++s)
         if (c->slot_used[s] && (s == f.slot || !f.pipelined))
             RT_HIP(hipStreamWaitEvent(ctx->stream, c->freed[s], 0));
-    st = record(f.ev, 0, ctx->stream);
-    if (st != RT_OK) return st;
+    RT_TRY(record(f.ev, 0, ctx->stream));
     // each of this rank's slots: all frames in one launch, frames max_rows rows apart; a slot's
     // outputs follow the previous slot's (rank-local outputs), or — rank 0 of a weighted split —
     // sit at the slot's place in the receive buffer, where the assembly reads them
-    const size_t slot_px = static_cast<size_t>(nframes) * pl.max_rows * cam->width;
     for (int j = 0; j < pl.nslots; ++j) {
         if (pl.slot_rows[j] == 0) continue;
-        rt_render_opts so = pl.opts;
-        if (weighted) slot_opts(pl.opts, pl.block, pl.slots, pl.first_slot + j, so);
+        const rt_render_opts so = pl.slot(j);
         void* out[3];
         for (int k = 0; k < 3; ++k) {
-            const size_t off = j * slot_px * 3;  // elements
-            char* base;
-            if (!(outputs & kOutputs[k])) {
-                base = local && local[k] ? static_cast<char*>(local[k]) + off * (k == 0 ? 8 : k == 1 ? 4 : 1)
-                                         : nullptr;
-            } else if (f.direct) {
-                base = static_cast<char*>(dst[k]);
-            } else if (weighted && c->rank == 0) {
-                base = static_cast<char*>(c->recv[f.slot][k].ptr) +
-                       static_cast<size_t>(pl.first_slot + j) * slot_px * bytes_per_px(k);
-            } else {
-                base = static_cast<char*>(c->send[f.slot][k].ptr);
-            }
-            out[k] = base;
+            if (!(outputs & kFrameOutputs[k].bit))
+                out[k] = local && local[k] ? static_cast<char*>(local[k]) +
+                                                 j * send_bytes(pl, cam->width, nframes, k)
+                                           : nullptr;
+            else if (f.direct)
+                out[k] = dst[k];
+            else if (weighted && c->rank == 0)
+                out[k] = recv_slot(c, f.slot, k, pl, cam->width, nframes, pl.first_slot + j);
+            else
+                out[k] = c->send[f.slot][k].ptr;
         }
-        st = enqueue_frames(ctx, sc, cams, nframes, &so, static_cast<double*>(out[0]),
-                            static_cast<float*>(out[1]), static_cast<uint8_t*>(out[2]),
-                            pl.max_rows);
-        if (st != RT_OK) return st;
+        RT_TRY(enqueue_frames(ctx, sc, cams, nframes, &so, static_cast<double*>(out[0]),
+                              static_cast<float*>(out[1]), static_cast<uint8_t*>(out[2]),
+                              pl.max_rows));
     }
-    st = record(f.ev, 1, ctx->stream);
-    if (st != RT_OK) return st;
+    RT_TRY(record(f.ev, 1, ctx->stream));
     if (f.pipelined) {
         RT_HIP(hipEventRecord(c->rendered[f.slot], ctx->stream));
         RT_HIP(hipStreamWaitEvent(f.gs, c->rendered[f.slot], 0));
@@ -375,18 +309,17 @@ rt_status after_failed_frame(rt_comm* c, rt_status st) {
 // buffer's nframes·max_rows rows land in slot `rank` of rank 0's receive buffer.
 rt_status gather_part(rt_comm* c, const rt_camera* cam, int outputs, const Frame& f) {
     if (f.direct) return RT_OK;
-    if (f.pl.slots > c->nranks) {
+    if (f.pl.weighted()) {
         // weighted split: rank 0's own slots are already in place; each other rank's one slot
         // goes to its place in rank 0's receive buffer (grouped P2P, equal counts)
-        const int w = f.pl.slots - c->nranks + 1;
         for (int k = 0; k < 3; ++k) {
-            if (!(outputs & kOutputs[k])) continue;
+            if (!(outputs & kFrameOutputs[k].bit)) continue;
             const size_t count = send_bytes(f.pl, cam->width, f.nframes, k);
             if (c->rank == 0) {
-                char* recv = static_cast<char*>(c->recv[f.slot][k].ptr);
                 for (int r = 1; r < c->nranks; ++r)
-                    RT_NCCL(ncclRecv(recv + static_cast<size_t>(w + r - 1) * count, count,
-                                     ncclUint8, r, c->nccl, f.gs));
+                    RT_NCCL(ncclRecv(recv_slot(c, f.slot, k, f.pl, cam->width, f.nframes,
+                                               f.pl.slot_of(r)),
+                                     count, ncclUint8, r, c->nccl, f.gs));
             } else {
                 RT_NCCL(ncclSend(c->send[f.slot][k].ptr, count, ncclUint8, 0, c->nccl, f.gs));
             }
@@ -394,7 +327,7 @@ rt_status gather_part(rt_comm* c, const rt_camera* cam, int outputs, const Frame
         return RT_OK;
     }
     for (int k = 0; k < 3; ++k) {
-        if (!(outputs & kOutputs[k])) continue;
+        if (!(outputs & kFrameOutputs[k].bit)) continue;
         char* send = static_cast<char*>(c->send[f.slot][k].ptr);
         char* recv = c->rank == 0 ? static_cast<char*>(c->recv[f.slot][k].ptr) : send;
         RT_NCCL(ncclGather(send, recv, send_bytes(f.pl, cam->width, f.nframes, k), ncclUint8, 0,
@@ -423,19 +356,17 @@ rt_status gather_local(rt_comm* const* comms, int n, const rt_camera* cam, int o
     }
     DeviceGuard g0(root->device);
     for (int k = 0; k < 3; ++k) {
-        if (!(outputs & kOutputs[k])) continue;
+        if (!(outputs & kFrameOutputs[k].bit)) continue;
         const size_t bytes = send_bytes(f0.pl, cam->width, f0.nframes, k);
-        char* recv = static_cast<char*>(root->recv[f0.slot][k].ptr);
-        // weighted split: rank 0's slots are in place, rank i's slot is w + i − 1
-        const int w = f0.pl.slots - n + 1;
-        for (int i = (w > 1 ? 1 : 0); i < n; ++i) {  // rank i's whole batch into its slot
+        // weighted split: rank 0's slots are in place already
+        for (int i = f0.pl.weighted() ? 1 : 0; i < n; ++i) {  // rank i's whole batch into its slot
             const void* send = comms[i]->send[f[i].slot][k].ptr;
-            const size_t at = static_cast<size_t>(w > 1 ? w + i - 1 : i) * bytes;
+            char* recv = recv_slot(root, f0.slot, k, f0.pl, cam->width, f0.nframes,
+                                   f0.pl.slot_of(i));
             if (comms[i]->device == root->device)
-                RT_HIP(hipMemcpyAsync(recv + at, send, bytes, hipMemcpyDeviceToDevice, f0.gs));
+                RT_HIP(hipMemcpyAsync(recv, send, bytes, hipMemcpyDeviceToDevice, f0.gs));
             else
-                RT_HIP(hipMemcpyPeerAsync(recv + at, root->device, send, comms[i]->device, bytes,
-                                          f0.gs));
+                RT_HIP(hipMemcpyPeerAsync(recv, root->device, send, comms[i]->device, bytes, f0.gs));
         }
     }
     RT_HIP(hipEventRecord(root->xfer_done, f0.gs));
@@ -450,19 +381,17 @@ rt_status gather_local(rt_comm* const* comms, int n, const rt_camera* cam, int o
 // Phase 3 (rank 0): gathered rows into image order in the caller's device framebuffers.
 rt_status assemble_part(rt_comm* c, const rt_camera* cam, int outputs, const Frame& f,
                         void* const* dst) {
-    rt_status st = f.direct ? RT_OK : record(f.ev, 3, f.gs);
-    if (st != RT_OK) return st;
+    if (!f.direct) RT_TRY(record(f.ev, 3, f.gs));
     if (c->rank == 0 && !f.direct) {
         for (int k = 0; k < 3; ++k) {
-            if (!(outputs & kOutputs[k]) || !dst[k]) continue;
+            if (!(outputs & kFrameOutputs[k].bit) || !dst[k]) continue;
             RT_HIP(launch_assemble_rows(c->recv[f.slot][k].ptr, dst[k],
-                                        size_t(cam->width) * bytes_per_px(k), cam->height,
+                                        size_t(cam->width) * kFrameOutputs[k].px_bytes, cam->height,
                                         f.pl.block, static_cast<uint32_t>(f.pl.slots),
                                         f.pl.max_rows, static_cast<uint32_t>(f.nframes), f.gs));
         }
     }
-    st = f.direct ? RT_OK : record(f.ev, 4, f.gs);
-    if (st != RT_OK) return st;
+    if (!f.direct) RT_TRY(record(f.ev, 4, f.gs));
     if (f.pipelined) {
         RT_HIP(hipEventRecord(c->freed[f.slot], f.gs));
         c->slot_used[f.slot] = true;
@@ -487,105 +416,84 @@ rt_status init_streams(rt_comm* c) {
     return RT_OK;
 }
 
+// Rank `rank` of `nranks` on ctx's device, with its gather stream and events and no transport
+// yet; nothing is left behind on failure.
+rt_status new_comm(rt_context* ctx, int nranks, int rank, rt_comm** out) {
+    *out = nullptr;
+    rt_comm* c = new (std::nothrow) rt_comm();
+    if (!c) return fail(RT_ERR_OOM, "host allocation failed");
+    c->ctx = ctx;
+    c->device = ctx->device;
+    c->nranks = nranks;
+    c->rank = rank;
+    DeviceGuard g(c->device);
+    const rt_status st = init_streams(c);
+    if (st != RT_OK) {
+        rt_comm_destroy(c);
+        return st;
+    }
+    *out = c;
+    return RT_OK;
+}
+
 rt_status check_root_outputs(const rt_comm* c, int outputs, void* const* dst) {
     if (c->rank != 0) return RT_OK;
     for (int k = 0; k < 3; ++k)
-        if ((outputs & kOutputs[k]) && !dst[k])
+        if ((outputs & kFrameOutputs[k].bit) && !dst[k])
             return fail(RT_ERR_INVALID_ARG, "rank 0 needs a device framebuffer for every "
                                             "requested output");
     return RT_OK;
 }
 
-// RTAMD_MULTI_HOST=1: the same block-cyclic split, each context's rows copied straight into the
-// caller's host rows (every device's copies are enqueued before the first synchronisation, so
-// the devices' transfers overlap).
+// RTAMD_MULTI_HOST=1, or a frame without any framebuffer (its ray counts only): the same
+// block-cyclic split (make_plan, weight 1), each context's rows copied straight into the caller's
+// host rows (every device's copies are enqueued before the first synchronisation, so the devices'
+// transfers overlap).
 rt_status render_multi_host(rt_context* const* ctxs, rt_scene* const* scenes, int n,
                             const rt_camera* cam, const rt_render_opts* opts, double* h64,
                             float* h32, uint8_t* hldr, rt_stats* stats) {
     // (arguments validated by rt_render_multi)
-    rt_status st = RT_OK;
-    rt_render_opts base;
-    if (opts) base = *opts;
-    else rt_render_opts_default(&base);
-    if (base.row_begin != 0 || (base.row_end != 0 && base.row_end != cam->height) ||
-        base.row_cycle > 1)
-        return fail(RT_ERR_INVALID_ARG, "rt_render_multi renders the whole image; the row "
-                                        "split is its own (row_block only)");
+    rt_render_opts base = resolved(opts);
     if (stats) base.flags |= RT_FLAG_COUNT_RAYS;
-    const uint32_t H = cam->height, W = cam->width;
-    const uint32_t block = n == 1 ? 0 : (base.row_block ? base.row_block : 16);
-    std::vector<rt_render_opts> o(static_cast<size_t>(n), base);
-    std::vector<uint32_t> rows(static_cast<size_t>(n));
-    // 1. every context renders its rows (block-cyclic) into its own device buffers, async
-    for (int i = 0; i < n; ++i) {
-        rt_context* ctx = ctxs[i];
-        DeviceGuard g(ctx->device);
-        o[i].row_end = H;
-        if (block) {
-            o[i].row_begin = static_cast<uint32_t>(i) * block;
-            o[i].row_block = static_cast<uint16_t>(block);
-            o[i].row_cycle = static_cast<uint16_t>(n);
-            if (o[i].row_begin >= H) {
-                rows[i] = 0;
-                continue;
+    std::vector<Plan> pl(static_cast<size_t>(n));
+    for (int i = 0; i < n; ++i) RT_TRY(plan_frame(cam, base, n, i, 1, pl[i]));
+    auto stage = [&](int i) {  // context i's rows through its own device buffers
+        return FrameStage(ctxs[i], h64, h32, hldr, static_cast<size_t>(pl[i].rows) * cam->width);
+    };
+    for (int i = 0; i < n; ++i) {  // 1. every context with rows renders them, async
+        if (pl[i].rows == 0) continue;
+        DeviceGuard g(ctxs[i]->device);
+        const FrameStage fs = stage(i);
+        RT_TRY(fs.grow());
+        if (stats) RT_TRY(counters_zero(ctxs[i]));
+        RT_TRY(enqueue_render(ctxs[i], scenes[i], cam, &pl[i].opts, fs.d64(), fs.d32(), fs.dldr()));
+    }
+    for (int i = 0; i < n; ++i) {  // 2. its packed rows, block by block, to their image rows
+        if (pl[i].rows == 0) continue;
+        DeviceGuard g(ctxs[i]->device);
+        const FrameStage fs = stage(i);
+        for (RowBlocks b(pl[i].opts, cam->height); !b.done(); b.next())
+            for (int k = 0; k < 3; ++k) {
+                const size_t row = cam->width * kFrameOutputs[k].px_bytes;
+                if (!fs.host[k]) continue;
+                RT_HIP(hipMemcpyAsync(static_cast<char*>(fs.host[k]) + b.y * row,
+                                      static_cast<char*>(fs.dev(k)) + b.packed * row,
+                                      b.rows() * row, hipMemcpyDeviceToHost, ctxs[i]->stream));
             }
-        }
-        rows[i] = rendered_rows(o[i], H);
-        const size_t npx = static_cast<size_t>(rows[i]) * W;
-        if (h64) RT_HIP(ctx->out64.ensure(npx * 3 * sizeof(double)));
-        if (h32) RT_HIP(ctx->out32.ensure(npx * 3 * sizeof(float)));
-        if (hldr) RT_HIP(ctx->ldr.ensure(npx * 3));
-        if (stats)
-            RT_HIP(hipMemsetAsync(ctx->counters.ptr, 0, 2 * sizeof(unsigned long long),
-                                  ctx->stream));
-        st = enqueue_render(ctx, scenes[i], cam, &o[i],
-                     h64 ? static_cast<double*>(ctx->out64.ptr) : nullptr,
-                     h32 ? static_cast<float*>(ctx->out32.ptr) : nullptr,
-                     hldr ? static_cast<uint8_t*>(ctx->ldr.ptr) : nullptr);
-        if (st != RT_OK) return st;
     }
-    // 2. gather: each context's packed rows back to their image rows in the caller's buffers
     if (stats) std::memset(stats, 0, sizeof *stats);
-    for (int i = 0; i < n; ++i) {
-        if (rows[i] == 0) continue;
-        rt_context* ctx = ctxs[i];
-        DeviceGuard g(ctx->device);
-        const size_t row64 = size_t(W) * 3 * sizeof(double), row32 = size_t(W) * 3 * sizeof(float),
-                     row8 = size_t(W) * 3;
-        uint32_t k = 0;  // packed row of this context
-        for (uint32_t b0 = o[i].row_begin; b0 < H; b0 += block ? block * n : H) {
-            const uint32_t nb = block ? std::min(block, H - b0) : rows[i];
-            if (h64)
-                RT_HIP(hipMemcpyAsync(reinterpret_cast<char*>(h64) + b0 * row64,
-                                      static_cast<char*>(ctx->out64.ptr) + k * row64, nb * row64,
-                                      hipMemcpyDeviceToHost, ctx->stream));
-            if (h32)
-                RT_HIP(hipMemcpyAsync(reinterpret_cast<char*>(h32) + b0 * row32,
-                                      static_cast<char*>(ctx->out32.ptr) + k * row32, nb * row32,
-                                      hipMemcpyDeviceToHost, ctx->stream));
-            if (hldr)
-                RT_HIP(hipMemcpyAsync(hldr + b0 * row8, static_cast<char*>(ctx->ldr.ptr) + k * row8,
-                                      nb * row8, hipMemcpyDeviceToHost, ctx->stream));
-            k += nb;
-        }
-    }
-    for (int i = 0; i < n; ++i) {
+    for (int i = 0; i < n; ++i) {  // 3. wait; the counts and times of the contexts that rendered
         rt_context* ctx = ctxs[i];
         DeviceGuard g(ctx->device);
         RT_HIP(hipStreamSynchronize(ctx->stream));
-        if (o[i].flags & RT_FLAG_TIME_KERNEL) {
-            st = harvest_events(ctx, true);
-            if (st != RT_OK) return st;
-        }
-        if (rows[i] == 0 || !stats) continue;
-        {
-            unsigned long long c[2] = {0, 0};
-            RT_HIP(hipMemcpy(c, ctx->counters.ptr, sizeof c, hipMemcpyDeviceToHost));
-            stats->trace_rays += c[0];
-            stats->shadow_rays += c[1];
-            stats->kernel_ms += ctx->timed_ms;
-            stats->launches += ctx->launches;
-        }
+        if (base.flags & RT_FLAG_TIME_KERNEL) RT_TRY(harvest_events(ctx, true));
+        if (pl[i].rows == 0 || !stats) continue;
+        unsigned long long c[2] = {0, 0};
+        RT_TRY(counters_read(ctx, c, false));
+        stats->trace_rays += c[0];
+        stats->shadow_rays += c[1];
+        stats->kernel_ms += ctx->timed_ms;
+        stats->launches += ctx->launches;
     }
     return RT_OK;
 }
@@ -607,18 +515,15 @@ rt_status render_multi_group(rt_context* const* ctxs, rt_scene* const* scenes, i
     if (!same) {
         release_group(root);
         std::vector<rt_comm*> comms(static_cast<size_t>(n), nullptr);
-        rt_status st = local ? rt_comm_create_local(ctxs, n, comms.data())
-                             : rt_comm_create_all(ctxs, n, comms.data());
-        if (st != RT_OK) return st;
+        RT_TRY(local ? rt_comm_create_local(ctxs, n, comms.data())
+                     : rt_comm_create_all(ctxs, n, comms.data()));
         root->group_ctxs.assign(ctxs, ctxs + n);
         root->group_comms = comms;
         // every member knows the group it is in, so destroying any of them first releases it
         for (int i = 1; i < n; ++i) ctxs[i]->group_roots.push_back(root);
     }
     for (int i = 0; i < n; ++i) root->group_comms[i]->ctx = ctxs[i];
-    rt_render_opts o;
-    if (opts) o = *opts;
-    else rt_render_opts_default(&o);
+    rt_render_opts o = resolved(opts);
     if (stats) o.flags |= RT_FLAG_COUNT_RAYS;
     // the device-to-host copies below run on root->stream: a pipelined frame would gather and
     // assemble on the communicators' own streams, unordered with them (one-shot host frames
@@ -627,32 +532,18 @@ rt_status render_multi_group(rt_context* const* ctxs, rt_scene* const* scenes, i
     if (stats)
         for (int i = 0; i < n; ++i) {
             DeviceGuard g(ctxs[i]->device);
-            RT_HIP(hipMemsetAsync(ctxs[i]->counters.ptr, 0, 2 * sizeof(unsigned long long),
-                                  ctxs[i]->stream));
+            RT_TRY(counters_zero(ctxs[i]));
         }
-    const size_t npx = static_cast<size_t>(cam->width) * cam->height;
+    const FrameStage fs(root, h64, h32, hldr, static_cast<size_t>(cam->width) * cam->height);
     {
         DeviceGuard g(root->device);
-        if (h64) RT_HIP(root->out64.ensure(npx * 3 * sizeof(double)));
-        if (h32) RT_HIP(root->out32.ensure(npx * 3 * sizeof(float)));
-        if (hldr) RT_HIP(root->ldr.ensure(npx * 3));
+        RT_TRY(fs.grow());
     }
-    rt_status st = rt_render_gather_all(root->group_comms.data(), scenes, n, cam, &o, outputs,
-                                        h64 ? root->out64.ptr : nullptr,
-                                        h32 ? root->out32.ptr : nullptr,
-                                        hldr ? root->ldr.ptr : nullptr);
-    if (st != RT_OK) return st;
+    RT_TRY(rt_render_gather_all(root->group_comms.data(), scenes, n, cam, &o, outputs, fs.dev(0),
+                                fs.dev(1), fs.dev(2)));
     {
         DeviceGuard g(root->device);
-        if (h64)
-            RT_HIP(hipMemcpyAsync(h64, root->out64.ptr, npx * 3 * sizeof(double),
-                                  hipMemcpyDeviceToHost, root->stream));
-        if (h32)
-            RT_HIP(hipMemcpyAsync(h32, root->out32.ptr, npx * 3 * sizeof(float),
-                                  hipMemcpyDeviceToHost, root->stream));
-        if (hldr)
-            RT_HIP(hipMemcpyAsync(hldr, root->ldr.ptr, npx * 3, hipMemcpyDeviceToHost,
-                                  root->stream));
+        RT_TRY(fs.download());
     }
     if (stats) std::memset(stats, 0, sizeof *stats);
     for (int i = 0; i < n; ++i) {
@@ -660,15 +551,14 @@ rt_status render_multi_group(rt_context* const* ctxs, rt_scene* const* scenes, i
         RT_HIP(hipStreamSynchronize(ctxs[i]->stream));
         if (!stats) continue;
         unsigned long long c[2] = {0, 0};
-        RT_HIP(hipMemcpy(c, ctxs[i]->counters.ptr, sizeof c, hipMemcpyDeviceToHost));
+        RT_TRY(counters_read(ctxs[i], c, false));
         stats->trace_rays += c[0];
         stats->shadow_rays += c[1];
     }
     if (stats && (o.flags & RT_FLAG_TIME_KERNEL)) {  // the frame's render time on the slowest GPU
         for (int i = 0; i < n; ++i) {
             rt_gather_timing t;
-            st = rt_comm_timing(root->group_comms[i], &t, 1);
-            if (st != RT_OK) return st;
+            RT_TRY(rt_comm_timing(root->group_comms[i], &t, 1));
             stats->kernel_ms = std::max(stats->kernel_ms, t.render_ms);
         }
         stats->launches = 1;
@@ -695,15 +585,12 @@ rt_status rt_render_multi(rt_context* const* ctxs, rt_scene* const* scenes, int 
             if (ctxs[j]->device == ctxs[i]->device) distinct = false;
         }
     }
-    rt_status st = validate_camera(cam);
-    if (st != RT_OK) return st;
+    RT_TRY(validate_camera(cam));
     const int outputs = (h64 ? RT_OUT_HDR64 : 0) | (h32 ? RT_OUT_HDR32 : 0) |
                         (hldr ? RT_OUT_LDR : 0);
-    const char* env = std::getenv("RTAMD_MULTI_HOST");  // force the host assembly (tests)
+    const char* env = std::getenv("RTAMD_MULTI_HOST");  // each context's rows to the host by itself
     if (outputs && !(env && std::atoi(env) == 1)) {
-        rt_render_opts o;
-        if (opts) o = *opts;
-        else rt_render_opts_default(&o);
+        rt_render_opts o = resolved(opts);
         if (!hldr) o.tonemap = RT_TONEMAP_NONE;
         return render_multi_group(ctxs, scenes, n, cam, &o, outputs, !distinct, h64, h32, hldr,
                                   stats);
@@ -760,18 +647,9 @@ rt_status rt_comm_create_ex(rt_context* ctx, int nranks, int rank, const uint8_t
     if (timeout_ms < 0) return fail(RT_ERR_INVALID_ARG, "timeout_ms must be >= 0");
     *out = nullptr;
     DeviceGuard g(ctx->device);
-    rt_comm* c = new (std::nothrow) rt_comm();
-    if (!c) return fail(RT_ERR_OOM, "host allocation failed");
-    c->ctx = ctx;
-    c->device = ctx->device;
-    c->nranks = nranks;
-    c->rank = rank;
+    rt_comm* c;
+    RT_TRY(new_comm(ctx, nranks, rank, &c));
     c->timeout_ms = timeout_ms;
-    rt_status st = init_streams(c);
-    if (st != RT_OK) {
-        rt_comm_destroy(c);
-        return st;
-    }
     ncclUniqueId u;
     std::memcpy(u.internal, id, sizeof u.internal);
     // Non-blocking initialisation: a rank that never joins (a dead or missing peer process)
@@ -786,7 +664,7 @@ rt_status rt_comm_create_ex(rt_context* ctx, int nranks, int rank, const uint8_t
         return nccl_fail(r, "ncclCommInitRankConfig");
     }
     c->nonblocking = true;
-    st = comm_wait(c, "ncclCommInitRankConfig");
+    const rt_status st = comm_wait(c, "ncclCommInitRankConfig");
     if (st != RT_OK) {
         const std::string msg = rt_last_error();
         rt_comm_destroy(c);
@@ -820,25 +698,13 @@ rt_status rt_comm_create_all(rt_context* const* ctxs, int n, rt_comm** out) {
         RT_NCCL(ncclCommInitAll(comms.data(), n, devs.data()));
     }
     for (int i = 0; i < n; ++i) {
-        rt_comm* c = new (std::nothrow) rt_comm();
-        if (!c) {
+        const rt_status st = new_comm(ctxs[i], n, i, &out[i]);
+        if (st != RT_OK) {  // the ranks made so far own their RCCL communicator, the rest do not
             for (int j = 0; j < i; ++j) rt_comm_destroy(out[j]);
             for (int j = i; j < n; ++j) (void)ncclCommDestroy(comms[j]);
-            return fail(RT_ERR_OOM, "host allocation failed");
-        }
-        c->ctx = ctxs[i];
-        c->device = devs[i];
-        c->nccl = comms[i];
-        c->nranks = n;
-        c->rank = i;
-        out[i] = c;
-        DeviceGuard g(devs[i]);
-        rt_status st = init_streams(c);
-        if (st != RT_OK) {
-            for (int j = 0; j <= i; ++j) rt_comm_destroy(out[j]);
-            for (int j = i + 1; j < n; ++j) (void)ncclCommDestroy(comms[j]);
             return st;
         }
+        out[i]->nccl = comms[i];
     }
     return RT_OK;
 }
@@ -853,22 +719,12 @@ rt_status rt_comm_create_local(rt_context* const* ctxs, int n, rt_comm** out) {
     }
     std::vector<rt_comm*> peers(static_cast<size_t>(n), nullptr);
     for (int i = 0; i < n; ++i) {
-        rt_comm* c = new (std::nothrow) rt_comm();
-        rt_status st = c ? RT_OK : fail(RT_ERR_OOM, "host allocation failed");
-        if (c) {
-            c->ctx = ctxs[i];
-            c->device = ctxs[i]->device;
-            c->local = true;
-            c->nranks = n;
-            c->rank = i;
-            peers[static_cast<size_t>(i)] = c;
-            DeviceGuard g(c->device);
-            st = init_streams(c);
-        }
+        const rt_status st = new_comm(ctxs[i], n, i, &peers[static_cast<size_t>(i)]);
         if (st != RT_OK) {
             for (rt_comm* p : peers) rt_comm_destroy(p);
             return st;
         }
+        peers[static_cast<size_t>(i)]->local = true;
     }
     for (int i = 0; i < n; ++i) {
         peers[static_cast<size_t>(i)]->peers = peers;
@@ -967,7 +823,7 @@ rt_status rt_render_gather_batch(rt_comm* c, const rt_scene* sc, const rt_camera
     if (st == RT_OK) st = check_root_outputs(c, outputs, dst);
     if (st != RT_OK) return st;
     for (int k = 0; k < 3; ++k)
-        if ((outputs & kOutputs[k]) && local[k])
+        if ((outputs & kFrameOutputs[k].bit) && local[k])
             return fail(RT_ERR_INVALID_ARG, "an output is either gathered or rank-local");
     if (c->local && c->nranks > 1)
         return fail(RT_ERR_INVALID_ARG, "local communicators (rt_comm_create_local) gather "

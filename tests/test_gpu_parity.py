@@ -709,16 +709,28 @@ def test_bvh_ties_go_to_lowest_index(ctx):
 
 
 # ------------------------------------------------------------------ one frame, several contexts
-@pytest.mark.parametrize("name,n,block", [("c2", 3, 16), ("glass", 2, 0), ("c3", 4, 7)])
-def test_render_multi_equals_single(name, n, block):
+_MULTI_CASES = [("c2", 3, 16), ("glass", 2, 0), ("c3", 4, 7)]
+
+
+@pytest.mark.parametrize(
+    "name,n,block,host",
+    [pytest.param(*c, False, id="-".join(map(str, c))) for c in _MULTI_CASES] +
+    [pytest.param(*c, True, id="-".join(map(str, c)) + "-host") for c in _MULTI_CASES])
+def test_render_multi_equals_single(name, n, block, host, monkeypatch):
     """rt_render_multi (Scene::SetDevices): n contexts — here all on GPU 0 — render their
-    block-cyclic rows concurrently and the host assembles one frame equal to the single-context
-    render, ray counts summed."""
+    block-cyclic rows concurrently into one frame equal to the single-context render, ray counts
+    summed: gathered on the first context's device, or with RTAMD_MULTI_HOST=1 (host; read per
+    call) each context's rows copied to their host rows.  Which path ran shows in the launches of
+    the timed frame on fresh contexts: one per context with rows (every one has some here: 136
+    rows, at most 4 x 16) on the host path, 1 on the gathered one."""
+    if host:
+        monkeypatch.setenv("RTAMD_MULTI_HOST", "1")
     sc = make_config(name, 240, 136)
     ctxs = [capi.Context(0) for _ in range(n)]
     try:
         scenes = [c.scene(sc) for c in ctxs]
-        multi = capi.render_multi(scenes, hdr64=True, tonemap=1, stats=True, row_block=block)
+        multi = capi.render_multi(scenes, hdr64=True, tonemap=1, stats=True, row_block=block,
+                                  flags=capi.RT_FLAG_TIME_KERNEL)
         single = scenes[0].render(hdr64=True, tonemap=1, stats=True)
         for ds in scenes:
             ds.close()
@@ -729,6 +741,27 @@ def test_render_multi_equals_single(name, n, block):
     assert np.array_equal(multi["ldr"], single["ldr"])
     assert (multi["trace_rays"], multi["shadow_rays"]) == (single["trace_rays"],
                                                             single["shadow_rays"])
+    assert multi["launches"] == (n if host else 1)
+
+
+def test_render_multi_stats_only():
+    """rt_render_multi without any framebuffer: every context still renders its rows (into no
+    output) for the ray counts, which sum to the single-context render's."""
+    sc = make_config("c2", 240, 136)
+    ctxs = [capi.Context(0) for _ in range(3)]
+    try:
+        scenes = [c.scene(sc) for c in ctxs]
+        multi = capi.render_multi(scenes, hdr64=False, stats=True)
+        single = scenes[0].render(hdr64=True, stats=True)
+        for ds in scenes:
+            ds.close()
+    finally:
+        for c in ctxs:
+            c.close()
+    assert "hdr64" not in multi and "ldr" not in multi
+    assert (multi["trace_rays"], multi["shadow_rays"]) == (single["trace_rays"],
+                                                            single["shadow_rays"])
+    assert multi["trace_rays"] > 0
 
 
 # ------------------------------------------------------------------ planes: edge rays
