@@ -37,6 +37,10 @@
  *                                  (Scene.h:289-297, for a range of its AA samples, into a resident sum)
  *   rt_resolve[_device]            GeneratePixelAt's division by the sample count   Scene.h:298-300,
  *                                  then tonemap()/toColor() as rt_tonemap
+ *   rt_accumulate_adaptive[_device] that loop left per pixel where a stop rule on the pixel's samples
+ *                                  says so (no counterpart: the reference takes every sample)
+ *   rt_resolve_counts[_device]     the division by each pixel's own count, zero samples included
+ *                                  Scene.h:298-303
  *   rt_tonemap                     tonemap() RaytracingEngine.cpp:165-174 and the operators of
  *                                  tonemapAll() RaytracingEngine.cpp:176-214, each followed by
  *                                  toColor() RaytracingEngine.cpp:113-121
@@ -868,6 +872,74 @@ rt_status rt_resolve_device(rt_context* ctx, const void* d_sum, size_t n_pixels,
 rt_status rt_resolve(rt_context* ctx, const double* sum, size_t n_pixels, int samples, int tonemap,
                      double* hdr64, float* hdr32, uint8_t* ldr);
 
+/* Adaptive progressive frames: the sum of rt_accumulate_samples continued per pixel only while a
+ * stop rule on the pixel's own samples asks for more.  State per pixel of the row set of opts,
+ * rows-local like d_sum above: d_sum 3 doubles, d_moments 2 doubles {m1, m2}, d_count one int32.
+ * fresh != 0: none of the three is read (no memset is needed) and n, sum, m1, m2 start at
+ * 0 / +0.0.  For every pixel px:
+ *
+ *   n = count[px]
+ *   while n < sample_end:
+ *       if n >= min_samples and converged(n, m1, m2): break
+ *       c   = TraceRay(camera ray of sample n at px, 0, bias)   -- exactly rt_accumulate_samples' ray, key and TraceRay
+ *       sum = sum + c                                           -- GeneratePixelAt's fold, Scene.h:289-297
+ *       L   = (c.x*0.2126 + c.y*0.7152) + c.z*0.0722            -- luminance, Vec3::dot order
+ *       m1  = m1 + L;  m2 = m2 + L*L;  n = n + 1
+ *   count[px] = n
+ *
+ *   converged(n, m1, m2):            -- IEEE binary64, one rounding per operation, no FMA, no sqrt, no libm
+ *       nd = (double)n;  mean = m1 / nd
+ *       var  = (m2 - m1*mean) / (nd - 1.0)
+ *       err2 = var / nd                                   -- squared standard error of the mean luminance
+ *       ref  = mean > lum_floor ? mean : lum_floor
+ *       lim  = tolerance * ref
+ *       return err2 <= lim*lim                            -- false for NaN: such a pixel runs to sample_end
+ *
+ * The rule is re-examined before every sample, so count[px] is a function of the pixel's sample
+ * sequence alone: it does not depend on how calls cut the range (sample_end = 3, then 5, then 8
+ * on one state is sample_end = 8, in all three arrays, bit for bit; a pixel the rule stopped
+ * stays stopped), on the launch shape, or on which kernel traced the pixel.  sum[px] is
+ * rt_accumulate_samples(0, count[px])[px] bit for bit; with min_samples >= sample_end the rule
+ * never fires, sum is rt_accumulate_samples(0, sample_end) and every count is sample_end.  A
+ * pixel that takes no sample in a call that is not fresh is not written.
+ * Kernels: one thread per pixel in 8x8 tiles while at least half of a wave's pixels want samples;
+ * the rest is appended to a device-side list in the context and finished 64 listed pixels to a
+ * wave.  RTAMD_ADAPT_LIST=0 in the environment, read per call, keeps every pixel in the tile
+ * kernel; the three arrays are the same bits.
+ * Of opts the call reads what rt_accumulate_samples_device reads, the row set included.
+ * RT_ERR_INVALID_ARG, before anything is dereferenced or a device is touched: a NULL context,
+ *   scene, camera, rule or array; zero width or height; sample_end < 1 or > max(1, aa_samples);
+ *   min_samples < 2; tolerance negative or NaN; lum_floor not > 0; a row set outside the image.
+ * RT_ERR_UNSUPPORTED: as rt_accumulate_samples_device; a row set above 2^32 pixels.
+ * Asynchronous on the context's stream; no host memory is touched. */
+typedef struct rt_adaptive_rule {
+    double tolerance;     /* relative standard error of the mean luminance to stop at, >= 0 */
+    double lum_floor;     /* the mean luminance below which the error is absolute, > 0 */
+    int32_t min_samples;  /* samples every pixel takes before the rule is examined, >= 2 */
+    int32_t _pad0;
+} rt_adaptive_rule;
+rt_status rt_accumulate_adaptive_device(rt_context* ctx, const rt_scene* scene,
+                                        const rt_camera* cam, const rt_render_opts* opts,
+                                        const rt_adaptive_rule* rule, int fresh, int sample_end,
+                                        void* d_sum, void* d_moments, void* d_count);
+/* The same on host arrays (in and out: read unless fresh), synchronous. */
+rt_status rt_accumulate_adaptive(rt_context* ctx, const rt_scene* scene, const rt_camera* cam,
+                                 const rt_render_opts* opts, const rt_adaptive_rule* rule,
+                                 int fresh, int sample_end, double* sum, double* moments,
+                                 int32_t* count);
+
+/* rt_resolve_device with each pixel's own count as the divisor: v = sum / (double)count, and
+ * {0,0,0} for a pixel whose count is 0 (GeneratePixelAt, Scene.h:298-303: its sum is not read);
+ * then what rt_resolve_device writes.  The argument checks are rt_resolve_device's, plus a NULL
+ * count with n_pixels > 0. */
+rt_status rt_resolve_counts_device(rt_context* ctx, const void* d_sum, const void* d_count,
+                                   size_t n_pixels, int tonemap, void* d_hdr64, void* d_hdr32,
+                                   void* d_ldr);
+/* The same on host pointers, synchronous. */
+rt_status rt_resolve_counts(rt_context* ctx, const double* sum, const int32_t* count,
+                            size_t n_pixels, int tonemap, double* hdr64, float* hdr32,
+                            uint8_t* ldr);
+
 /* Device tonemap of host FP64 radiance: op in [0, RT_TONEMAP_COUNT) writes n*3 bytes;
  * op == RT_TONEMAP_COUNT writes all seven operators, tonemapAll() order, 7*n*3 bytes. */
 rt_status rt_tonemap(rt_context* ctx, const double* hdr, size_t n_pixels, int op,
@@ -942,6 +1014,11 @@ rt_status rt_debug_tile_shadowed(rt_context* ctx, uint64_t* with, uint64_t* with
 /* Test hook (read-only, waits for the context's stream): the pixels the context's last launch of
  * the packet kernel's fix-up variant queued for its fix-up launch (0 before the first one). */
 rt_status rt_debug_fixup_count(rt_context* ctx, uint32_t* pixels);
+
+/* Test hook (read-only, waits for the context's stream): the pixels the context's latest adaptive
+ * call appended to its list for the list kernel (0 before the first one and with
+ * RTAMD_ADAPT_LIST=0). */
+rt_status rt_debug_adaptive_listed(rt_context* ctx, uint32_t* pixels);
 
 #ifdef __cplusplus
 } /* extern "C" */

@@ -60,6 +60,41 @@ std::vector<Vec3> resolve(const std::vector<Vec3>& sum, int samples) {
     return out;
 }
 
+namespace {
+void check_counts(const std::vector<Vec3>& sum, const std::vector<int32_t>& counts) {
+    if (counts.size() != sum.size())
+        throw std::runtime_error("resolve: one count per pixel of the sum is needed");
+}
+}  // namespace
+
+std::vector<Vec3> resolve(const std::vector<Vec3>& sum, const std::vector<int32_t>& counts) {
+    check_counts(sum, counts);
+    std::vector<Vec3> out(sum.size(), Vec3(0, 0, 0));
+    double none[3];
+    const int32_t none_i[1] = {0};
+    check(rt_resolve_counts(thread_context(current_device()),
+                            reinterpret_cast<const double*>(sum.data()),
+                            counts.empty() ? none_i : counts.data(), sum.size(), RT_TONEMAP_NONE,
+                            out.empty() ? none : reinterpret_cast<double*>(out.data()), nullptr,
+                            nullptr),
+          "rt_resolve_counts");
+    return out;
+}
+
+std::vector<Color> resolveTonemapped(const std::vector<Vec3>& sum,
+                                     const std::vector<int32_t>& counts, int op) {
+    check_counts(sum, counts);
+    std::vector<Color> out(sum.size());
+    uint8_t none[3];
+    const int32_t none_i[1] = {0};
+    check(rt_resolve_counts(thread_context(current_device()),
+                            reinterpret_cast<const double*>(sum.data()),
+                            counts.empty() ? none_i : counts.data(), sum.size(), op, nullptr,
+                            nullptr, out.empty() ? none : reinterpret_cast<uint8_t*>(out.data())),
+          "rt_resolve_counts");
+    return out;
+}
+
 std::vector<Color> resolveTonemapped(const std::vector<Vec3>& sum, int samples, int op) {
     std::vector<Color> out(sum.size());
     uint8_t none[3];

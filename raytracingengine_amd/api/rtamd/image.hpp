@@ -34,6 +34,12 @@ std::vector<Vec3> resolve(const std::vector<Vec3>& sum, int samples);
 // samples = 1 it is tonemapOp(sum, op).
 std::vector<Color> resolveTonemapped(const std::vector<Vec3>& sum, int samples,
                                      int op = 6 /* RT_TONEMAP_ACES, tonemap()'s */);
+// The same for a sum whose pixels hold different numbers of samples (Scene::AccumulateAdaptive,
+// rt_resolve_counts): sum[i] / (double)counts[i], and (0, 0, 0) where counts[i] is 0.
+std::vector<Vec3> resolve(const std::vector<Vec3>& sum, const std::vector<int32_t>& counts);
+std::vector<Color> resolveTonemapped(const std::vector<Vec3>& sum,
+                                     const std::vector<int32_t>& counts,
+                                     int op = 6 /* RT_TONEMAP_ACES */);
 }  // namespace rtamd
 
 #ifdef RTAMD_GLOBAL_TONEMAP

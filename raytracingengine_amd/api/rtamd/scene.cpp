@@ -653,6 +653,30 @@ void Scene::AccumulateSamples(int begin, int end, std::vector<Vec3>& sum) const 
                  "rt_accumulate_samples");
 }
 
+void Scene::AccumulateAdaptive(int sampleEnd, const rtamd::AdaptiveRule& rule,
+                               rtamd::AdaptiveState& state) const {
+    const size_t n = camera.width * camera.height;
+    const bool fresh = state.sum.empty() && state.moments.empty() && state.counts.empty();
+    if (fresh) {
+        state.sum.assign(n, Vec3(0, 0, 0));
+        state.moments.assign(2 * n, 0.0);
+        state.counts.assign(n, 0);
+    } else if (state.sum.size() != n || state.moments.size() != 2 * n || state.counts.size() != n) {
+        throw std::runtime_error("AccumulateAdaptive: the state is not empty and not the frame's");
+    }
+    rt_scene* sc = upload();
+    const rt_camera cam = cameraDesc();
+    const rt_render_opts o = optsDesc(RT_TONEMAP_NONE);
+    const rt_adaptive_rule r{rule.tolerance, rule.lumFloor, rule.minSamples, 0};
+    double none[3];  // with no pixel the entry still checks the camera, the rule and sampleEnd
+    int32_t none_i[1];
+    rtamd::check(rt_accumulate_adaptive(dev_->ctx, sc, &cam, &o, &r, fresh ? 1 : 0, sampleEnd,
+                                        n ? reinterpret_cast<double*>(state.sum.data()) : none,
+                                        n ? state.moments.data() : none,
+                                        n ? state.counts.data() : none_i),
+                 "rt_accumulate_adaptive");
+}
+
 rtamd::Hits Scene::IntersectClosest(const std::vector<Rayon>& rays) const {
     static_assert(sizeof(Rayon) == 6 * sizeof(double), "Rayon is not six packed doubles");
     static_assert(sizeof(rt_material) == 7 * sizeof(double), "rt_material is not seven doubles");

@@ -23,6 +23,8 @@
 //   AccumulateSamples(b, e, sum) → rt_accumulate_samples (GeneratePixelAt's sample loop,
 //                              Scene.h:289-297, for a range of its samples; rtamd::resolve in
 //                              image.hpp divides, Scene.h:298-300)
+//   AccumulateAdaptive(end, rule, state) → rt_accumulate_adaptive (that loop, left per pixel by a
+//                              stop rule; rtamd::resolve(sum, counts) divides by each count)
 // The single-ray IntersectAnyBefore(ray, maxDist) of the reference's signature stays a host
 // utility over the shapes' Intersect members: one ray per launch would pay an upload, a launch
 // and a download to learn one bit; the batch overloads give the same answers for many rays.
@@ -65,6 +67,22 @@ struct GBuffer {
     std::vector<Vec3> normal;        // HitInfo::normal (unflipped)
     std::vector<int32_t> prim;       // {type, index} pairs as rt_intersect_rays reports them
     std::vector<float> albedo;       // r g b of HitInfo::material.color
+};
+
+// Scene::AccumulateAdaptive's stop rule (rt_adaptive_rule, rt_capi.h): a pixel stops once it has
+// minSamples samples and the standard error of its mean luminance is at most tolerance times
+// max(mean, lumFloor).
+struct AdaptiveRule {
+    double tolerance = 0.05;
+    double lumFloor = 0.01;
+    int minSamples = 4;
+};
+// ... and its state, one entry per pixel (row-major): the sum of the pixel's samples so far,
+// the two luminance moments {m1, m2} the rule reads, and the number of samples taken.
+struct AdaptiveState {
+    std::vector<Vec3> sum;
+    std::vector<double> moments;
+    std::vector<int32_t> counts;
 };
 
 // Scene::ScatterRays' result: per ray one TraceRay level (Scene.h:131-198) before its children
@@ -255,6 +273,13 @@ public:
     // 0 <= begin < end <= max(1, antiAliasingAmount).  rtamd::resolve(sum, end) (image.hpp) is the
     // frame after `end` samples; with end = antiAliasingAmount it is RenderImage(), bit for bit.
     void AccumulateSamples(int begin, int end, std::vector<Vec3>& sum) const;
+    // AccumulateSamples where every pixel stops by `rule` (rt_accumulate_adaptive): each pixel
+    // continues from state.counts up to sampleEnd samples while the rule wants more.  An empty
+    // state starts the frame; a state of the frame's size is continued.  1 <= sampleEnd <=
+    // max(1, antiAliasingAmount).  rtamd::resolve(state.sum, state.counts) (image.hpp) is the
+    // frame; with rule.minSamples >= sampleEnd = antiAliasingAmount it is RenderImage().
+    void AccumulateAdaptive(int sampleEnd, const rtamd::AdaptiveRule& rule,
+                            rtamd::AdaptiveState& state) const;
     void SetDevice(int device) { device_ = device; dev_.reset(); devices_.clear(); }
     // RenderImage / RenderImageTonemapped / RenderImageF32 over several GPUs of the node from
     // this process: one scene copy per GPU, block-cyclic rows, gathered to the first GPU and

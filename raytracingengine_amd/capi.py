@@ -8,6 +8,7 @@ from __future__ import annotations
 import ctypes
 import math
 import os
+from typing import NamedTuple
 
 import numpy as np
 
@@ -112,6 +113,8 @@ EXPORTED = [
     "rt_trace_rays_device",
     "rt_accumulate_samples", "rt_accumulate_samples_device",
     "rt_resolve", "rt_resolve_device",
+    "rt_accumulate_adaptive", "rt_accumulate_adaptive_device",
+    "rt_resolve_counts", "rt_resolve_counts_device", "rt_debug_adaptive_listed",
 ]
 
 
@@ -418,6 +421,11 @@ def load_library(path: str = LIB_PATH):
         "rt_accumulate_samples_device": [vp, vp, vp, vp, i32, i32, vp],
         "rt_resolve": [vp, vp, ctypes.c_size_t, i32, i32, vp, vp, vp],
         "rt_resolve_device": [vp, vp, ctypes.c_size_t, i32, i32, vp, vp, vp],
+        "rt_accumulate_adaptive": [vp, vp, vp, vp, vp, i32, i32, vp, vp, vp],
+        "rt_accumulate_adaptive_device": [vp, vp, vp, vp, vp, i32, i32, vp, vp, vp],
+        "rt_resolve_counts": [vp, vp, vp, ctypes.c_size_t, i32, vp, vp, vp],
+        "rt_resolve_counts_device": [vp, vp, vp, ctypes.c_size_t, i32, vp, vp, vp],
+        "rt_debug_adaptive_listed": [vp, vp],
         "rt_tonemap": [vp, vp, ctypes.c_size_t, i32, vp],
         "rt_debug_f64_ops": [vp, vp, vp, ctypes.c_size_t, vp],
         "rt_debug_vec_ops": [vp, vp, ctypes.c_size_t, vp],
@@ -521,6 +529,27 @@ def _query_opts(bias=None, no_bvh: bool = False, max_recursion=None, seed=None) 
 
 def device_count() -> int:
     return load_library().rt_device_count()
+
+
+class AdaptiveRule(ctypes.Structure):
+    """rt_adaptive_rule (rt_capi.h): the stop rule of the adaptive entries."""
+    _fields_ = [("tolerance", ctypes.c_double), ("lum_floor", ctypes.c_double),
+                ("min_samples", ctypes.c_int32), ("_pad0", ctypes.c_int32)]
+
+
+# The defaults of DeviceScene.accumulate_adaptive[_device] and render_adaptive.
+ADAPTIVE_TOLERANCE = 0.05   # render_adaptive's: a row of profiles/adaptive_time.txt (README)
+ADAPTIVE_MIN_SAMPLES = 4
+ADAPTIVE_LUM_FLOOR = 0.01
+
+
+class AdaptiveState(NamedTuple):
+    """The state of an adaptive frame, one row per pixel of the row set: sum float64 [n,3],
+    moments float64 [n,2] {m1, m2}, count int32 [n] — torch tensors from the _device entry, numpy
+    arrays from the host entry."""
+    sum: object
+    moments: object
+    count: object
 
 
 def progressive_schedule(aa_samples: int) -> list:
@@ -638,6 +667,12 @@ class Context:
         """Pixels the last fix-up variant launch of this context queued for its fix-up launch."""
         n = ctypes.c_uint32()
         _check(_lib.rt_debug_fixup_count(self._h, ctypes.byref(n)))
+        return n.value
+
+    def debug_adaptive_listed(self) -> int:
+        """Pixels the latest adaptive call of this context listed for its list kernel."""
+        n = ctypes.c_uint32()
+        _check(_lib.rt_debug_adaptive_listed(self._h, ctypes.byref(n)))
         return n.value
 
     def debug_vec_ops(self, v: np.ndarray) -> np.ndarray:
@@ -1117,6 +1152,133 @@ class DeviceScene:
             acc = self.accumulate_device(done, k, sum=acc, cam=cam, **opts)
             done = k
             yield k, self.resolve_device(acc, k, tonemap=tonemap, hdr64=hdr64, hdr32=hdr32)
+
+    def accumulate_adaptive(self, sample_end: int, tolerance: float,
+                            min_samples: int = ADAPTIVE_MIN_SAMPLES,
+                            lum_floor: float = ADAPTIVE_LUM_FLOOR, state=None, cam=None,
+                            fresh=None, **opts) -> AdaptiveState:
+        """Continue every pixel of the row set of opts up to sample_end samples while the stop
+        rule wants more (rt_accumulate_adaptive; the rule is in rt_capi.h): a pixel stops once it
+        has min_samples samples and the squared standard error of its mean luminance is at most
+        (tolerance * max(mean, lum_floor))**2.  state: the AdaptiveState to continue (its
+        contiguous numpy arrays are updated in place); None starts a fresh one.  fresh=True with
+        a state starts afresh in its arrays, whose contents are then not read.  cam and opts as
+        accumulate."""
+        rec, w, h = self._camera_record(cam)
+        o = default_opts(**opts)
+        n = rendered_rows(o, h) * w
+        rule = AdaptiveRule(tolerance, lum_floor, min_samples, 0)
+        if state is None:
+            state = AdaptiveState(np.empty((n, 3), np.float64), np.empty((n, 2), np.float64),
+                                  np.empty(n, np.int32))
+            fresh = True
+        else:
+            for a, dt, k in zip(state, (np.float64, np.float64, np.int32), (3, 2, 1)):
+                if not (isinstance(a, np.ndarray) and a.dtype == dt and a.flags.c_contiguous
+                        and a.flags.writeable and a.size == k * n):
+                    raise ValueError("state: contiguous writable arrays sum float64 [n,3], "
+                                     "moments float64 [n,2], count int32 [n], n = rows*W")
+        _check(_lib.rt_accumulate_adaptive(self.ctx.handle, self._h, rec.ctypes.data,
+                                           ctypes.byref(o), ctypes.byref(rule), 1 if fresh else 0,
+                                           sample_end, *(a.ctypes.data or 8 for a in state)))
+        return state
+
+    def accumulate_adaptive_device(self, sample_end: int, tolerance: float,
+                                   min_samples: int = ADAPTIVE_MIN_SAMPLES,
+                                   lum_floor: float = ADAPTIVE_LUM_FLOOR, state=None, cam=None,
+                                   fresh=None, **opts) -> AdaptiveState:
+        """Asynchronous rt_accumulate_adaptive_device on the context's stream: accumulate_adaptive
+        on torch tensors on the context's device.  state None: a fresh state in new tensors;
+        fresh=True with a state: a fresh one in its tensors, which need no initialisation."""
+        import torch
+        rec, w, h = self._camera_record(cam)
+        o = default_opts(**opts)
+        n = rendered_rows(o, h) * w
+        rule = AdaptiveRule(tolerance, lum_floor, min_samples, 0)
+        fresh = fresh or state is None
+        dev = self._device()
+        given = (None, None, None) if state is None else state
+        state = AdaptiveState(
+            _out_tensor(given[0], dev, torch.float64, (n, 3), "state.sum", "rows*W*3"),
+            _out_tensor(given[1], dev, torch.float64, (n, 2), "state.moments", "rows*W*2"),
+            _out_tensor(given[2], dev, torch.int32, (n,), "state.count", "rows*W"))
+        _check(_lib.rt_accumulate_adaptive_device(self.ctx.handle, self._h, rec.ctypes.data,
+                                                  ctypes.byref(o), ctypes.byref(rule),
+                                                  1 if fresh else 0, sample_end,
+                                                  *(t.data_ptr() or 8 for t in state)))
+        return state
+
+    def resolve_counts(self, sum, count, tonemap: int = TONEMAP_NONE, hdr64: bool = True,
+                       hdr32: bool = False) -> dict:
+        """resolve() with each pixel's own count as the divisor (rt_resolve_counts): sum float64
+        [n,3], count int32 [n]; a pixel whose count is 0 is (0, 0, 0)."""
+        sum, n = _host_rows(sum, 3)
+        count = np.ascontiguousarray(count, np.int32).reshape(-1)
+        if count.size != n:
+            raise ValueError("count: one int32 per pixel of the sum")
+        out = {}
+        if hdr64:
+            out["hdr64"] = np.empty((n, 3), np.float64)
+        if hdr32:
+            out["hdr32"] = np.empty((n, 3), np.float32)
+        if tonemap != TONEMAP_NONE:
+            out["ldr"] = np.empty((7, n, 3) if tonemap == TONEMAP_ALL else (n, 3), np.uint8)
+        ptr = {k: (v.ctypes.data or 8) for k, v in out.items()}
+        _check(_lib.rt_resolve_counts(self.ctx.handle, sum.ctypes.data or 8, count.ctypes.data or 8,
+                                      n, tonemap, ptr.get("hdr64"), ptr.get("hdr32"),
+                                      ptr.get("ldr")))
+        return out
+
+    def resolve_counts_device(self, sum, count, tonemap: int = TONEMAP_NONE, hdr64: bool = True,
+                              hdr32: bool = False, out=None) -> dict:
+        """Asynchronous rt_resolve_counts_device on the context's stream: resolve_counts() on a
+        contiguous float64 [n,3] sum and int32 [n] count on the context's device, the outputs as
+        resolve_device's."""
+        import torch
+        dev = self._device()
+        n = _checked_input(sum, dev, torch.float64, 3, "sum")
+        if _checked_input(count, dev, torch.int32, 1, "count") != n:
+            raise ValueError("count: one int32 per pixel of the sum")
+        want = []
+        if hdr64:
+            want.append(("hdr64", torch.float64, (n, 3)))
+        if hdr32:
+            want.append(("hdr32", torch.float32, (n, 3)))
+        if tonemap != TONEMAP_NONE:
+            want.append(("ldr", torch.uint8, (7, n, 3) if tonemap == TONEMAP_ALL else (n, 3)))
+        res = {name: _out_tensor(None if out is None else out.get(name), dev, tdt, shape,
+                                 f"out[{name!r}]", str(math.prod(shape)))
+               for name, tdt, shape in want}
+        ptr = {k: (v.data_ptr() or 8) for k, v in res.items()}
+        _check(_lib.rt_resolve_counts_device(self.ctx.handle, sum.data_ptr() or 8,
+                                             count.data_ptr() or 8, n, tonemap, ptr.get("hdr64"),
+                                             ptr.get("hdr32"), ptr.get("ldr")))
+        return res
+
+    def render_adaptive(self, tolerance: float = ADAPTIVE_TOLERANCE,
+                        min_samples: int = ADAPTIVE_MIN_SAMPLES,
+                        lum_floor: float = ADAPTIVE_LUM_FLOOR, schedule=None,
+                        tonemap: int = TONEMAP_NONE, hdr64: bool = True, hdr32: bool = False,
+                        cam=None, **opts):
+        """render_progressive with the stop rule: after each step k of `schedule` it yields
+        (k, outputs), outputs = resolve_counts_device of one state continued to k samples, with
+        outputs["samples"] the state's count tensor (int32 [n], the same tensor at every step:
+        copy it to keep a step's counts).  Enqueued on the context's stream, not synchronised."""
+        rec, _, _ = self._camera_record(cam)
+        aa = max(1, int(rec["aa_samples"][0]))
+        steps = progressive_schedule(aa) if schedule is None else [int(k) for k in schedule]
+        if (not steps or steps[0] < 1 or steps[-1] != aa
+                or any(b <= a for a, b in zip(steps, steps[1:]))):
+            raise ValueError("schedule: increasing sample counts from at least 1, ending at "
+                             "max(1, aa_samples)")
+        state = None
+        for k in steps:
+            state = self.accumulate_adaptive_device(k, tolerance, min_samples, lum_floor,
+                                                    state=state, cam=cam, **opts)
+            out = self.resolve_counts_device(state.sum, state.count, tonemap=tonemap, hdr64=hdr64,
+                                             hdr32=hdr32)
+            out["samples"] = state.count
+            yield k, out
 
     def debug_tile_order(self):
         """The packet kernel's tile-order state for this scene's camera (rt_debug_tile_order):

@@ -81,28 +81,7 @@ __global__ __launch_bounds__(256) void resolve_kernel(const double* sum, size_t 
     const size_t i = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const d3 c = sdiv(mk(sum[3 * i], sum[3 * i + 1], sum[3 * i + 2]), samples);
-    if (out64) {
-        out64[3 * i + 0] = c.x;
-        out64[3 * i + 1] = c.y;
-        out64[3 * i + 2] = c.z;
-    }
-    if (out32) {
-        out32[3 * i + 0] = static_cast<float>(c.x);
-        out32[3 * i + 1] = static_cast<float>(c.y);
-        out32[3 * i + 2] = static_cast<float>(c.z);
-    }
-    if (!ldr) return;
-    const int lo = op == 7 ? 0 : op, hi = op == 7 ? 7 : op + 1;
-    for (int k = lo; k < hi; ++k) {
-        uint8_t* o = ldr + (op == 7 ? static_cast<size_t>(k) * 3 * n : 0) + 3 * i;
-        if (k == 1) {
-            o[0] = reinhard_byte(c.x);
-            o[1] = reinhard_byte(c.y);
-            o[2] = reinhard_byte(c.z);
-        } else {
-            to_color(tonemap_op(c, k), o[0], o[1], o[2]);
-        }
-    }
+    resolve_store(c, i, n, op, out64, out32, ldr);
 }
 
 hipError_t launch_resolve(const double* sum, size_t n, int samples, int op, double* out64,

@@ -271,6 +271,20 @@ rt_status fixup_buffers(rt_context* ctx, size_t px, TraceParams& p) {
     return RT_OK;
 }
 
+rt_status adaptive_buffers(rt_context* ctx, size_t px, AdaptiveArgs& a) {
+    if (px >= (size_t(1) << 32)) return fail(RT_ERR_UNSUPPORTED, "adaptive list above 2^32 pixels");
+    RT_HIP(ctx->adapt_ctl.ensure(sizeof(uint32_t)));
+    if (ctx->adapt_list.bytes < px * sizeof(uint32_t)) {
+        // as fixup_buffers: the list's users are scratch users, the last scratch event covers them
+        if (ctx->scratch_used) RT_HIP(hipEventSynchronize(ctx->scratch_event));
+        RT_HIP(ctx->adapt_list.ensure(px * sizeof(uint32_t)));
+    }
+    RT_HIP(hipMemsetAsync(ctx->adapt_ctl.ptr, 0, sizeof(uint32_t), ctx->stream));
+    a.list = static_cast<uint32_t*>(ctx->adapt_list.ptr);
+    a.list_count = static_cast<uint32_t*>(ctx->adapt_ctl.ptr);
+    return RT_OK;
+}
+
 rt_status check_batch(const rt_camera* cams, int nframes) {
     if (!cams || nframes < 1) return fail(RT_ERR_INVALID_ARG, "frame batch: no cameras");
     for (int f = 0; f < nframes; ++f) {
@@ -631,7 +645,7 @@ rt_status rt_context_destroy(rt_context* ctx) {
     leave_groups(ctx);  // communicators of any group this context is in go first
     for (DeviceBuffer* b : {&ctx->out64, &ctx->out32, &ctx->ldr, &ctx->tm_in, &ctx->tm_out,
                             &ctx->dbg, &ctx->rays, &ctx->counters, &ctx->wf, &ctx->wf_ctl,
-                            &ctx->fix_list, &ctx->fix_ctl})
+                            &ctx->fix_list, &ctx->fix_ctl, &ctx->adapt_list, &ctx->adapt_ctl})
         b->release();
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
     delete ctx;
@@ -1082,6 +1096,17 @@ rt_status rt_debug_fixup_count(rt_context* ctx, uint32_t* pixels) {
     // the count the last fix-variant launch appended to: its fix-up launch zeroed the other one
     RT_HIP(hipMemcpy(pixels, static_cast<const uint32_t*>(ctx->fix_ctl.ptr) + (1 - ctx->fix_parity),
                      sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+rt_status rt_debug_adaptive_listed(rt_context* ctx, uint32_t* pixels) {
+    if (!ctx || !pixels)
+        return fail(RT_ERR_INVALID_ARG, "NULL argument to rt_debug_adaptive_listed");
+    *pixels = 0;
+    if (!ctx->adapt_listing) return RT_OK;
+    DeviceGuard g(ctx->device);
+    RT_HIP(hipStreamSynchronize(ctx->stream));
+    RT_HIP(hipMemcpy(pixels, ctx->adapt_ctl.ptr, sizeof(uint32_t), hipMemcpyDeviceToHost));
     return RT_OK;
 }
 

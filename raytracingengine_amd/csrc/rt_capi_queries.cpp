@@ -41,6 +41,9 @@ public:
     explicit Stage(rt_context* ctx) : ctx_(ctx) {}
     int in(const void* host, size_t bytes) { return plan_.input(host, bytes); }
     int out(void* host, size_t bytes, size_t align = 8) { return plan_.output(host, bytes, align); }
+    int inout(void* host, size_t bytes, bool read, size_t align = 8) {
+        return plan_.inout(host, bytes, read, align);
+    }
     // The requested outputs of `host` for n rays; the first one's item (the others follow).
     template <class Rec, size_t N>
     int outs(const OutField<Rec> (&tab)[N], int outputs, const Rec& host, size_t n) {
@@ -332,6 +335,38 @@ rt_status enqueue_resolve(rt_context* ctx, const void* sum, size_t n, int sample
     return RT_OK;
 }
 
+// RTAMD_ADAPT_LIST=0 (read per call) keeps every pixel in the tile kernel; otherwise the call
+// uses the context's list, scratch like the fix-up list (scratch_wait / scratch_done).
+rt_status enqueue_adaptive(rt_context* ctx, const QueryParams& q, const rt_adaptive_rule& rule,
+                           int fresh, int sample_end, void* sum, void* moments, void* count) {
+    AdaptiveArgs a{};
+    a.tolerance = rule.tolerance;
+    a.lum_floor = rule.lum_floor;
+    a.min_samples = rule.min_samples;
+    a.sample_end = sample_end;
+    a.fresh = fresh != 0;
+    a.sum = f64(sum);
+    a.moments = f64(moments);
+    a.count = static_cast<int32_t*>(count);
+    const char* e = std::getenv("RTAMD_ADAPT_LIST");
+    const bool listing = !(e && std::atoi(e) == 0);
+    if (listing) {
+        RT_TRY(scratch_wait(ctx));
+        RT_TRY(adaptive_buffers(ctx, static_cast<size_t>(q.p.rows) * q.p.width, a));
+    }
+    ctx->adapt_listing = listing;
+    RT_HIP(launch_accumulate_adaptive(q.p, q.path, a, ctx->stream));
+    return listing ? scratch_done(ctx) : RT_OK;
+}
+
+rt_status enqueue_resolve_counts(rt_context* ctx, const void* sum, const void* count, size_t n,
+                                 int tonemap, void* hdr64, void* hdr32, void* ldr) {
+    RT_HIP(launch_resolve_counts(f64(sum), static_cast<const int32_t*>(count), n, tonemap,
+                                 f64(hdr64), static_cast<float*>(hdr32),
+                                 static_cast<uint8_t*>(ldr), ctx->stream));
+    return RT_OK;
+}
+
 // ---- argument checks and parameters of the camera entries -------------------------------------
 // The argument checks of the two camera-ray entries and the camera part of build_params: no scene
 // is involved, and of opts only the row set and the seed are read.
@@ -362,21 +397,12 @@ rt_status camera_rays_params(const rt_context* ctx, const rt_camera* cam,
     return RT_OK;
 }
 
-// The argument checks of the two accumulate entries, made before the context or the scene is
-// dereferenced, then build_params with the members of opts the call reads: the kernel selection
-// (path) and the RT_ERR_UNSUPPORTED of rt_trace_rays for the scene and opts.
-rt_status accumulate_params(rt_context* ctx, const rt_scene* sc, const rt_camera* cam,
-                            const rt_render_opts* opts, int s0, int s1, const void* sum,
-                            const char* entry, QueryParams& q) {
-    const std::string name(entry);
-    if (!ctx || !sc || !cam || !sum) return fail(RT_ERR_INVALID_ARG, "NULL argument to " + name);
-    if (cam->width == 0 || cam->height == 0)
-        return fail(RT_ERR_INVALID_ARG, "zero camera width or height passed to " + name);
-    if (s0 < 0 || s0 >= s1 || s1 > std::max(1, cam->aa_samples))
-        return fail(RT_ERR_INVALID_ARG, "sample range [" + std::to_string(s0) + "," +
-                                            std::to_string(s1) +
-                                            ") empty or outside [0, max(1, aa_samples)] passed to " +
-                                            name);
+// What the entries that continue a sum (accumulate, adaptive) do after their own argument checks:
+// the row set, checked before the context or the scene is dereferenced, then build_params with
+// the members of opts the call reads: the kernel selection (path) and the RT_ERR_UNSUPPORTED of
+// rt_trace_rays for the scene and opts.  name: the entry's, ends every message.
+rt_status sum_params(rt_context* ctx, const rt_scene* sc, const rt_camera* cam,
+                     const rt_render_opts* opts, const std::string& name, QueryParams& q) {
     rt_render_opts o;
     rt_render_opts_default(&o);
     if (opts) {
@@ -395,10 +421,51 @@ rt_status accumulate_params(rt_context* ctx, const rt_scene* sc, const rt_camera
     return RT_OK;
 }
 
-// The checks of the two resolve entries, before the context is dereferenced.
+// The argument checks of the two accumulate entries, made before the context or the scene is
+// dereferenced, then sum_params.
+rt_status accumulate_params(rt_context* ctx, const rt_scene* sc, const rt_camera* cam,
+                            const rt_render_opts* opts, int s0, int s1, const void* sum,
+                            const char* entry, QueryParams& q) {
+    const std::string name(entry);
+    if (!ctx || !sc || !cam || !sum) return fail(RT_ERR_INVALID_ARG, "NULL argument to " + name);
+    if (cam->width == 0 || cam->height == 0)
+        return fail(RT_ERR_INVALID_ARG, "zero camera width or height passed to " + name);
+    if (s0 < 0 || s0 >= s1 || s1 > std::max(1, cam->aa_samples))
+        return fail(RT_ERR_INVALID_ARG, "sample range [" + std::to_string(s0) + "," +
+                                            std::to_string(s1) +
+                                            ") empty or outside [0, max(1, aa_samples)] passed to " +
+                                            name);
+    return sum_params(ctx, sc, cam, opts, name, q);
+}
+
+// The argument checks of the two adaptive entries, in the same place, then sum_params.
+rt_status adaptive_params(rt_context* ctx, const rt_scene* sc, const rt_camera* cam,
+                          const rt_render_opts* opts, const rt_adaptive_rule* rule, int sample_end,
+                          const void* sum, const void* moments, const void* count,
+                          const char* entry, QueryParams& q) {
+    const std::string name(entry);
+    if (!ctx || !sc || !cam || !rule || !sum || !moments || !count)
+        return fail(RT_ERR_INVALID_ARG, "NULL argument to " + name);
+    if (cam->width == 0 || cam->height == 0)
+        return fail(RT_ERR_INVALID_ARG, "zero camera width or height passed to " + name);
+    if (sample_end < 1 || sample_end > std::max(1, cam->aa_samples))
+        return fail(RT_ERR_INVALID_ARG, "sample_end " + std::to_string(sample_end) +
+                                            " outside [1, max(1, aa_samples)] passed to " + name);
+    if (rule->min_samples < 2)
+        return fail(RT_ERR_INVALID_ARG, "rule->min_samples " + std::to_string(rule->min_samples) +
+                                            " < 2 passed to " + name);
+    if (!(rule->tolerance >= 0.0))
+        return fail(RT_ERR_INVALID_ARG, "rule->tolerance negative or NaN passed to " + name);
+    if (!(rule->lum_floor > 0.0))
+        return fail(RT_ERR_INVALID_ARG, "rule->lum_floor not above 0 passed to " + name);
+    return sum_params(ctx, sc, cam, opts, name, q);
+}
+
+// The checks of the resolve entries, before the context is dereferenced.  count_missing: the
+// entry divides by per-pixel counts (samples is then 1) and was given none.
 rt_status check_resolve_args(const rt_context* ctx, const void* sum, size_t n, int samples,
                              int tonemap, const void* hdr64, const void* hdr32, const void* ldr,
-                             const char* entry) {
+                             const char* entry, bool count_missing = false) {
     const std::string name(entry);
     if (samples < 1)
         return fail(RT_ERR_INVALID_ARG, "samples " + std::to_string(samples) + " < 1 passed to " + name);
@@ -408,6 +475,7 @@ rt_status check_resolve_args(const rt_context* ctx, const void* sum, size_t n, i
     if (ldr && tonemap == RT_TONEMAP_NONE)
         return fail(RT_ERR_INVALID_ARG, "bytes requested with RT_TONEMAP_NONE from " + name);
     if (!sum && n > 0) return fail(RT_ERR_INVALID_ARG, "NULL sum passed to " + name);
+    if (count_missing && n > 0) return fail(RT_ERR_INVALID_ARG, "NULL count passed to " + name);
     if (!ctx) return fail(RT_ERR_INVALID_ARG, "NULL context passed to " + name);
     return RT_OK;
 }
@@ -916,6 +984,66 @@ rt_status rt_resolve(rt_context* ctx, const double* sum, size_t n, int samples, 
                               ctx->stream));
     RT_HIP(hipStreamSynchronize(ctx->stream));
     return RT_OK;
+}
+
+// ---- adaptive progressive frames (rt_adaptive.hip) ---------------------------------------------
+rt_status rt_accumulate_adaptive_device(rt_context* ctx, const rt_scene* sc, const rt_camera* cam,
+                                        const rt_render_opts* opts, const rt_adaptive_rule* rule,
+                                        int fresh, int sample_end, void* d_sum, void* d_moments,
+                                        void* d_count) {
+    QueryParams q;
+    RT_TRY(adaptive_params(ctx, sc, cam, opts, rule, sample_end, d_sum, d_moments, d_count,
+                           "rt_accumulate_adaptive_device", q));
+    DeviceGuard g(ctx->device);
+    return enqueue_adaptive(ctx, q, *rule, fresh, sample_end, d_sum, d_moments, d_count);
+}
+
+rt_status rt_accumulate_adaptive(rt_context* ctx, const rt_scene* sc, const rt_camera* cam,
+                                 const rt_render_opts* opts, const rt_adaptive_rule* rule,
+                                 int fresh, int sample_end, double* sum, double* moments,
+                                 int32_t* count) {
+    QueryParams q;
+    RT_TRY(adaptive_params(ctx, sc, cam, opts, rule, sample_end, sum, moments, count,
+                           "rt_accumulate_adaptive", q));
+    DeviceGuard g(ctx->device);
+    const size_t px = static_cast<size_t>(q.p.rows) * q.p.width;
+    Stage s(ctx);  // the state so far goes up unless the call is fresh; all of it comes back
+    const int i_sum = s.inout(sum, px * 3 * sizeof(double), !fresh),
+              i_mom = s.inout(moments, px * 2 * sizeof(double), !fresh),
+              i_cnt = s.inout(count, px * sizeof(int32_t), !fresh, sizeof(int32_t));
+    RT_TRY(s.upload());
+    RT_TRY(enqueue_adaptive(ctx, q, *rule, fresh, sample_end, s.at(i_sum), s.at(i_mom),
+                            s.at(i_cnt)));
+    return s.finish();
+}
+
+rt_status rt_resolve_counts_device(rt_context* ctx, const void* d_sum, const void* d_count,
+                                   size_t n, int tonemap, void* d_hdr64, void* d_hdr32,
+                                   void* d_ldr) {
+    RT_TRY(check_resolve_args(ctx, d_sum, n, 1, tonemap, d_hdr64, d_hdr32, d_ldr,
+                              "rt_resolve_counts_device", !d_count));
+    if (n == 0) return RT_OK;
+    DeviceGuard g(ctx->device);
+    return enqueue_resolve_counts(ctx, d_sum, d_count, n, tonemap, d_hdr64, d_hdr32, d_ldr);
+}
+
+rt_status rt_resolve_counts(rt_context* ctx, const double* sum, const int32_t* count, size_t n,
+                            int tonemap, double* hdr64, float* hdr32, uint8_t* ldr) {
+    RT_TRY(check_resolve_args(ctx, sum, n, 1, tonemap, hdr64, hdr32, ldr, "rt_resolve_counts",
+                              !count));
+    if (n == 0) return RT_OK;
+    DeviceGuard g(ctx->device);
+    const size_t planes = tonemap == RT_TONEMAP_COUNT ? RT_TONEMAP_COUNT : 1;
+    Stage s(ctx);  // the counts (4 B each) after the arrays of doubles, before the floats and bytes
+    const int i_sum = s.in(sum, n * 3 * sizeof(double)),
+              i_64 = s.out(hdr64, hdr64 ? n * 3 * sizeof(double) : 0),
+              i_32 = s.out(hdr32, hdr32 ? n * 3 * sizeof(float) : 0, sizeof(float)),
+              i_cnt = s.in(count, n * sizeof(int32_t)),
+              i_ldr = s.out(ldr, ldr ? planes * n * 3 : 0, 1);
+    RT_TRY(s.upload());
+    RT_TRY(enqueue_resolve_counts(ctx, s.at(i_sum), s.at(i_cnt), n, tonemap, s.at(i_64),
+                                  s.at(i_32), s.at(i_ldr)));
+    return s.finish();
 }
 
 rt_status rt_tonemap(rt_context* ctx, const double* hdr, size_t n, int op, uint8_t* out) {

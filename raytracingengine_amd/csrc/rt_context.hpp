@@ -85,6 +85,10 @@ struct rt_context {
     // context like the counters (ordered across streams by scratch_wait / scratch_done)
     rtamd::DeviceBuffer fix_list, fix_ctl;
     int fix_parity = 0;  // which of the two counts of fix_ctl the next fix-variant launch uses
+    // the adaptive frames' list of unfinished pixels (AdaptiveArgs.list) and its count, scratch
+    // of the context like the fix-up list; adapt_listing: the latest adaptive call used them
+    rtamd::DeviceBuffer adapt_list, adapt_ctl;
+    bool adapt_listing = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> free_events;
     double timed_ms = 0.0;
@@ -282,6 +286,10 @@ rt_status packet_batch_images(rt_context* ctx, const rt_scene* sc, const rt_came
 // latest such user.
 rt_status scratch_wait(rt_context* ctx);
 rt_status scratch_done(rt_context* ctx);
+// The list of an adaptive call over px pixels (rt_capi_queries.cpp): grows ctx->adapt_list as
+// fixup_buffers grows its list and zeroes the count on ctx->stream.  The caller has made
+// scratch_wait and makes scratch_done after its launches.
+rt_status adaptive_buffers(rt_context* ctx, size_t px, AdaptiveArgs& a);
 // The two ray counters [trace, shadow]: zeroed on ctx->stream; read into c, either enqueued on
 // ctx->stream (c is valid once the stream has been synchronized) or with a blocking copy.
 rt_status counters_zero(rt_context* ctx);

@@ -376,6 +376,27 @@ hipError_t launch_accumulate_samples(const TraceParams& p, int path, int s0, int
                                      hipStream_t stream);
 hipError_t launch_resolve(const double* sum, size_t n, int samples, int op, double* out64,
                           float* out32, uint8_t* ldr, hipStream_t stream);
+// Adaptive progressive frames (rt_adaptive.hip).  The rule of rt_accumulate_adaptive_device
+// (rt_capi.h) over the pixels of p's row set, on the rows-local state sum (3 doubles a pixel),
+// moments (2) and count (int32): each pixel continues from its count while the rule wants a
+// sample, up to sample_end.  fresh: the state is not read.  list / list_count: a list of
+// p.rows * p.width row-local pixel indices and its count, zero before the launch — the tile
+// kernel appends the pixels its waves leave unfinished, the list kernel (launched after it)
+// finishes them; list == null: the tile kernel finishes every pixel, one launch.
+struct AdaptiveArgs {
+    double tolerance, lum_floor;
+    int32_t min_samples, sample_end, fresh;
+    double* sum;
+    double* moments;
+    int32_t* count;
+    uint32_t* list;
+    uint32_t* list_count;
+};
+hipError_t launch_accumulate_adaptive(const TraceParams& p, int path, const AdaptiveArgs& a,
+                                      hipStream_t stream);
+// launch_resolve with each pixel's own count as the divisor; a count of 0: the pixel is {0,0,0}.
+hipError_t launch_resolve_counts(const double* sum, const int32_t* count, size_t n, int op,
+                                 double* out64, float* out32, uint8_t* ldr, hipStream_t stream);
 hipError_t launch_tonemap(const double* hdr, size_t n, int op, uint8_t* out, hipStream_t stream);
 hipError_t launch_debug_f64(const double* x, const double* y, size_t n, double* out,
                             hipStream_t stream);

@@ -40,6 +40,12 @@ struct StagePlan {
         return count++;
     }
 
+    // An array the query continues in place: an output that is also an input when `read` is set.
+    int inout(void* host, size_t bytes, bool read, size_t align = 8) {
+        item[count].src = read ? host : nullptr;
+        return output(host, bytes, align);
+    }
+
     // kShort and kBytesFirst exist for the host test's mutants only (an item one byte into its
     // predecessor; the byte-sized items placed before the others).
     template <bool kShort = false, bool kBytesFirst = false>

@@ -360,6 +360,36 @@ __device__ __forceinline__ void store_pixel(const TraceParams& P, size_t o, d3 v
     }
 }
 
+// What the resolve kernels (rt_accumulate.hip, rt_adaptive.hip) write for pixel i of n with value
+// c: the float64 and float32 pixels and the tonemapped bytes.  The bytes are tonemap_kernel's
+// (rt_trace.hip): tonemap_op + to_color, reinhard_byte for operator 1; op == 7 writes the seven
+// operators' planes in tonemapAll() order.  A null output is not written; op is read only with ldr.
+__device__ __forceinline__ void resolve_store(d3 c, size_t i, size_t n, int op, double* out64,
+                                              float* out32, uint8_t* ldr) {
+    if (out64) {
+        out64[3 * i + 0] = c.x;
+        out64[3 * i + 1] = c.y;
+        out64[3 * i + 2] = c.z;
+    }
+    if (out32) {
+        out32[3 * i + 0] = static_cast<float>(c.x);
+        out32[3 * i + 1] = static_cast<float>(c.y);
+        out32[3 * i + 2] = static_cast<float>(c.z);
+    }
+    if (!ldr) return;
+    const int lo = op == 7 ? 0 : op, hi = op == 7 ? 7 : op + 1;
+    for (int k = lo; k < hi; ++k) {
+        uint8_t* o = ldr + (op == 7 ? static_cast<size_t>(k) * 3 * n : 0) + 3 * i;
+        if (k == 1) {
+            o[0] = reinhard_byte(c.x);
+            o[1] = reinhard_byte(c.y);
+            o[2] = reinhard_byte(c.z);
+        } else {
+            to_color(tonemap_op(c, k), o[0], o[1], o[2]);
+        }
+    }
+}
+
 // Camera::getRay (Math.h:99-121) for pixel (x, y) and AA sample s; sample 0 is never jittered.
 __device__ __forceinline__ d3 camera_dir(const TraceParams& P, d3 cam, uint32_t x, uint32_t y,
                                          uint64_t pix, int s) {
